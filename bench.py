@@ -2,9 +2,16 @@
 """bench.py — BASELINE.json metric: "GiB/s device-resident fp32 bucket reduce
 per GPU; % of HBM3E peak".
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
   (N > 1: one rank per GPU under torch.distributed.run; without a launcher
   around it, bench.py starts that launcher itself as a child)
+
+A plain run sets up, warms up, times the K steps and prints the line.
+--full adds everything measured or checked beside the headline: the parity
+check of the timed outputs, the same-buffer rate, the other kernel families,
+host_staged, cpu_baseline and c1 at N = 1, the --extras sub-benchmarks at
+N > 1. --dump-outputs DIR writes the last timed step's output as
+DIR/<name>.npy (z at N = 1, rank 0's all_reduce at N > 1).
 
 N = 1 (BASELINE.json configs[1], C2): one step = one launch of the HIP bucket
 reduce z = x + y over a device-resident 256 MiB fp32 bucket (67,108,864
@@ -129,7 +136,43 @@ def parse():
                          "sub-benchmarks, line) with a single rank")
     ap.add_argument("--profile-only", action="store_true",
                     help="only the timed kernel loop (for rocprofv3 runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity check of the timed outputs, the "
+                         "same-buffer rate, N=1: kernel families, host-staged, CPU baseline "
+                         "and C1 (each with its --no-* switch); N>1: the --extras "
+                         "sub-benchmarks. Without it the run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as "
+                         "DIR/<name>.npy (float32; a fixed, seeded sample of an output "
+                         "larger than the size limit)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files of one run together
+DUMP_EDGE = 4096  # elements kept from either end of a sampled output
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every {name: 1-D device tensor} as path/<name>.npy in
+    float32 (float64 stays float64). An output within its share of half of
+    DUMP_LIMIT_BYTES is written whole; of a larger one, its first and last
+    DUMP_EDGE elements and a sample at sorted indices drawn from
+    numpy's default_rng(0): the same elements in every run of the same
+    arguments, so two builds' files compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // 2 // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.dtype != torch.float64:
+            t = t.float()
+        n, keep = t.numel(), budget // t.element_size()
+        if n > keep:
+            idx = np.random.default_rng(0).integers(0, n, keep - 2 * DUMP_EDGE)
+            idx = np.concatenate([np.arange(DUMP_EDGE), np.sort(idx),
+                                  np.arange(n - DUMP_EDGE, n)])
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def load_traffic():
@@ -951,17 +994,24 @@ def main():
         if rank == 0:
             print(json.dumps({"kernel_us": kernel_s * 1e6}))
         return
+    if args.dump_outputs and not multi and rank == 0:
+        # the last timed launch's output (launch i writes set i % len(sets))
+        dump_outputs(args.dump_outputs, {"z": sets[(args.steps - 1) % len(sets)][2]})
     # same buffers every launch: the 256 MiB output can stay in the Infinity
-    # Cache between launches; reported beside, never as `value`
-    hot_s, _, _ = time_local_reduce(lib, sets[:1], args.steps, args.warmup, world)
+    # Cache between launches; reported beside, never as `value` (--full: a
+    # timed loop of its own)
+    hot_s = None
+    if args.full:
+        hot_s, _, _ = time_local_reduce(lib, sets[:1], args.steps, args.warmup, world)
 
     out = {}
     if not multi:
         step_s = wall_local / args.steps
         value = s_bytes / kernel_s / 2**30
-        # parity check of every timed output (full oracle check: tests/)
-        for xs, ys, zs in sets:
-            assert torch.equal(zs, xs + ys)
+        if args.full:
+            # parity check of every timed output (full oracle check: tests/)
+            for xs, ys, zs in sets:
+                assert torch.equal(zs, xs + ys)
         workload = "C2: device-resident z = x + y, one 256 MiB fp32 bucket"
         parallelism = "single GPU"
     else:
@@ -1056,6 +1106,9 @@ def main():
         step_s, phase_us = _timed_phases(
             prim_ex, lambda: prim_ex.all_reduce_(pieces, average=True, coalesce=coalesce),
             args.steps, args.warmup, dev, world)
+        if args.dump_outputs and rank == 0:
+            # rank 0's buckets as the last timed all-reduce left them
+            dump_outputs(args.dump_outputs, {"all_reduce": gb.views[0]})
         value = s_bytes / step_s / 2**30  # per GPU, as the metric says
         busbw = 2 * (world - 1) / world * s_bytes / step_s / 1e9
         _progress(rank, "C3 %.3f ms per step" % (step_s * 1e3))
@@ -1132,7 +1185,7 @@ def main():
         dog.daemon = True
         dog.start()
         t_extras = time.perf_counter()
-        wanted = args.extras.split(",")
+        wanted = args.extras.split(",") if args.full else []
         for key, fn in extra:
             if args.no_extra:
                 break
@@ -1170,7 +1223,7 @@ def main():
                   dict(value=value, step_s=step_s, kernel_s=kernel_s, workload=workload,
                        parallelism=parallelism))
     res.update(out)
-    if rank == 0 and not multi:
+    if rank == 0 and not multi and args.full:
         if not args.no_kernels:
             _progress(rank, "kernel families")
             try:
@@ -1208,6 +1261,7 @@ def _result(args, world, sets, s_bytes, n, hot_s, prim):
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(step_s * 1e3, 4),
+        "full": bool(args.full),
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -1238,7 +1292,7 @@ def _result(args, world, sets, s_bytes, n, hot_s, prim):
             "bytes_per_launch": 3 * s_bytes,
             "kernel_us": round(kernel_s * 1e6, 2),
             "rotate": len(sets),
-            "same_buffer_GBps": round(3 * s_bytes / hot_s / 1e9, 1),
+            "same_buffer_GBps": None if hot_s is None else round(3 * s_bytes / hot_s / 1e9, 1),
         },
     }
 

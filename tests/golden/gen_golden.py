@@ -5,7 +5,7 @@ Run in the build container (needs /root/reference):
     make -C oracle ref && python tests/golden/gen_golden.py
 
 Outputs (data only — inputs and expected outputs):
-  transform2.npz + transform2.json
+  transform2_0.npz, transform2_1.npz + transform2.json
       std_transform_2 of the reference, compiled from its own sources
       (srcs/go/kungfu/base/{op.cpp,f16.c,dtype.c}, see oracle/Makefile `ref`),
       over dtype x op x n x input kind. Small cases are stored whole; large
@@ -45,6 +45,12 @@ DTYPES = {
 OPS = {"sum": 0, "min": 1, "max": 2, "prod": 3}
 SMALL_N = [1, 7, 8, 9, 31, 1027]
 LARGE_N = [262144, 262147]  # one full 1 MiB fp32 chunk, and ragged
+NPZ_PARTS = 2  # the stored cases in this many files, each below 1 MiB
+
+
+def npz_part(key):
+    """The transform2_<part>.npz that holds array `key` (cNNNN_x/_y/_z)."""
+    return int(key[1:5]) // len(SMALL_N) % NPZ_PARTS  # whole runs of SMALL_N in turn
 
 
 def gen_inputs(name, n, seed, kind):
@@ -172,7 +178,9 @@ def main():
         index.append(dict(id=key, dtype="f32", code=0x20408, op="sum", opcode=0,
                           n=1023, seed=77, kind="alias_" + alias, stored=True))
         cid += 1
-    np.savez_compressed(os.path.join(HERE, "transform2.npz"), **arrays)
+    for part in range(NPZ_PARTS):
+        np.savez_compressed(os.path.join(HERE, "transform2_%d.npz" % part),
+                            **{k: v for k, v in arrays.items() if npz_part(k) == part})
     with open(os.path.join(HERE, "transform2.json"), "w") as f:
         json.dump(index, f, indent=0)
 

@@ -23,7 +23,9 @@ def index():
 
 def arrays():
     if "npz" not in _cache:
-        _cache["npz"] = dict(np.load(os.path.join(GOLDEN, "transform2.npz")))
+        _cache["npz"] = {}
+        for part in range(gen_golden.NPZ_PARTS):
+            _cache["npz"].update(np.load(os.path.join(GOLDEN, "transform2_%d.npz" % part)))
     return _cache["npz"]
 
 

@@ -31,7 +31,7 @@ def test_bench_n2_rehearsal_with_p2p_children():
            "--master-addr", "127.0.0.1", "--master-port", str(_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
            "--device-index", "0", "--steps", "3", "--warmup", "1", "--elems", str(4 << 20),
-           "--extras", "c4_torch,c5_torch,c3_p2p,c5_p2p", "--extras-timeout", "100"]
+           "--full", "--extras", "c4_torch,c5_torch,c3_p2p,c5_p2p", "--extras-timeout", "100"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -155,7 +155,7 @@ def test_bench_exchange_branch_single_rank_rccl():
     extras = ("c4,c5,c5_pipe,c5_overlap,c4_overlap,c4_pipe,c4_rs_avg,c4_named,c3_pipe,c3_a2a,"
               "c3_fused,c4_torch,c5_torch")
     argv = ["--rehearse-exchange", "--steps", "3", "--warmup", "1", "--elems", str(4 << 20),
-            "--extras", extras, "--extras-timeout", "200"]
+            "--full", "--extras", extras, "--extras-timeout", "200"]
     code = _BRANCH_CHILD % (ROOT, os.path.join(ROOT, "tests"), argv)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=260,
                        cwd=ROOT, env=env)
@@ -243,7 +243,7 @@ def test_bench_native_branch_over_ipc_transport(world):
            str(world), "--master-addr", "127.0.0.1", "--master-port", str(_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--dist-backend", "gloo",
            "--device-index", "0", "--test-transport", "ipc", "--steps", "3", "--warmup", "1",
-           "--elems", str(4 << 20), "--extras", ",".join(_IPC_EXTRAS),
+           "--elems", str(4 << 20), "--full", "--extras", ",".join(_IPC_EXTRAS),
            "--extras-timeout", "150" if world <= 4 else "400"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240 if world <= 4 else 560,
                        cwd=ROOT, env=env)

@@ -182,17 +182,31 @@ def session_async_binary(tmp_path_factory):
     return out
 
 
+@pytest.fixture
+def sock_dir():
+    """A directory for the sessions' unix sockets. A socket's path has to fit
+    sockaddr_un's 108 bytes with its name (about 35 characters) on it;
+    pytest's tmp_path, which stacks the user's and the test's names on the
+    temporary directory, can pass that on its own. So: a directory straight
+    under the temporary directory, as the other session tests use, or under
+    /tmp where even that is too deep."""
+    import tempfile
+    base = tempfile.gettempdir()
+    with tempfile.TemporaryDirectory(prefix="kfs", dir=base if len(base) <= 56 else "/tmp") as d:
+        yield d
+
+
 @pytest.mark.parametrize("np_", [2, 3, 4])
-def test_c_session_async_any_order(session_async_binary, tmp_path, np_):
-    r = subprocess.run([session_async_binary, str(np_), "2", str(tmp_path)],
+def test_c_session_async_any_order(session_async_binary, sock_dir, np_):
+    r = subprocess.run([session_async_binary, str(np_), "2", sock_dir],
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr
 
 
 @pytest.mark.parametrize("np_", [2, 3, 4])
-def test_c_session_dead_peer_fails_calls(session_async_binary, tmp_path, np_):
+def test_c_session_dead_peer_fails_calls(session_async_binary, sock_dir, np_):
     """The last rank destroys its session once every session is up; the
     others' async all-reduces must fail within 30 s (C++ host, threads)."""
-    r = subprocess.run([session_async_binary, str(np_), "1", str(tmp_path), "dead"],
+    r = subprocess.run([session_async_binary, str(np_), "1", sock_dir, "dead"],
                        capture_output=True, text=True, timeout=90)
     assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr

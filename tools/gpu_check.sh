@@ -33,7 +33,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python tools/pmc_traffic.py "$OUT/pmc_FETCH_SIZE" "$OUT/pmc_WRITE_SIZE" "$OUT/traffic.json" > /dev/null && \
     mkdir -p profiles && cp "$OUT/traffic.json" profiles/traffic.json
-step bench 600 python bench.py || exit $?
+step bench 600 python bench.py --full || exit $?
 tail -1 "$OUT/bench.log" > "$OUT/bench.json"
 for extra in "$@"; do
   case $extra in
