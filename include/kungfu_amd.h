@@ -158,6 +158,63 @@ int kf_sma_blend(void *v, const void *sum, size_t n, KungFu_Datatype dt,
 int kf_sma_blend_batch(void *const *vs, const void *const *sums, const size_t *counts, int nb,
                        KungFu_Datatype dt, int np, double alpha, void *stream);
 
+/* ---- gradient monitors: segmented squared norms ------------------------- */
+
+/* What MonitorGradientNoiseScaleOptimizer and MonitorGradientVarianceOptimizer
+ * (grad_noise_scale.py, grad_variance.py) need beyond the sync reduce: many
+ * tensors, each reduced to one fp64 scalar, in one read-only pass.
+ *
+ * A plan holds nseg segments: a[s] (and b[s], or b == NULL for a plan that
+ * only runs KF_NORM_SQ), counts[s] elements of `dt` (f32, f16, bf16 or f64;
+ * anything else: KF_ERR_DTYPE). Pointers are device pointers aligned to the
+ * element size only; a count may be 0; nseg >= 1 with no upper limit.
+ * kf_segnorm_create uploads the segment table to HBM and allocates the
+ * per-block partials workspace on the current device (once per optimizer:
+ * bucket views never move). It returns NULL on failure, with kf_last_error()
+ * starting with the status name ("KF_ERR_ARG: ...").
+ *
+ * kf_segnorm_run only queues launches on `stream`: no allocation, no host
+ * sync, safe to capture into a hipGraph. It writes nseg + 1 doubles to the
+ * device array `out`:
+ *   KF_NORM_SQ   out[s] = sum_i a_s[i]^2
+ *   KF_NORM_VAR  out[s] = sum_i d_i^2, d_i = fl_T(a_s[i] - fl_T(b_s[i] * b_s[i]))
+ *                (square_grad - tf.square(grad), grad_variance.py:51-54, in the
+ *                tensors' own dtype T: every operation rounded to T, no FMA
+ *                contraction; f16 / bf16 compute in fp32 and round to T after
+ *                the multiply and after the subtract). Needs b: KF_ERR_ARG.
+ *   out[nseg]    = out[0] + out[1] + ... left to right in fp64, or with
+ *                KF_NORM_TOTAL_SQRT or-ed into the mode the same sum of
+ *                sqrt(out[s]) (sum_t ||var_t||, grad_variance.py:55-58).
+ * Accumulation is fp64 from the first add: |out[s] - exact_s| <=
+ * (n_s + 2) * 2^-53 * exact_s; fp32 inputs near FLT_MAX do not overflow and
+ * fp32 subnormals are not flushed. A count of 0 gives 0.0. The same plan and
+ * the same input bytes give the same output bits on every run (no atomics;
+ * partials are combined in a fixed order after a launch boundary).
+ * A plan's workspace serves one run at a time in stream order: runs of one
+ * plan on two streams at once are the caller's to order. */
+typedef struct kf_segnorm kf_segnorm_t; /* opaque plan */
+enum { KF_NORM_SQ = 0, KF_NORM_VAR = 1 }; /* mode */
+#define KF_NORM_TOTAL_SQRT 0x100 /* or-ed into mode */
+
+kf_segnorm_t *kf_segnorm_create(const void *const *a, const void *const *b /* NULL: SQ only */,
+                                const size_t *counts, int nseg, KungFu_Datatype dt);
+int kf_segnorm_run(kf_segnorm_t *p, int mode, double *out /* device, nseg + 1 */, void *stream);
+void kf_segnorm_destroy(kf_segnorm_t *p);
+
+/* The gradient noise scale's running estimate, on the device so that a
+ * monitored step needs no host sync (monitor.py:10-17, ema.hpp:19-27,
+ * collective.cpp:298-300; fp32, no contraction, one lane):
+ *   Gs = (float)*sq_small, Gb = (float)*sq_big
+ *   G = (1 / (bb - bs)) * (bb * Gb - bs * Gs)
+ *   S = (1 / (1 / bs - 1 / bb)) * (Gs - Gb)
+ *   each EMA: x on its first update, else alpha * v + (1 - alpha) * x
+ *   noise_scale = s_ema / g_ema
+ * state is 4 device floats {g_ema, s_ema, noise_scale, has_value}; all zero
+ * means "no value yet". bb == bs (one peer) follows IEEE (inf or NaN), as the
+ * reference. alpha <= 0: KF_ERR_ARG (collective.cpp:283). */
+int kf_noise_scale_update(const double *sq_small, const double *sq_big, float batch_small,
+                          float batch_big, float alpha, float *state, void *stream);
+
 /* ---- runtime / diagnostics ---------------------------------------------- */
 
 /* HIP device count visible to the library (0 on a GPU-less host). */

@@ -98,7 +98,16 @@ EXPORTED = (
     "kf_session_info",
     "kf_exchange_create_local",
     "kf_hier_all_reduce",
+    "kf_segnorm_create",
+    "kf_segnorm_run",
+    "kf_segnorm_destroy",
+    "kf_noise_scale_update",
 )
+
+# kf_segnorm_run modes (include/kungfu_amd.h)
+NORM_SQ = 0
+NORM_VAR = 1
+NORM_TOTAL_SQRT = 0x100
 
 STATUS = {
     0: "KF_OK",
@@ -351,6 +360,15 @@ def load():
     lib.kf_hier_all_reduce.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
                                        c_int, c_int, c_int, ctypes.c_char_p, c_void_p]
     lib.kf_hier_all_reduce.restype = c_int
+    lib.kf_segnorm_create.argtypes = [P(c_void_p), P(c_void_p), P(c_size_t), c_int, c_int]
+    lib.kf_segnorm_create.restype = c_void_p
+    lib.kf_segnorm_run.argtypes = [c_void_p, c_int, c_void_p, c_void_p]
+    lib.kf_segnorm_run.restype = c_int
+    lib.kf_segnorm_destroy.argtypes = [c_void_p]
+    lib.kf_segnorm_destroy.restype = None
+    lib.kf_noise_scale_update.argtypes = [c_void_p, c_void_p, ctypes.c_float, ctypes.c_float,
+                                          ctypes.c_float, c_void_p, c_void_p]
+    lib.kf_noise_scale_update.restype = c_int
     _lib = lib
     # HIP resources go back while the runtime is alive, before the C exit
     # handlers run (include/kungfu_amd.h kf_shutdown)

@@ -892,6 +892,12 @@ int transform2_host(const void *x, const void *y, void *out, size_t n,
 
 }  // namespace
 
+namespace kf
+{
+// kf_last_error's text, for the library's other sources (kf_segnorm.hip)
+void set_last_error(const std::string &msg) { t_last_error = msg; }
+}  // namespace kf
+
 extern "C" {
 
 uint32_t kungfu_type_size(KungFu_Datatype dt)

@@ -177,3 +177,111 @@ def sma_blend_batch_(vs, sums, np_, alpha, stream=None):
                                 _stream(stream, vs[0].device))
     _lib.check(rc, "kf_sma_blend_batch")
     return vs
+
+
+_NORM_DTYPES = (torch.float32, torch.float16, torch.bfloat16, torch.float64)
+
+
+class SegNorm:
+    """Squared norms of many tensors in one pass (kf_segnorm_*): a plan over
+    a list of tensors, or of (a, b) tensor pairs, of one float dtype on one
+    GPU. The plan keeps the tensors alive and reads them where they are on
+    every run, so build it once over views that never move (bucket views).
+
+    run(mode) returns a device fp64 tensor of nseg + 1 values:
+      "sq"   out[s] = sum a_s[i]^2
+      "var"  out[s] = sum d_i^2, d_i = fl(a_s[i] - fl(b_s[i] * b_s[i])) in the
+             tensors' dtype (needs pairs)
+      out[nseg] = out[0] + ... + out[nseg - 1] left to right, or with
+      total_sqrt=True the sum of sqrt(out[s]).
+    fp64 accumulation, |out[s] - exact| <= (n_s + 2) * 2^-53 * exact, the same
+    bits on every run of the same bytes. Nothing is allocated and the host is
+    not synchronised once `out` is given, so a run can be captured into a
+    graph. Runs of one plan on two streams at once are the caller's to order
+    (one workspace per plan)."""
+
+    MODES = {"sq": _lib.NORM_SQ, "var": _lib.NORM_VAR}
+
+    def __init__(self, tensors):
+        tensors = list(tensors)
+        if not tensors:
+            raise ValueError("SegNorm: at least one segment")
+        paired = isinstance(tensors[0], (tuple, list))
+        a = [t[0] for t in tensors] if paired else tensors
+        b = [t[1] for t in tensors] if paired else None
+        _check_dev(a + (b or []))
+        first = a[0]
+        if first.dtype not in _NORM_DTYPES:
+            raise TypeError("SegNorm: unsupported dtype %s" % first.dtype)
+        for t in a + (b or []):
+            if t.dtype != first.dtype or t.device != first.device:
+                raise ValueError("SegNorm: one dtype and one device per plan")
+        if b is not None:
+            for x, y in zip(a, b):
+                if x.numel() != y.numel():
+                    raise ValueError("SegNorm: a pair's tensors differ in length")
+        self._keep = (a, b)
+        self.nseg = len(a)
+        self.paired = paired
+        self.device = first.device
+        self.counts = [t.numel() for t in a]
+        lib = _lib.load()
+        cnt = (ctypes.c_size_t * self.nseg)(*self.counts)
+        with torch.cuda.device(self.device):
+            self._plan = lib.kf_segnorm_create(
+                _lib.ptr_array([t.data_ptr() for t in a]),
+                _lib.ptr_array([t.data_ptr() for t in b]) if paired else None,
+                cnt, self.nseg, int(kungfu_dtype(first)))
+        if not self._plan:
+            raise _lib.KungFuAMDError("kf_segnorm_create failed: %s"
+                                      % lib.kf_last_error().decode())
+
+    def run(self, mode="sq", out=None, stream=None, total_sqrt=False):
+        if self._plan is None:
+            raise ValueError("SegNorm: closed")
+        m = self.MODES[mode] if isinstance(mode, str) else int(mode)
+        if total_sqrt:
+            m |= _lib.NORM_TOTAL_SQRT
+        if out is None:
+            out = torch.empty(self.nseg + 1, dtype=torch.float64, device=self.device)
+        else:
+            _check_dev([out])
+            if (out.dtype != torch.float64 or out.numel() != self.nseg + 1
+                    or out.device != self.device):
+                raise ValueError("SegNorm.run: out must be %d float64 values on %s"
+                                 % (self.nseg + 1, self.device))
+        rc = _lib.load().kf_segnorm_run(self._plan, m, out.data_ptr(),
+                                        _stream(stream, self.device))
+        _lib.check(rc, "kf_segnorm_run", source="")
+        return out
+
+    def close(self):
+        if self._plan is not None:
+            _lib.load().kf_segnorm_destroy(self._plan)
+            self._plan = None
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def noise_scale_update_(sq_small, sq_big, batch_small, batch_big, alpha, state, stream=None):
+    """One update of the gradient noise scale's running estimate on the device
+    (kf_noise_scale_update: monitor.py:10-17 and the NoiseScale op, in fp32).
+    sq_small, sq_big: fp64 device scalars (|g_local|^2, |g_averaged|^2);
+    state: 4 fp32 device values {g_ema, s_ema, noise_scale, has_value}, all
+    zero before the first update. Returns state."""
+    _check_dev([sq_small, sq_big, state])
+    if sq_small.dtype != torch.float64 or sq_big.dtype != torch.float64 or \
+            sq_small.numel() != 1 or sq_big.numel() != 1:
+        raise ValueError("noise_scale_update_: sq_small and sq_big are fp64 scalars")
+    if state.dtype != torch.float32 or state.numel() != 4:
+        raise ValueError("noise_scale_update_: state is 4 float32 values")
+    rc = _lib.load().kf_noise_scale_update(sq_small.data_ptr(), sq_big.data_ptr(),
+                                           float(batch_small), float(batch_big), float(alpha),
+                                           state.data_ptr(), _stream(stream, state.device))
+    _lib.check(rc, "kf_noise_scale_update", source="")
+    return state

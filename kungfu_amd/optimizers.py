@@ -13,6 +13,11 @@ Operator surface kept from the reference:
 * ``SynchronousAveragingOptimizer(optimizer, named_parameters=None, alpha=0.1)``
   — SMA (sma_sgd.py:9-74): before the local update every variable with a
   gradient becomes ``(1 - alpha) * v + alpha * allreduce_sum(v) / np``.
+* ``MonitorGradientNoiseScaleOptimizer`` and ``MonitorGradientVarianceOptimizer``
+  (grad_noise_scale.py, grad_variance.py): S-SGD (sum, / np) that on every
+  ``monitor_interval``-th step also reduces the gradient buckets to scalars
+  on the device (ops.SegNorm: one read-only pass, fp64) — the gradient noise
+  scale's running estimate, or the per-parameter gradient variance.
 
 Buckets: parameters are grouped (in registration order, per dtype/device) into
 flat padded device buckets (``collective.GradBuckets``); ``p.grad`` (S-SGD) or
@@ -134,21 +139,27 @@ class _SyncSGD(_Bucketed):
                 p.grad = v
         self._kf_reset_overlap()
 
+    @staticmethod
+    def _kf_place(ps, gb):
+        """Every gradient of one group into its bucket view (zeros for a
+        parameter without one)."""
+        for p, view in zip(ps, gb.views):
+            g = p.grad
+            v = view.view_as(p)
+            if g is None:
+                v.zero_()
+                p.grad = v
+            elif g.data_ptr() != v.data_ptr():
+                v.copy_(g)
+                p.grad = v
+
     def sync_gradients(self):
         if self._kf_overlap:
             return self._kf_finish_overlap()
         if self._kf_groups is None:
             self._kf_build(None)
         for ps, gb in self._kf_groups:
-            for p, view in zip(ps, gb.views):
-                g = p.grad
-                v = view.view_as(p)
-                if g is None:
-                    v.zero_()
-                    p.grad = v
-                elif g.data_ptr() != v.data_ptr():
-                    v.copy_(g)
-                    p.grad = v
+            self._kf_place(ps, gb)
             self._kf_ex.all_reduce_(gb.buckets, op=self._kf_op,
                                     average=self._kf_average)
 
@@ -180,6 +191,209 @@ def SynchronousSGDOptimizer(optimizer, named_parameters=None, op=None,
             raise ValueError("overlap=True needs an exchange with start_() "
                              "(collective.Exchange)")
         opt._kf_setup_overlap()
+    return opt
+
+
+class _Monitored(_SyncSGD):
+    """S-SGD (sum, / np) with a monitor on every `monitor_interval`-th step
+    (step counter from 0). The monitor reads each gradient bucket where it is
+    with one segmented-norm pass (ops.SegNorm) and leaves its results on the
+    device; a step that is not monitored is exactly plain S-SGD, and a
+    monitored one changes no gradient either.
+
+    overlap=True is not offered: the local norm has to be read after the last
+    gradient is in its bucket and before that bucket is exchanged in place,
+    which is the window the overlapped schedule removes."""
+
+    def _kf_setup_monitor(self, named_parameters, exchange, bucket_bytes, monitor_interval,
+                          overlap):
+        if overlap:
+            raise ValueError("the monitoring optimizers have no overlap=True: the local "
+                             "norm is read before a bucket is exchanged in place")
+        if int(monitor_interval) < 1:
+            raise ValueError("monitor_interval must be at least 1")
+        self._kf_setup(named_parameters, exchange, bucket_bytes)
+        self._kf_op = "sum"
+        self._kf_average = True
+        self._kf_overlap = False
+        self._kf_interval = int(monitor_interval)
+        self._kf_step = 0
+        self._kf_plans = None
+
+    def _kf_result_device(self):
+        return self._kf_params[0].device
+
+    def sync_gradients(self):
+        if self._kf_groups is None:
+            self._kf_build(None)
+        monitored = self._kf_step % self._kf_interval == 0
+        self._kf_step += 1
+        for ps, gb in self._kf_groups:
+            self._kf_place(ps, gb)
+        if monitored:
+            self._kf_before_exchange()
+        for ps, gb in self._kf_groups:
+            self._kf_ex.all_reduce_(gb.buckets, op="sum", average=True)
+        if monitored:
+            self._kf_after_exchange()
+
+    def _kf_total(self, outs, into):
+        """The groups' totals (each run's last value) added into `into`."""
+        dev = into.device
+        tot = outs[0][-1].to(dev)
+        for o in outs[1:]:  # several dtype groups: one tiny add each
+            tot = tot + o[-1].to(dev)
+        into.copy_(tot)
+
+
+class _NoiseScale(_Monitored):
+    def _kf_before_exchange(self):
+        from . import ops
+        import torch
+        if self._kf_plans is None:
+            # one segment per bucket: its real span, not the padding
+            self._kf_plans = [ops.SegNorm([b[:sp] for b, sp in zip(gb.buckets, gb.spans)])
+                              for _, gb in self._kf_groups]
+            self._kf_outs = [(torch.zeros(pl.nseg + 1, dtype=torch.float64, device=pl.device),
+                              torch.zeros(pl.nseg + 1, dtype=torch.float64, device=pl.device))
+                             for pl in self._kf_plans]
+        for pl, (small, _) in zip(self._kf_plans, self._kf_outs):
+            pl.run("sq", out=small)
+        self._kf_total([o[0] for o in self._kf_outs], self._kf_sq[0])
+
+    def _kf_after_exchange(self):
+        from . import ops
+        for pl, (_, big) in zip(self._kf_plans, self._kf_outs):
+            pl.run("sq", out=big)
+        self._kf_total([o[1] for o in self._kf_outs], self._kf_sq[1])
+        bs = self._kf_device_batch
+        ops.noise_scale_update_(self._kf_sq[0], self._kf_sq[1], bs, bs * self._kf_ex.world,
+                                self._kf_alpha, self._kf_ns_state)
+
+    @property
+    def noise_scale(self):
+        """0-dim fp32 device tensor: the running s_ema / g_ema (`.item()` it
+        when wanted; nothing here synchronises the host)."""
+        return self._kf_ns_state[2]
+
+    @property
+    def noise_scale_state(self):
+        """{g_ema, s_ema, noise_scale, has_value} as 4 fp32 device values."""
+        return self._kf_ns_state
+
+    @property
+    def last_sq_small(self):
+        """|local gradient|^2 of the last monitored step (0-dim fp64, device)."""
+        return self._kf_sq[0]
+
+    @property
+    def last_sq_big(self):
+        """|averaged gradient|^2 of the last monitored step."""
+        return self._kf_sq[1]
+
+
+def MonitorGradientNoiseScaleOptimizer(optimizer, device_batch_size, monitor_interval=1,
+                                       named_parameters=None, alpha=0.9, exchange=None,
+                                       bucket_bytes=32 << 20, overlap=False):
+    """S-SGD that also estimates the gradient noise scale (grad_noise_scale.py):
+    on a monitored step |g|^2 of the local gradients (before the exchange) and
+    of the averaged ones (after it) are taken over the buckets' real spans,
+    and kf_noise_scale_update runs monitor.py:10-17 and the NoiseScale op's
+    two EMAs on the device with batch_small = device_batch_size and
+    batch_big = device_batch_size * world. With one peer the formula divides
+    by zero and gives inf or NaN, as the reference.
+
+    Results stay on the device: `noise_scale` (0-dim fp32), `last_sq_small`
+    and `last_sq_big` (0-dim fp64)."""
+    if not device_batch_size > 0:
+        raise ValueError("device_batch_size must be greater than zero")
+    if not alpha > 0:
+        raise ValueError("alpha must be greater than zero")
+    import torch
+    opt = _wrap(optimizer, _NoiseScale)
+    opt._kf_setup_monitor(named_parameters, exchange, bucket_bytes, monitor_interval, overlap)
+    opt._kf_device_batch = float(device_batch_size)
+    opt._kf_alpha = float(alpha)
+    dev = opt._kf_result_device()
+    opt._kf_ns_state = torch.zeros(4, dtype=torch.float32, device=dev)
+    opt._kf_sq = torch.zeros(2, dtype=torch.float64, device=dev)
+    return opt
+
+
+class _GradVariance(_Monitored):
+    def _kf_build_variance(self):
+        from . import ops
+        from .collective import workspace_like
+        import torch
+        self._kf_work, self._kf_plans, self._kf_outs, self._kf_index = [], [], [], []
+        pos = {id(p): i for i, p in enumerate(self._kf_params)}
+        for ps, gb in self._kf_groups:
+            if gb.buckets[0].dtype == torch.float16:
+                raise TypeError("MonitorGradientVarianceOptimizer: fp16 gradients have no "
+                                "element-wise product on the device (the reduce defines "
+                                "fp16 SUM only)")
+            ws = workspace_like(gb.buckets)
+            pairs = []
+            for v in gb.views:  # the workspace view under each gradient view
+                j = next(j for j, b in enumerate(gb.buckets)
+                         if b.data_ptr() <= v.data_ptr() < b.data_ptr() + max(1, b.numel()) * b.element_size())
+                off = (v.data_ptr() - gb.buckets[j].data_ptr()) // v.element_size()
+                pairs.append((ws[j][off:off + v.numel()], v))
+            pl = ops.SegNorm(pairs)
+            self._kf_work.append(ws)
+            self._kf_plans.append(pl)
+            self._kf_outs.append(torch.zeros(pl.nseg + 1, dtype=torch.float64, device=pl.device))
+            self._kf_index.append(torch.tensor([pos[id(p)] for p in ps], dtype=torch.int64,
+                                               device=self._kf_var.device))
+
+    def _kf_before_exchange(self):
+        from . import ops
+        if self._kf_plans is None:
+            self._kf_build_variance()
+        for (_, gb), ws in zip(self._kf_groups, self._kf_work):
+            for b, w in zip(gb.buckets, ws):  # w = g * g, the reduce's own PROD
+                ops.bucket_reduce([b, b], out=w, op="prod")
+
+    def _kf_after_exchange(self):
+        for ws in self._kf_work:  # mean over the peers of g * g
+            self._kf_ex.all_reduce_(ws, op="sum", average=True)
+        dev = self._kf_var.device
+        for pl, out, idx in zip(self._kf_plans, self._kf_outs, self._kf_index):
+            pl.run("var", out=out, total_sqrt=True)
+            self._kf_var.index_copy_(0, idx, out[:-1].to(dev))
+        self._kf_total(self._kf_outs, self._kf_var_total)
+
+    @property
+    def variance(self):
+        """0-dim fp64 device tensor: sum over the parameters of
+        ||mean(g^2) - mean(g)^2|| (grad_variance.py:55-58)."""
+        return self._kf_var_total
+
+    @property
+    def last_variances(self):
+        """Per parameter (registration order) sum d^2, d = mean(g^2) -
+        mean(g)^2 element-wise in the gradient's dtype; fp64, device."""
+        return self._kf_var
+
+
+def MonitorGradientVarianceOptimizer(optimizer, monitor_interval=1, named_parameters=None,
+                                     exchange=None, bucket_bytes=32 << 20, overlap=False):
+    """S-SGD that also monitors the gradient variance (grad_variance.py): on a
+    monitored step each bucket's g * g goes into a workspace (the reduce
+    kernel's PROD) before the exchange, gradients and workspaces are both
+    averaged over the peers, and one segmented pass takes, per parameter,
+    sum d^2 with d = mean(g^2) - mean(g)^2 rounded as the tensors' dtype
+    (KF_NORM_VAR), and the sum of their square roots.
+
+    Results stay on the device: `variance` (0-dim fp64) and `last_variances`
+    (fp64, one per parameter). fp64 accumulation in a fixed order; the
+    reference's tf.norm sums in fp32 in an order TF does not define."""
+    import torch
+    opt = _wrap(optimizer, _GradVariance)
+    opt._kf_setup_monitor(named_parameters, exchange, bucket_bytes, monitor_interval, overlap)
+    dev = opt._kf_result_device()
+    opt._kf_var = torch.zeros(len(opt._kf_params), dtype=torch.float64, device=dev)
+    opt._kf_var_total = torch.zeros((), dtype=torch.float64, device=dev)
     return opt
 
 

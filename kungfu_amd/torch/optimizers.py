@@ -12,11 +12,17 @@ pass through to it.
 
 ``SynchronousAveragingOptimizer`` is the SMA wrapper (sma_sgd.py:9-74); the
 reference has no torch version, so it is the package's own.
+
+``MonitorGradientNoiseScaleOptimizer`` and ``MonitorGradientVarianceOptimizer``
+(grad_noise_scale.py, grad_variance.py; TF only in the reference) take
+``named_parameters`` positionally like the S-SGD wrapper; they average
+(sum, / np) as their TF originals do.
 """
 from .. import optimizers as _opt
 from ..optimizers import SynchronousAveragingOptimizer
 
-__all__ = ["SynchronousSGDOptimizer", "SynchronousAveragingOptimizer"]
+__all__ = ["SynchronousSGDOptimizer", "SynchronousAveragingOptimizer",
+           "MonitorGradientNoiseScaleOptimizer", "MonitorGradientVarianceOptimizer"]
 
 
 def SynchronousSGDOptimizer(optimizer, named_parameters, op=None, **kwargs):
@@ -25,3 +31,20 @@ def SynchronousSGDOptimizer(optimizer, named_parameters, op=None, **kwargs):
     kwargs.setdefault("average", False)
     return _opt.SynchronousSGDOptimizer(optimizer, named_parameters=named_parameters, op=op,
                                         **kwargs)
+
+
+def MonitorGradientNoiseScaleOptimizer(optimizer, named_parameters, device_batch_size,
+                                       monitor_interval=1, alpha=0.9, **kwargs):
+    """kungfu_amd.optimizers.MonitorGradientNoiseScaleOptimizer with
+    `named_parameters` positional."""
+    return _opt.MonitorGradientNoiseScaleOptimizer(
+        optimizer, device_batch_size, monitor_interval=monitor_interval,
+        named_parameters=named_parameters, alpha=alpha, **kwargs)
+
+
+def MonitorGradientVarianceOptimizer(optimizer, named_parameters, monitor_interval=1, **kwargs):
+    """kungfu_amd.optimizers.MonitorGradientVarianceOptimizer with
+    `named_parameters` positional."""
+    return _opt.MonitorGradientVarianceOptimizer(
+        optimizer, monitor_interval=monitor_interval, named_parameters=named_parameters,
+        **kwargs)
