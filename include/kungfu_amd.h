@@ -491,6 +491,88 @@ int kf_peer_barrier(void *const *sigs, int world, int rank, uint64_t epoch,
                     uint32_t timeout_us, void *status, void *stream);
 const char *kf_p2p_last_error(void);
 
+/* ---- pair averaging: a device-side model store (kungfu_amd/pairavg.py) ----
+ *
+ * What PairAveragingOptimizer (AD-PSGD, async_sgd.py) needs: every rank
+ * publishes whole snapshots of its variables into slots in its own HBM; a
+ * peer pulls the latest one over the pair's xGMI link and blends it into its
+ * own variables. A puller gets one whole published version or nothing, never
+ * a mix of two, and no kernel ever waits, spins or loops on a value another
+ * rank writes.
+ *
+ * A plan holds, on the current device: `slots` snapshot slots (2 to 64) in
+ * ONE allocation, each holding every span at a 16-byte aligned offset; a
+ * control block of uncached fine-grained words (as kf_signal_alloc(.., 0)):
+ * latest (versions published, 0 = none) and one seqlock per slot, odd while
+ * the slot is being written; privately a staging buffer of one slot, the
+ * pick record and four counters. Slots and control block are exported with
+ * kf_ipc_export by the caller (kf_pairavg_local gives their addresses) and
+ * every peer's mapping of them is handed back with kf_pairavg_set_peers;
+ * with world == 1 the only target is the rank itself and no call is needed.
+ *
+ * kf_pairavg_create does all allocation. spans[i] are device pointers, 16-byte
+ * aligned, of span_bytes[i] bytes (whole elements of `dt`: f32, f16, bf16 or
+ * f64, else KF_ERR_DTYPE; a length may be 0; any number of spans, launched
+ * KF_MAX_SEGMENTS at a time). Every rank of a group passes spans of the same
+ * lengths and the same `slots`. NULL on failure, kf_pairavg_last_error()
+ * starting with the status name ("KF_ERR_ARG: ...").
+ *
+ * Every other call only queues launches on `stream`: no allocation, no host
+ * sync, safe to capture into a hipGraph (the version counter lives on the
+ * device).
+ *   kf_pairavg_publish        version n = published + 1 goes to slot n % slots:
+ *       begin  lock[s] += 1 (odd), release store at system scope
+ *       copy   variables -> slot s (16-B non-temporal; the bytes past a
+ *              span's last whole vector one per lane)
+ *       end    lock[s] += 1 (even), then latest = n, release stores at system
+ *              scope in that order; the `published` counter becomes n
+ *   kf_pairavg_pull_average   from rank `target`:
+ *       pick   v0 = latest, s = v0 % slots, l0 = lock[s], acquire loads at
+ *              system scope; v0 == 0: empty, l0 odd: torn
+ *       fetch  the target's slot s -> staging (nothing when empty or torn)
+ *       check  l1 = lock[s]; valid = (l1 == l0); exactly one of the valid /
+ *              torn / empty counters grows by one
+ *       blend  valid: every element v = fl_T(0.5 * fl_T(v + o)), o the staged
+ *              element (TF's 0.5 * (v + other_v), async_sgd.py:130-133, in the
+ *              tensor's dtype: every operation rounded to T, no contraction;
+ *              f16 / bf16 compute in fp32 and round to T after the add and
+ *              after the multiply). Not valid: the variables keep their bits.
+ * The launch boundaries order the markers and the data. A torn pull is
+ * skipped and counted, not retried: with S slots it needs the target to
+ * publish twice between pick and check. The phases are also exported singly,
+ * for tests and tools; the two composite calls are exactly these in order.
+ * kf_pairavg_counters copies {valid, torn, empty, published} into out[4]
+ * (host or device memory) with a stream-ordered asynchronous copy.
+ * Slot data is ordinary device memory read by a peer: like the P2P exchange
+ * it relies on the release at the writer's kernel end and the invalidate at
+ * the reader's kernel start, and has only run with ranks as processes on one
+ * GPU; across two physical GPUs it is unmeasured. */
+#pragma GCC visibility pop
+typedef struct kf_pairavg kf_pairavg_t; /* opaque plan */
+#pragma GCC visibility push(default)
+kf_pairavg_t *kf_pairavg_create(const void *const *spans, const size_t *span_bytes, int nspan,
+                                KungFu_Datatype dt, int slots, int world, int rank);
+/* This rank's slot allocation, control block and the bytes of one slot. */
+int kf_pairavg_local(kf_pairavg_t *p, void **slot_base, void **ctrl_base, size_t *slot_bytes);
+/* slot_bases[r] / ctrl_bases[r]: rank r's slot allocation (16-byte aligned)
+ * and control block (8-byte aligned) as mapped in this process, `world`
+ * entries (the plan's world); entry `rank` is ignored. */
+int kf_pairavg_set_peers(kf_pairavg_t *p, const void *const *slot_bases,
+                         const void *const *ctrl_bases, int world);
+void kf_pairavg_destroy(kf_pairavg_t *p);
+int kf_pairavg_publish(kf_pairavg_t *p, void *stream);
+int kf_pairavg_pull_average(kf_pairavg_t *p, int target, void *stream);
+/* the phases singly, for tests and tools */
+int kf_pairavg_publish_begin(kf_pairavg_t *p, void *stream);
+int kf_pairavg_publish_copy(kf_pairavg_t *p, void *stream);
+int kf_pairavg_publish_end(kf_pairavg_t *p, void *stream);
+int kf_pairavg_pick(kf_pairavg_t *p, int target, void *stream);
+int kf_pairavg_fetch(kf_pairavg_t *p, int target, void *stream);
+int kf_pairavg_check(kf_pairavg_t *p, int target, void *stream);
+int kf_pairavg_blend(kf_pairavg_t *p, void *stream);
+int kf_pairavg_counters(kf_pairavg_t *p, uint64_t *out /* 4 */, void *stream);
+const char *kf_pairavg_last_error(void);
+
 /* ---- multi-GPU exchange over RCCL (kungfu_amd/csrc/kf_exchange.hip) ------
  *
  * The reference's GPU collective, srcs/cpp/src/nccl/gpu_collective.cpp:

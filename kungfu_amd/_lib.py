@@ -102,6 +102,21 @@ EXPORTED = (
     "kf_segnorm_run",
     "kf_segnorm_destroy",
     "kf_noise_scale_update",
+    "kf_pairavg_create",
+    "kf_pairavg_local",
+    "kf_pairavg_set_peers",
+    "kf_pairavg_destroy",
+    "kf_pairavg_publish",
+    "kf_pairavg_pull_average",
+    "kf_pairavg_publish_begin",
+    "kf_pairavg_publish_copy",
+    "kf_pairavg_publish_end",
+    "kf_pairavg_pick",
+    "kf_pairavg_fetch",
+    "kf_pairavg_check",
+    "kf_pairavg_blend",
+    "kf_pairavg_counters",
+    "kf_pairavg_last_error",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -369,6 +384,24 @@ def load():
     lib.kf_noise_scale_update.argtypes = [c_void_p, c_void_p, ctypes.c_float, ctypes.c_float,
                                           ctypes.c_float, c_void_p, c_void_p]
     lib.kf_noise_scale_update.restype = c_int
+    lib.kf_pairavg_create.argtypes = [P(c_void_p), P(c_size_t), c_int, c_int, c_int, c_int, c_int]
+    lib.kf_pairavg_create.restype = c_void_p
+    lib.kf_pairavg_local.argtypes = [c_void_p, P(c_void_p), P(c_void_p), P(c_size_t)]
+    lib.kf_pairavg_local.restype = c_int
+    lib.kf_pairavg_set_peers.argtypes = [c_void_p, P(c_void_p), P(c_void_p), c_int]
+    lib.kf_pairavg_set_peers.restype = c_int
+    lib.kf_pairavg_destroy.argtypes = [c_void_p]
+    lib.kf_pairavg_destroy.restype = None
+    for name in ("publish", "publish_begin", "publish_copy", "publish_end", "blend"):
+        fn = getattr(lib, "kf_pairavg_" + name)
+        fn.argtypes, fn.restype = [c_void_p, c_void_p], c_int
+    for name in ("pull_average", "pick", "fetch", "check"):
+        fn = getattr(lib, "kf_pairavg_" + name)
+        fn.argtypes, fn.restype = [c_void_p, c_int, c_void_p], c_int
+    lib.kf_pairavg_counters.argtypes = [c_void_p, c_void_p, c_void_p]
+    lib.kf_pairavg_counters.restype = c_int
+    lib.kf_pairavg_last_error.argtypes = []
+    lib.kf_pairavg_last_error.restype = ctypes.c_char_p
     _lib = lib
     # HIP resources go back while the runtime is alive, before the C exit
     # handlers run (include/kungfu_amd.h kf_shutdown)
@@ -383,7 +416,7 @@ def check(rc, what, source=None):
     never stands in for it."""
     if rc != 0:
         lib = load()
-        order = ["exchange", "session", "", "ingest", "p2p"]
+        order = ["exchange", "session", "", "ingest", "p2p", "pairavg"]
         if source in order:
             order.remove(source)
             order.insert(0, source)

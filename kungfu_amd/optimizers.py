@@ -18,6 +18,10 @@ Operator surface kept from the reference:
   ``monitor_interval``-th step also reduces the gradient buckets to scalars
   on the device (ops.SegNorm: one read-only pass, fp64) — the gradient noise
   scale's running estimate, or the per-parameter gradient variance.
+* ``PairAveragingOptimizer(optimizer, named_parameters=None, ...)`` — AD-PSGD
+  (async_sgd.py): asynchronous; every step averages the variables with one
+  peer's latest published model, read out of that peer's HBM through a
+  device-side model store (``pairavg.PeerModelStore``), with no collective.
 
 Buckets: parameters are grouped (in registration order, per dtype/device) into
 flat padded device buckets (``collective.GradBuckets``); ``p.grad`` (S-SGD) or
@@ -490,4 +494,147 @@ def SynchronousAveragingOptimizer(optimizer, named_parameters=None, alpha=0.1,
     if opt._kf_overlap and not hasattr(opt._kf_ex, "start_"):
         raise ValueError("overlap=True needs an exchange with start_() "
                          "(collective.Exchange or exchange.NativeExchange)")
+    return opt
+
+
+class _PairAveraging:
+    """AD-PSGD (async_sgd.py): no exchange and no collective in a step. The
+    variables live in buckets like `_SMA`'s; one pairavg.PeerModelStore per
+    dtype group publishes them and pulls a peer's. Everything that touches
+    the device is built on the first step."""
+
+    def _kf_setup_pair(self, named_parameters, bucket_bytes, slots, seed, peer_selector):
+        import torch
+        if int(slots) < 2:
+            raise ValueError("slots must be at least 2")
+        if named_parameters is None:
+            params = [p for g in self.param_groups for p in g["params"]]
+        else:
+            params = [p for _, p in named_parameters]
+        for p in params:  # an integer parameter cannot require a gradient: check all
+            if p.dtype not in (torch.float32, torch.float16, torch.bfloat16, torch.float64):
+                raise ValueError("PairAveragingOptimizer averages f32, f16, bf16 and f64 "
+                                 "parameters, not %s" % p.dtype)
+        self._kf_params = [p for p in params if p.requires_grad]
+        if len({p.device for p in self._kf_params}) > 1:
+            raise ValueError("PairAveragingOptimizer: parameters on more than one device")
+        self._kf_bucket_bytes = bucket_bytes
+        self._kf_slots = int(slots)
+        self._kf_seed = seed
+        self._kf_selector = peer_selector
+        self._kf_rng = None
+        self._kf_groups = None
+        self._kf_stores = None
+        self._kf_step = 0
+        self._kf_last_target = None
+
+    @staticmethod
+    def _kf_world_rank():
+        import torch.distributed as dist
+        if dist.is_initialized():
+            return dist.get_world_size(), dist.get_rank()
+        return 1, 0
+
+    def _kf_select(self):
+        world, rank = self._kf_world_rank()
+        if self._kf_selector is not None:
+            target = int(self._kf_selector(self._kf_step, rank, world))
+        else:
+            if self._kf_rng is None:
+                import random
+                # the generator stays on the host; without a seed every rank
+                # draws its own sequence
+                self._kf_rng = random.Random(self._kf_seed if self._kf_seed is not None
+                                             else 0x9E3779B1 * (rank + 1))
+            from .pairavg import random_peer
+            target = random_peer(self._kf_rng, world, rank)
+        if not 0 <= target < world:
+            raise ValueError("peer_selector returned %d, outside [0, %d)" % (target, world))
+        return target
+
+    def _kf_build_pair(self):
+        import torch
+        import torch.distributed as dist
+        from .pairavg import PeerModelStore
+        groups = {}
+        for p in self._kf_params:
+            groups.setdefault((p.dtype, p.device), []).append(p)
+        self._kf_groups, self._kf_stores = [], []
+        for (dtype, device), ps in groups.items():
+            # the buckets are never exchanged in shards: no padding for a world
+            gb = GradBuckets([p.numel() for p in ps], dtype, device, 1,
+                             bucket_bytes=self._kf_bucket_bytes)
+            for p, view in zip(ps, gb.views):  # move the variables into buckets
+                v = view.view_as(p)
+                v.copy_(p.data)
+                p.data = v
+            self._kf_groups.append((ps, gb))
+            self._kf_stores.append(PeerModelStore(
+                [b[:sp] for b, sp in zip(gb.buckets, gb.spans)], slots=self._kf_slots))
+        # init_store + barrier (async_sgd.py:113-121): after it no peer finds
+        # version 0
+        for st in self._kf_stores:
+            st.publish()
+        torch.cuda.current_stream().synchronize()
+        if dist.is_initialized() and dist.get_world_size() > 1:
+            dist.barrier()
+
+    def step(self, closure=None):
+        target = self._kf_select()
+        if self._kf_stores is None:
+            self._kf_build_pair()
+        for (ps, gb), st in zip(self._kf_groups, self._kf_stores):
+            # only variables that have a gradient take part (async_sgd.py:
+            # 110-112 pairs grads_and_vars); others are restored after the blend
+            saved = [(p, p.data.clone()) for p in ps if p.grad is None]
+            st.pull_average_(target)
+            for p, d in saved:
+                p.data.copy_(d)
+        self._kf_last_target = target
+        out = super().step(closure)
+        for st in self._kf_stores:
+            st.publish()
+        self._kf_step += 1
+        return out
+
+    @property
+    def pair_counters(self):
+        """{valid, torn, empty, published} of the pulls and publishes so far,
+        summed over the dtype groups (one store each). Waits for the device."""
+        tot = dict.fromkeys(("valid", "torn", "empty", "published"), 0)
+        for st in self._kf_stores or []:
+            for k, v in st.counters().items():
+                tot[k] += v
+        return tot
+
+    @property
+    def last_target(self):
+        """The peer the last step pulled from (None before the first)."""
+        return self._kf_last_target
+
+    def close(self):
+        """Collective: release the stores (PeerModelStore.close)."""
+        for st in self._kf_stores or []:
+            st.close()
+        self._kf_stores = None
+
+
+def PairAveragingOptimizer(optimizer, named_parameters=None, bucket_bytes=32 << 20, slots=2,
+                           seed=None, peer_selector=None):
+    """AD-PSGD (async_sgd.py:110-142). Each step: pull a peer's latest
+    published model out of its HBM and average it into the variables
+    (v = 0.5 * (v + other), pairavg.PeerModelStore), run the wrapped
+    optimizer's step on the gradients already computed, publish the result.
+    The first step first publishes the initial model and joins a barrier, so
+    that no peer finds an empty store afterwards. No rank ever waits for
+    another after that: a pull that would mix two versions is skipped and
+    counted (`pair_counters`).
+
+    The peer is the reference's random choice (pairavg.random_peer, host-side
+    random.Random(seed), or a per-rank sequence without a seed) unless
+    `peer_selector(step, rank, world) -> int` gives it; `last_target` is the
+    last one. Parameters live on one device and are f32, f16, bf16 or f64.
+    RCCL plays no part."""
+    opt = _wrap(optimizer, _PairAveraging)
+    opt._kf_setup_pair(named_parameters, bucket_bytes, slots, seed, peer_selector)
     return opt

@@ -75,6 +75,38 @@ def _device_identity(dev):
     return (socket.gethostname(), pci)
 
 
+def share_ipc(lib, group, world, rank, ptrs, bases):
+    """Export this rank's allocations, import every peer's: rows[j][r] =
+    address of rank r's buffer j as seen from this process. Collective over
+    `group`. `bases` ((rank, handle) -> mapped base) keeps one mapping per
+    peer allocation; its owner closes them with kf_ipc_close. Shared by
+    P2PExchange and pairavg.PeerModelStore."""
+    mine = []
+    for p in ptrs:
+        h = (ctypes.c_char * 64)()
+        off = ctypes.c_size_t()
+        _lib.check(lib.kf_ipc_export(p, h, ctypes.byref(off)), "kf_ipc_export")
+        mine.append((bytes(h), off.value))
+    everyone = [None] * world
+    dist.all_gather_object(everyone, mine, group=group)
+    rows = []
+    for j, p in enumerate(ptrs):
+        row = []
+        for r in range(world):
+            if r == rank:
+                row.append(p)
+                continue
+            h, off = everyone[r][j]
+            key = (r, h)
+            if key not in bases:
+                base = ctypes.c_void_p()
+                _lib.check(lib.kf_ipc_import(h, ctypes.byref(base)), "kf_ipc_import")
+                bases[key] = base.value
+            row.append(bases[key] + off)
+        rows.append(row)
+    return rows
+
+
 class P2PExchange:
     def __init__(self, buckets, group=None, mode="pull", barrier="device", timeout_s=60.0,
                  coalesce=True):
@@ -131,30 +163,7 @@ class P2PExchange:
     def _share(self, ptrs):
         """Export my allocations, import every peer's: rows[j][r] = address of
         rank r's buffer j as seen from this process."""
-        mine = []
-        for p in ptrs:
-            h = (ctypes.c_char * 64)()
-            off = ctypes.c_size_t()
-            _lib.check(self.lib.kf_ipc_export(p, h, ctypes.byref(off)), "kf_ipc_export")
-            mine.append((bytes(h), off.value))
-        everyone = [None] * self.world
-        dist.all_gather_object(everyone, mine, group=self.group)
-        rows = []
-        for j, p in enumerate(ptrs):
-            row = []
-            for r in range(self.world):
-                if r == self.rank:
-                    row.append(p)
-                    continue
-                h, off = everyone[r][j]
-                key = (r, h)
-                if key not in self._bases:
-                    base = ctypes.c_void_p()
-                    _lib.check(self.lib.kf_ipc_import(h, ctypes.byref(base)), "kf_ipc_import")
-                    self._bases[key] = base.value
-                row.append(self._bases[key] + off)
-            rows.append(row)
-        return rows
+        return share_ipc(self.lib, self.group, self.world, self.rank, ptrs, self._bases)
 
     def close(self):
         torch.cuda.synchronize()

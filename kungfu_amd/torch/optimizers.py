@@ -17,12 +17,16 @@ reference has no torch version, so it is the package's own.
 (grad_noise_scale.py, grad_variance.py; TF only in the reference) take
 ``named_parameters`` positionally like the S-SGD wrapper; they average
 (sum, / np) as their TF originals do.
+
+``PairAveragingOptimizer`` (async_sgd.py; TF only in the reference) likewise
+takes ``named_parameters`` positionally.
 """
 from .. import optimizers as _opt
 from ..optimizers import SynchronousAveragingOptimizer
 
 __all__ = ["SynchronousSGDOptimizer", "SynchronousAveragingOptimizer",
-           "MonitorGradientNoiseScaleOptimizer", "MonitorGradientVarianceOptimizer"]
+           "MonitorGradientNoiseScaleOptimizer", "MonitorGradientVarianceOptimizer",
+           "PairAveragingOptimizer"]
 
 
 def SynchronousSGDOptimizer(optimizer, named_parameters, op=None, **kwargs):
@@ -48,3 +52,9 @@ def MonitorGradientVarianceOptimizer(optimizer, named_parameters, monitor_interv
     return _opt.MonitorGradientVarianceOptimizer(
         optimizer, monitor_interval=monitor_interval, named_parameters=named_parameters,
         **kwargs)
+
+
+def PairAveragingOptimizer(optimizer, named_parameters, **kwargs):
+    """kungfu_amd.optimizers.PairAveragingOptimizer with `named_parameters`
+    positional."""
+    return _opt.PairAveragingOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
