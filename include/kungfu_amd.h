@@ -158,6 +158,30 @@ int kf_sma_blend(void *v, const void *sum, size_t n, KungFu_Datatype dt,
 int kf_sma_blend_batch(void *const *vs, const void *const *sums, const size_t *counts, int nb,
                        KungFu_Datatype dt, int np, double alpha, void *stream);
 
+/* SGD update of nb segments of one float dtype in one launch per 32 of them
+ * (kungfu_amd/csrc/kf_sgd.hip): torch.optim.SGD's single-tensor arithmetic on
+ * a summed gradient, one IEEE operation per step, no contraction:
+ *   g = np > 0 ? grads[b][i] / np : grads[b][i]     (kf_bucket_div's rounding)
+ *   if weight_decay != 0:  g = g + weight_decay * p
+ *   if momentum != 0:      m = first ? g : (momentum * m) + (c * g)
+ *                          g = nesterov ? g + momentum * m : m
+ *   p = p + nlr * g
+ * with c = 1 - dampening and nlr = -lr computed in double, and every scalar
+ * cast once to the compute type. f32 / f64 round every product and every sum
+ * in that type. f16 / bf16 compute in fp32 and round to the storage type
+ * after the /np, the weight-decay add, momentum * m, the momentum add, the
+ * nesterov add and the final add (where torch's tensor ops do); the
+ * alpha * x product and the add inside each are two fp32 roundings.
+ * Segment b is counts[b] elements at params[b], grads[b] (read only) and
+ * moms[b] with its own hyper[b] (a host array of nb, read before the call
+ * returns). moms, or moms[b], may be NULL where momentum == 0: no momentum
+ * stream; on a `first` step m is written and not read. Every pointer is
+ * 16-byte aligned. g, p and m are read once, p and m written once. */
+typedef struct { double lr, momentum, dampening, weight_decay; int nesterov; int first; } kf_sgd_hyper;
+int kf_sgd_update_batch(void *const *params, const void *const *grads, void *const *moms,
+                        const size_t *counts, int nb, KungFu_Datatype dt, int np,
+                        const kf_sgd_hyper *hyper, void *stream);
+
 /* ---- gradient monitors: segmented squared norms ------------------------- */
 
 /* What MonitorGradientNoiseScaleOptimizer and MonitorGradientVarianceOptimizer
@@ -662,6 +686,24 @@ int kf_exchange_all_reduce_batch(kf_exchange_t *ex, const void *const *sends, vo
 int kf_exchange_sma_batch(kf_exchange_t *ex, void *const *vs, void *const *sums,
                           const size_t *counts, int nb, KungFu_Datatype dt, double alpha,
                           int algo, void *stream);
+/* The synchronous step with the optimizer update on the shard (sharded
+ * optimizer state): reduce-scatter of the gradient buckets, kf_sgd_update_batch
+ * on this rank's shard of every bucket (params[b] + rank * q, grads[b] +
+ * rank * q, mom_shards[b], q = counts[b] / world elements), in-place all-gather
+ * of the PARAMETER buckets. Reduce-scatter: the shard holds the sum and the
+ * update divides by world. All-to-all (f16 / bf16 under KF_ALGO_AUTO): the
+ * rank-order fold applies the / world and the update divides by nothing.
+ * KF_ALGO_REDUCE_SCATTER_AVG: the / world inside the collective. World 1 on
+ * the built-in transport is the update over the whole buckets.
+ * counts[b] is a multiple of world and every shard starts 16-byte aligned
+ * (no tails); mom_shards[b] holds q elements, and may be NULL where
+ * hyper[b].momentum == 0. After the call the gradient buckets hold nothing
+ * defined: they are scratch of the call. Follows kf_exchange_set_timing (the
+ * update counts under phase 2, the parameters' all-gather under phase 3) and
+ * always runs un-pipelined. */
+int kf_exchange_sgd_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
+                          void *const *mom_shards, const size_t *counts, int nb,
+                          KungFu_Datatype dt, const kf_sgd_hyper *hyper, int algo, void *stream);
 /* Pipelined schedule for the batch calls (default 1 = off): the buckets of a
  * call are split into `groups` groups of consecutive buckets of about equal
  * bytes; the RCCL phases stay on the caller's stream in the same order on
@@ -671,8 +713,8 @@ int kf_exchange_sma_batch(kf_exchange_t *ex, void *const *vs, void *const *sums,
  * meanwhile, ordered by events. Same results bit for bit. */
 int kf_exchange_set_pipeline(kf_exchange_t *ex, int groups);
 /* Opt-in per-phase timing of the batch calls (kf_exchange_all_reduce,
- * kf_exchange_all_reduce_batch, kf_exchange_sma_batch) on the un-pipelined
- * schedule: timing events on the caller's stream before phase 1 (every
+ * kf_exchange_all_reduce_batch, kf_exchange_sma_batch, kf_exchange_sgd_batch)
+ * on the un-pipelined schedule: timing events on the caller's stream before phase 1 (every
  * bucket's reduce-scatter or all-to-all, and the tail gathers), phase 2 (the
  * /np epilogue or rank-order fold), phase 3 (the all-gathers), the SMA blend,
  * and after it. on != 0 starts a window with zeroed sums, 0 ends it. Costs

@@ -117,6 +117,8 @@ EXPORTED = (
     "kf_pairavg_blend",
     "kf_pairavg_counters",
     "kf_pairavg_last_error",
+    "kf_sgd_update_batch",
+    "kf_exchange_sgd_batch",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -138,6 +140,25 @@ STATUS = {
 }
 
 MAX_INPUTS = 16
+
+
+class SgdHyper(ctypes.Structure):
+    """kf_sgd_hyper (include/kungfu_amd.h): one segment's SGD scalars."""
+    _fields_ = [("lr", ctypes.c_double), ("momentum", ctypes.c_double),
+                ("dampening", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("nesterov", ctypes.c_int), ("first", ctypes.c_int)]
+
+
+def sgd_hyper_array(hypers):
+    """A kf_sgd_hyper[] from dicts with the keys of torch.optim.SGD's param
+    groups (lr, momentum, dampening, weight_decay, nesterov) and `first`."""
+    arr = (SgdHyper * max(1, len(hypers)))()
+    for a, h in zip(arr, hypers):
+        a.lr, a.momentum = float(h["lr"]), float(h.get("momentum", 0.0))
+        a.dampening, a.weight_decay = float(h.get("dampening", 0.0)), float(h.get("weight_decay", 0.0))
+        a.nesterov, a.first = int(bool(h.get("nesterov", False))), int(bool(h.get("first", False)))
+    return arr
+
 
 # kf_done_fn: void (*)(int status, void *arg)
 DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p)
@@ -402,6 +423,12 @@ def load():
     lib.kf_pairavg_counters.restype = c_int
     lib.kf_pairavg_last_error.argtypes = []
     lib.kf_pairavg_last_error.restype = ctypes.c_char_p
+    lib.kf_sgd_update_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_size_t), c_int,
+                                        c_int, c_int, P(SgdHyper), c_void_p]
+    lib.kf_sgd_update_batch.restype = c_int
+    lib.kf_exchange_sgd_batch.argtypes = [c_void_p, P(c_void_p), P(c_void_p), P(c_void_p),
+                                          P(c_size_t), c_int, c_int, P(SgdHyper), c_int, c_void_p]
+    lib.kf_exchange_sgd_batch.restype = c_int
     _lib = lib
     # HIP resources go back while the runtime is alive, before the C exit
     # handlers run (include/kungfu_amd.h kf_shutdown)

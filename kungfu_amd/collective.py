@@ -61,6 +61,10 @@ class HipEpilogue:
     def sma_blend_(self, v, summed, np_, alpha):
         return ops.sma_blend_(v, summed, np_, alpha)
 
+    def sgd_update_(self, params, grads, moms, hypers, np_):
+        """The SGD update of the shards (ops.sgd_update_batch_), one launch."""
+        return ops.sgd_update_batch_(params, grads, moms, hypers, np_)
+
 
 def coalesce_runs(buckets):
     """Maximal runs of buckets that are consecutive in one storage, each as
@@ -319,6 +323,66 @@ class Exchange:
             self.epilogue.sma_blend_(b, s, self.world, alpha)
             self._mark(marks, "blend")
         return buckets
+
+
+    def sgd_step_(self, param_buckets, grad_buckets, mom_shards, hypers):
+        """The synchronous step with the SGD update on this rank's shards (the
+        native exchange's kf_exchange_sgd_batch, for this path): every
+        gradient bucket is reduce-scattered (or all-to-all'ed and folded in
+        rank order with the / world), epilogue.sgd_update_ runs once over the
+        shards — parameters, summed gradients, momentum shards — and every
+        parameter bucket is all-gathered in place. After a reduce-scatter
+        the update divides by the world itself. mom_shards[b] holds
+        numel // world elements (None where hypers[b]'s momentum is 0). The
+        gradient buckets are only read here; callers must not rely on that
+        (the native exchange uses them as scratch)."""
+        params, grads = list(param_buckets), list(grad_buckets)
+        moms = [None] * len(params) if mom_shards is None else list(mom_shards)
+        hypers = list(hypers)
+        if not (len(params) == len(grads) == len(moms) == len(hypers)):
+            raise ValueError("sgd_step_: one grad bucket, momentum shard and hyper per bucket")
+        for p, g, m in zip(params, grads, moms):
+            self._check(p)
+            self._check(g)
+            if g.numel() != p.numel() or g.dtype != p.dtype or \
+                    (m is not None and m.numel() * self.world != p.numel()):
+                raise ValueError("sgd_step_: bucket / shard sizes do not match")
+        if not params:
+            return params
+        if self.world == 1:
+            self.epilogue.sgd_update_(params, grads, moms, hypers, 1)
+            return params
+        marks = self._marks()
+        works = []
+        for i, g in enumerate(grads):
+            shard = self._workspace(("sgd", "rs", i), g.numel() // self.world, g)
+            works.append((shard, self._scatter(g, shard, OP.SUM, ("sgd", "a2a", i))))
+        # one update launch over all shards: the / world is the fold's where
+        # the shards were folded here, the update's own after a reduce-scatter
+        sets = {0: ([], [], [], []), self.world: ([], [], [], [])}
+        for _, (w, _) in works:
+            w.wait()
+        self._mark(marks, "reduce_scatter")
+        for p, m, h, (shard, (w, recv)) in zip(params, moms, hypers, works):
+            if recv is not None:
+                self.epilogue.fold_(list(recv.chunk(self.world)), shard, OP.SUM, self.world)
+            q = shard.numel()
+            dst = sets[0 if recv is not None else self.world]
+            for lst, x in zip(dst, (p[self.rank * q:(self.rank + 1) * q], shard, m, h)):
+                lst.append(x)
+        for np_, (ps, gs, ms, hs) in sets.items():
+            if ps:
+                self.epilogue.sgd_update_(ps, gs, ms, hs, np_)
+        self._mark(marks, "epilogue")
+        gathers = []
+        for p in params:
+            q = p.numel() // self.world
+            gathers.append(dist.all_gather_into_tensor(p, p[self.rank * q:(self.rank + 1) * q],
+                                                       group=self.group, async_op=True))
+        for w in gathers:
+            w.wait()
+        self._mark(marks, "all_gather")
+        return params
 
 
 class _Handle:

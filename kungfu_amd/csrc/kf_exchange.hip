@@ -345,6 +345,13 @@ struct NamedTask {
     void *arg        = nullptr;
 };
 
+// kf_exchange_sgd_batch's tables (one entry per bucket)
+struct SgdStep {
+    void *const *params;
+    void *const *moms;  // this rank's momentum shards
+    const kf_sgd_hyper *hyper;
+};
+
 struct kf_exchange {
     const kf_transport_ops *T = nullptr;  // librccl, or a host's transport
     void *comm                = nullptr;
@@ -428,9 +435,12 @@ struct kf_exchange {
     // each variable blended once its sum is gathered
     // phases: which of the three to run (kAll; the hierarchical all-reduce
     // runs 1+2, its cross-host step, then 3)
+    // sgd != nullptr: the sharded SGD step (kf_exchange_sgd_batch), sends ==
+    // recvs = the gradient buckets, average set; the update runs on the
+    // shards in phase 2 and phase 3 gathers the parameter buckets
     int batch(const void *const *sends, void *const *recvs, const size_t *counts, int nb,
               KungFu_Datatype dt, KungFu_Op op, int average, int algo, hipStream_t s,
-              const double *sma_alpha = nullptr, int phases = 7);
+              const double *sma_alpha = nullptr, int phases = 7, const SgdStep *sgd = nullptr);
     int hier(kf_session_t *cross, const void *send, void *recv, size_t count, KungFu_Datatype dt,
              KungFu_Op op, int average, int algo, const std::string &name, hipStream_t s);
     kf_exchange *split(int color, int key, int *status);  // caller holds mu
@@ -523,11 +533,17 @@ static int resolve_algo(int algo, KungFu_Datatype dt, KungFu_Op op, int world, i
 
 int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_t *counts,
                        int nb, KungFu_Datatype dt, KungFu_Op op, int average, int algo,
-                       hipStream_t s, const double *sma_alpha, int phases)
+                       hipStream_t s, const double *sma_alpha, int phases, const SgdStep *sgd)
 {
     const int sz = tsize(dt);
     const int W = world, r = rank;
     const bool sma = sma_alpha != nullptr;
+    if (W == 1 && builtin && sgd) {  // a single peer: the update over the whole buckets
+        const int rc = kf_sgd_update_batch(sgd->params, sends, sgd->moms, counts, nb, dt, 1,
+                                           sgd->hyper, s);
+        if (rc != KF_OK) return fail(rc, std::string("kf_sgd_update_batch: ") + kf_last_error());
+        return KF_OK;
+    }
     if (W == 1 && builtin) {  // a single peer: the sum is the bucket, x / 1 == x
         for (int b = 0; b < nb && (phases & 1); ++b) {
             if (counts[b] && sends[b] != recvs[b]) {
@@ -606,7 +622,7 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
         std::vector<const void *> ins;
         std::vector<void *> outs;
         std::vector<size_t> cnts;
-        if (a == KF_ALGO_REDUCE_SCATTER && average) {
+        if (a == KF_ALGO_REDUCE_SCATTER && average && !sgd) {
             for (int b = b0; b < b1; ++b) {
                 const size_t q = counts[b] / W;
                 if (!q) continue;
@@ -645,6 +661,26 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
                                                  average ? W : 0, cs);
             if (e != KF_OK) return fail(e, "rank-order fold of the received shards");
         }
+        if (sgd) {
+            // the update on this rank's shard of every bucket; after a plain
+            // reduce-scatter the shard holds the sum and the kernel divides
+            // (the shard is read once, no /np pass); the fold and ncclAvg
+            // have divided already
+            std::vector<void *> ps, ms;
+            std::vector<const void *> gs;
+            cnts.clear();
+            for (int b = b0; b < b1; ++b) {
+                const size_t q = counts[b] / W;
+                ps.push_back(static_cast<char *>(sgd->params[b]) + r * q * sz);
+                gs.push_back(static_cast<const char *>(recvs[b]) + r * q * sz);
+                ms.push_back(sgd->moms ? sgd->moms[b] : nullptr);
+                cnts.push_back(q);
+            }
+            const int e = kf_sgd_update_batch(ps.data(), gs.data(), ms.data(), cnts.data(), b1 - b0,
+                                              dt, a == KF_ALGO_REDUCE_SCATTER ? W : 0,
+                                              sgd->hyper + b0, cs);
+            if (e != KF_OK) return fail(e, std::string("kf_sgd_update_batch: ") + kf_last_error());
+        }
         return KF_OK;
     };
 
@@ -656,7 +692,7 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
         for (int b = b0; b < b1 && rc3 == KF_OK; ++b) {
             const size_t q = counts[b] / W;
             if (!q) continue;
-            char *rcv   = static_cast<char *>(recvs[b]);
+            char *rcv   = static_cast<char *>(sgd ? sgd->params[b] : recvs[b]);
             const int e = T->all_gather(rcv + r * q * sz, rcv, q * sz, comm, s);
             if (e != 0) rc3 = tfail(e, "all_gather");
         }
@@ -675,7 +711,7 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
         return KF_OK;
     };
 
-    const int G = phases == 7 ? std::min(groups, nb) : 1;
+    const int G = phases == 7 && !sgd ? std::min(groups, nb) : 1;
     if (G <= 1) {
         Marks *mk = timing ? take_marks() : nullptr;
         auto mark = [&](int k) {
@@ -1594,6 +1630,47 @@ int kf_exchange_sma_batch(kf_exchange_t *ex, void *const *vs, void *const *sums,
     hipStream_t s = static_cast<hipStream_t>(stream);
     std::vector<const void *> snd(vs, vs + nb);
     return ex->batch(snd.data(), sums, counts, nb, dt, KungFu_SUM, 0, algo, s, &alpha);
+}
+
+int kf_exchange_sgd_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
+                          void *const *mom_shards, const size_t *counts, int nb,
+                          KungFu_Datatype dt, const kf_sgd_hyper *hyper, int algo, void *stream)
+{
+    if (!ex || nb < 0) return fail(KF_ERR_ARG, "kf_exchange_sgd_batch: bad arguments");
+    if (!is_float(dt)) return fail(KF_ERR_DTYPE, "kf_exchange_sgd_batch: f32, f16, bf16 and f64 only");
+    if (nb == 0) return KF_OK;
+    if (!params || !grads || !counts || !hyper) {
+        return fail(KF_ERR_ARG, "kf_exchange_sgd_batch: null table");
+    }
+    for (int b = 0; b < nb; ++b) {
+        if (counts[b] && (!params[b] || !grads[b])) {
+            return fail(KF_ERR_ARG, "kf_exchange_sgd_batch: null bucket");
+        }
+    }
+    if (algo < KF_ALGO_AUTO || algo > KF_ALGO_REDUCE_SCATTER_AVG) return fail(KF_ERR_ARG, "unknown algo");
+    // every rank must reach the same verdict before any collective is queued
+    const size_t W = static_cast<size_t>(ex->world), sz = static_cast<size_t>(tsize(dt));
+    for (int b = 0; b < nb; ++b) {
+        if (counts[b] == 0) continue;
+        if (counts[b] % W) {
+            return fail(KF_ERR_ARG, "kf_exchange_sgd_batch: counts must be multiples of the world "
+                                    "(padded buckets, no tails)");
+        }
+        void *m = mom_shards ? mom_shards[b] : nullptr;
+        if (hyper[b].momentum != 0 && !m) {
+            return fail(KF_ERR_ARG, "kf_exchange_sgd_batch: momentum != 0 needs a momentum shard");
+        }
+        if ((reinterpret_cast<uintptr_t>(params[b]) % 16) || (reinterpret_cast<uintptr_t>(grads[b]) % 16) ||
+            (reinterpret_cast<uintptr_t>(m) % 16) || (W > 1 && (counts[b] / W * sz) % 16)) {
+            return fail(KF_ERR_ARG, "kf_exchange_sgd_batch: buckets and their shards must start "
+                                    "16-byte aligned");
+        }
+    }
+    DeviceGuard g(ex->device);
+    std::lock_guard<std::mutex> lk(ex->mu);
+    const SgdStep step{params, mom_shards, hyper};
+    return ex->batch(grads, grads, counts, nb, dt, KungFu_SUM, 1, algo,
+                     static_cast<hipStream_t>(stream), nullptr, 7, &step);
 }
 
 int kf_exchange_set_pipeline(kf_exchange_t *ex, int groups)

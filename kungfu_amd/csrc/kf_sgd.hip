@@ -1,0 +1,513 @@
+// kf_sgd.hip — the SGD update fused into the shard step of a synchronous
+// exchange (include/kungfu_amd.h kf_sgd_update_batch):
+//
+//   reduce-scatter(grads) -> [own shard: g/np, weight decay, momentum,
+//                             p -= lr*g] -> all-gather(params)
+//
+// One batched element-wise launch over up to kSgdSeg segments of one dtype.
+// Every segment has its own param / grad / momentum pointers, its count and
+// its hyperparameters; all of that sits in the kernarg segment (lr changes
+// every step, so there is no device table to copy). A segment reads g, p and
+// m once and writes p and m once: 5 accesses per element (3 without momentum,
+// 4 on a group's first step, which does not read m).
+//
+// Arithmetic: torch.optim.SGD's single-tensor path, one IEEE operation per
+// step, no contraction (the pragma of kf_reduce_kernels.hpp and the
+// Makefile's -ffp-contract=off):
+//
+//   g = np > 0 ? sum / np : sum       (np a power of two: sum * 2^-k)
+//   if wd != 0:  g = g + wd*p
+//   if mu != 0:  m = first ? g : (mu*m) + (c*g)        c = 1 - dampening
+//                g = nesterov ? g + mu*m : m
+//   p = p + nlr*g                                      nlr = -lr
+//
+// f32 / f64 round every product and every sum in that type. f16 / bf16
+// compute in fp32 and round to the storage type where torch's tensor ops do:
+// after the /np, after the weight-decay add, after mu*m, after the momentum
+// add, after the nesterov add and after the final add; inside each of those
+// ops the alpha*x product and the add are two fp32 roundings.
+//
+// Shape: kf_reduce_kernels.hpp's batched kernels. One 256-thread block per
+// tile of 4 x 256 16-B vectors; all of a tile's loads (up to 12 per lane) are
+// issued before the arithmetic. Segments of about equal size are the rows of
+// a 2-D grid, others share a 1-D grid through a search table. Every pointer
+// is 16-byte aligned (the host checks it), so a segment is whole vectors and
+// a scalar tail of fewer than 16 bytes; there is no head.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "kf_reduce_kernels.hpp"
+#include "kungfu_amd.h"
+
+// Load / store policy of the streams, 1 = non-temporal. g is dead after this
+// kernel and is read non-temporally; p and m are read and then written in
+// place, p is read next by the all-gather and m by the next step, and both go
+// plain. ResNet-50's 25.6 M fp32 in 16 segments, kernel time from a kernel
+// trace, as a fraction of 8 TB/s (5 accesses per element; the SMA blend of
+// the same run beside it): all three non-temporal 0.680 (blend 0.793), plain
+// stores 0.740 (0.787), plain stores and plain p / m loads 0.768 (0.820);
+// event-timed, everything plain 0.676 against 0.720 for the shipped policy
+// (tools/bench_sharded_sgd.py, profiles/sharded_sgd/ab_policy*.jsonl).
+// Two vectors per lane per stream instead of four: 0.606 against 0.647.
+#ifndef KF_SGD_G_NT
+#define KF_SGD_G_NT 1
+#endif
+#ifndef KF_SGD_PM_NT
+#define KF_SGD_PM_NT 0
+#endif
+#ifndef KF_SGD_ST_NT
+#define KF_SGD_ST_NT 0
+#endif
+
+namespace kf
+{
+void set_last_error(const std::string &msg);  // kf_capi.hip: kf_last_error's text
+
+constexpr int kSgdSeg    = 32;
+constexpr int kSgdBlock  = 256;
+#ifndef KF_SGD_UNROLL
+#define KF_SGD_UNROLL 4  // 16-B vectors per lane per stream per tile
+#endif
+constexpr int kSgdUnroll = KF_SGD_UNROLL;
+
+enum { SGD_NESTEROV = 1, SGD_FIRST = 2 };
+
+// C: the compute type (float for f32 / f16 / bf16, double for f64).
+// One segment's entries sit together (one or two 64-byte lines of the kernarg
+// segment): a block reads them with one round of scalar loads. As separate
+// arrays they were nine lines per segment, and a launch over 16 segments
+// carried about 24 us that did not depend on its size (ResNet-50's shard
+// form, 64 MB of traffic, 36 us; tools/bench_sharded_sgd.py,
+// profiles/sharded_sgd/ab_layout.jsonl).
+template <typename C> struct SgdSeg {
+    void *p;
+    const void *g;
+    void *m;  // NULL: no momentum stream (mu == 0)
+    size_t n;
+    C nlr, mu, c, wd;
+    int flags;
+};
+template <typename C> struct SgdBatchArgs {
+    SgdSeg<C> seg[kSgdSeg];
+    unsigned blk0[kSgdSeg + 1];  // the search table (1-D grids only)
+    int nseg;
+};
+static_assert(sizeof(SgdBatchArgs<double>) + sizeof(Div) <= 3072, "kernarg budget");
+
+// one segment's scalars, read once per block (wave-uniform)
+template <typename C> struct SgdHyper {
+    C nlr, mu, c, wd;
+    bool has_m, first, nesterov;
+};
+
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+// Storage <-> compute. X is the compute scalar or a 2-lane vector of it:
+// `*` and `+` are then one IEEE operation per lane (v_pk_mul_f32 /
+// v_pk_add_f32 for fp32 pairs), and rnd() is the rounding to the storage type.
+template <typename T> struct SgdElt;
+template <> struct SgdElt<float> {
+    using S = float;
+    using C = float;
+    using X = f32x2;
+    __device__ static C widen(S s) { return s; }
+    __device__ static S narrow(C c) { return c; }
+    __device__ static C rnd(C c) { return c; }
+    __device__ static X rnd(X x) { return x; }
+    template <bool P2> __device__ static C div(C a, const Div &d)
+    {
+        return P2 ? __fmul_rn(a, d.fi) : __fdiv_rn(a, d.f);
+    }
+};
+template <> struct SgdElt<double> {
+    using S = double;
+    using C = double;
+    using X = f64x2;
+    __device__ static C widen(S s) { return s; }
+    __device__ static S narrow(C c) { return c; }
+    __device__ static C rnd(C c) { return c; }
+    __device__ static X rnd(X x) { return x; }
+    template <bool P2> __device__ static C div(C a, const Div &d)
+    {
+        return P2 ? __dmul_rn(a, d.di) : __ddiv_rn(a, d.d);
+    }
+};
+template <> struct SgdElt<f16_t> {
+    using S = uint16_t;
+    using C = float;
+    using X = f32x2;
+    __device__ static C widen(S s) { return f16_to_f32(s); }
+    __device__ static S narrow(C c) { return f32_to_f16(c); }
+    // The empty asm keeps a product from reaching the narrowing convert as a
+    // multiply: the compiler then selects v_fma_mixlo_f16 (x * y + 0), and
+    // the +0 addend turns a -0 product into +0.
+    __device__ static C rnd(C c)
+    {
+        asm("" : "+v"(c));
+        return f16_to_f32(f32_to_f16(c));
+    }
+    __device__ static X rnd(X x) { return X{rnd(x.x), rnd(x.y)}; }
+    template <bool P2> __device__ static C div(C a, const Div &d)
+    {
+        return P2 ? __fmul_rn(a, d.fi) : __fdiv_rn(a, d.f);
+    }
+};
+template <> struct SgdElt<bf16_t> {
+    using S = uint16_t;
+    using C = float;
+    using X = f32x2;
+    __device__ static C widen(S s) { return bf16_to_f32(s); }
+    __device__ static S narrow(C c) { return f32_to_bf16(c); }
+    __device__ static C rnd(C c) { return bf16_to_f32(f32_to_bf16(c)); }
+    __device__ static X rnd(X x) { return X{rnd(x.x), rnd(x.y)}; }
+    template <bool P2> __device__ static C div(C a, const Div &d)
+    {
+        return P2 ? __fmul_rn(a, d.fi) : __fdiv_rn(a, d.f);
+    }
+};
+
+// DIV: 0 = no /np, 1 = multiply by 2^-k, 2 = true division
+template <typename T, int DIV> struct SgdDiv {
+    using E = SgdElt<T>;
+    using C = typename E::C;
+    using X = typename E::X;
+    __device__ static C run(C g, const Div &d)
+    {
+        if constexpr (DIV == 0) return g;
+        else return E::rnd(E::template div<DIV == 1>(g, d));
+    }
+    __device__ static X run(X g, const Div &d)
+    {
+        if constexpr (DIV == 0) {
+            return g;
+        } else if constexpr (DIV == 1) {
+            const C inv = E::template div<true>(C(1), d);  // 2^-k, exact
+            return E::rnd(g * inv);
+        } else {
+            return E::rnd(X{E::template div<false>(g.x, d), E::template div<false>(g.y, d)});
+        }
+    }
+};
+
+// The update of H values (V = C) or of H lane pairs (V = X); g holds the
+// summed gradients on entry. Stage by stage over the H values, so that each
+// choice (on the segment's scalars: wave-uniform) is one branch per vector
+// and not one per element.
+template <typename T, int DIV, int H, typename V>
+__device__ __forceinline__ void sgd_math(V (&p)[H], V (&g)[H], V (&m)[H],
+                                         const SgdHyper<typename SgdElt<T>::C> &h, const Div &d)
+{
+    using E = SgdElt<T>;
+#pragma unroll
+    for (int i = 0; i < H; ++i) g[i] = SgdDiv<T, DIV>::run(g[i], d);
+    if (h.wd != 0) {
+#pragma unroll
+        for (int i = 0; i < H; ++i) g[i] = E::rnd(g[i] + h.wd * p[i]);
+    }
+    if (h.has_m) {
+        if (h.first) {
+#pragma unroll
+            for (int i = 0; i < H; ++i) m[i] = g[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < H; ++i) {
+                const V t = E::rnd(h.mu * m[i]);
+                m[i]      = E::rnd(t + h.c * g[i]);
+            }
+        }
+        if (h.nesterov) {
+#pragma unroll
+            for (int i = 0; i < H; ++i) g[i] = E::rnd(g[i] + h.mu * m[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < H; ++i) g[i] = m[i];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < H; ++i) p[i] = E::rnd(p[i] + h.nlr * g[i]);
+}
+
+// a 16-B vector of storage elements <-> N/2 two-lane compute values
+template <typename T> struct SgdVec {
+    using E = SgdElt<T>;
+    using S = typename E::S;
+    using X = typename E::X;
+    static constexpr int N = 16 / sizeof(S);
+    __device__ static void unpack(const u32x4 &raw, X (&x)[N / 2])
+    {
+        if constexpr (std::is_same<T, bf16_t>::value) {
+            // a 32-bit word holds two bf16 lanes: the low one widens by a
+            // shift, the high one by a mask
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                x[w] = X{__uint_as_float(raw[w] << 16), __uint_as_float(raw[w] & 0xffff0000u)};
+            }
+        } else {
+            Vec<S> v;
+            __builtin_memcpy(&v, &raw, 16);
+#pragma unroll
+            for (int i = 0; i < N / 2; ++i) x[i] = X{E::widen(v.e[2 * i]), E::widen(v.e[2 * i + 1])};
+        }
+    }
+    __device__ static u32x4 pack(const X (&x)[N / 2])
+    {
+        Vec<S> v;
+#pragma unroll
+        for (int i = 0; i < N / 2; ++i) {
+            v.e[2 * i]     = E::narrow(x[i].x);
+            v.e[2 * i + 1] = E::narrow(x[i].y);
+        }
+        u32x4 raw;
+        __builtin_memcpy(&raw, &v, 16);
+        return raw;
+    }
+};
+
+template <int NT> __device__ __forceinline__ void st_u4(void *base, size_t vi, const u32x4 &raw)
+{
+    u32x4 *p = reinterpret_cast<u32x4 *>(base) + vi;
+    if constexpr (NT) __builtin_nontemporal_store(raw, p);
+    else *p = raw;
+}
+
+// one vector: p and m updated and stored
+template <typename T, int DIV>
+__device__ __forceinline__ void sgd_vec(void *pp, void *pm, size_t vi, const u32x4 &rp,
+                                        const u32x4 &rg, const u32x4 &rm,
+                                        const SgdHyper<typename SgdElt<T>::C> &h, const Div &d)
+{
+    using SV        = SgdVec<T>;
+    using X         = typename SV::X;
+    constexpr int H = SV::N / 2;
+    X p[H], g[H], m[H];
+    SV::unpack(rp, p);
+    SV::unpack(rg, g);
+    SV::unpack(rm, m);
+    sgd_math<T, DIV, H, X>(p, g, m, h, d);
+    st_u4<KF_SGD_ST_NT>(pp, vi, SV::pack(p));
+    if (h.has_m) st_u4<KF_SGD_ST_NT>(pm, vi, SV::pack(m));
+}
+
+// Block `blk` of `nblk` on one segment.
+template <typename T, int DIV>
+__device__ __forceinline__ void sgd_body(void *pp, const void *pg, void *pm, size_t n,
+                                         const SgdHyper<typename SgdElt<T>::C> &h, const Div &d,
+                                         size_t blk, size_t nblk)
+{
+    using E         = SgdElt<T>;
+    using S         = typename E::S;
+    using C         = typename E::C;
+    constexpr int N = SgdVec<T>::N;
+    constexpr int U = kSgdUnroll, B = kSgdBlock;
+    const size_t nvec = n / N;
+    const bool ld_m   = h.has_m && !h.first;  // a first step never reads m
+
+    // the scalar tail: fewer than N elements, on the segment's first block
+    const size_t ti = nvec * N + threadIdx.x;
+    if (blk == 0 && ti < n) {
+        S *sp       = reinterpret_cast<S *>(pp);
+        const S *sg = reinterpret_cast<const S *>(pg);
+        S *sm       = reinterpret_cast<S *>(pm);
+        C p[1] = {E::widen(sp[ti])}, g[1] = {E::widen(sg[ti])};
+        C m[1] = {ld_m ? E::widen(sm[ti]) : C(0)};
+        sgd_math<T, DIV, 1, C>(p, g, m, h, d);
+        sp[ti] = E::narrow(p[0]);
+        if (h.has_m) sm[ti] = E::narrow(m[0]);
+    }
+
+    const size_t tile   = static_cast<size_t>(B) * U;
+    const size_t ntiles = (nvec + tile - 1) / tile;
+    for (size_t t = blk; t < ntiles; t += nblk) {
+        const size_t v0 = t * tile + threadIdx.x;
+        if (v0 + (U - 1) * B < nvec) {
+            // full tile: every load issued before the first use
+            u32x4 rp[U], rg[U], rm[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) rg[u] = ld_u4<KF_SGD_G_NT>(pg, v0 + u * B);
+#pragma unroll
+            for (int u = 0; u < U; ++u) rp[u] = ld_u4<KF_SGD_PM_NT>(pp, v0 + u * B);
+            if (ld_m) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) rm[u] = ld_u4<KF_SGD_PM_NT>(pm, v0 + u * B);
+            } else {
+#pragma unroll
+                for (int u = 0; u < U; ++u) rm[u] = u32x4{0, 0, 0, 0};
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                sgd_vec<T, DIV>(pp, pm, v0 + u * B, rp[u], rg[u], rm[u], h, d);
+            }
+        } else {
+            // ragged last tile
+            for (int u = 0; u < U; ++u) {
+                const size_t vi = v0 + u * B;
+                if (vi >= nvec) break;
+                const u32x4 rg = ld_u4<KF_SGD_G_NT>(pg, vi), rp = ld_u4<KF_SGD_PM_NT>(pp, vi);
+                const u32x4 rm = ld_m ? ld_u4<KF_SGD_PM_NT>(pm, vi) : u32x4{0, 0, 0, 0};
+                sgd_vec<T, DIV>(pp, pm, vi, rp, rg, rm, h, d);
+            }
+        }
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kSgdBlock)
+    sgd_update_kernel(SgdBatchArgs<typename SgdElt<T>::C> a, Div np, int div)
+{
+    using C = typename SgdElt<T>::C;
+    // Segments of about equal size (an exchange's shards of equal buckets)
+    // come as a 2-D grid, one row per segment: the segment is blockIdx.y,
+    // known before any kernarg load, and a row's blocks past the segment's
+    // last tile have nothing to do. Otherwise the segment of block b is the
+    // last s with blk0[s] <= b, searched in the kernarg table (wave-uniform
+    // scalar loads, one dependent load per step).
+    const bool rows = gridDim.y > 1;
+    int s           = static_cast<int>(blockIdx.y);
+    size_t blk = blockIdx.x, nblk = gridDim.x;
+    if (!rows) {
+        const unsigned b = blockIdx.x;
+        int lo = 0, hi = a.nseg - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (b >= a.blk0[mid]) lo = mid;
+            else hi = mid - 1;
+        }
+        s    = lo;
+        blk  = b - a.blk0[s];
+        nblk = a.blk0[s + 1] - a.blk0[s];
+    }
+    const SgdSeg<C> &g = a.seg[s];
+    SgdHyper<C> h;
+    h.nlr      = g.nlr;
+    h.mu       = g.mu;
+    h.c        = g.c;
+    h.wd       = g.wd;
+    h.has_m    = g.m != nullptr;
+    h.first    = (g.flags & SGD_FIRST) != 0;
+    h.nesterov = (g.flags & SGD_NESTEROV) != 0;
+    // the /np choice made once per kernel (kf_reduce_kernels.hpp EPI_MUL)
+    if (div == 0) sgd_body<T, 0>(g.p, g.g, g.m, g.n, h, np, blk, nblk);
+    else if (div == 1) sgd_body<T, 1>(g.p, g.g, g.m, g.n, h, np, blk, nblk);
+    else sgd_body<T, 2>(g.p, g.g, g.m, g.n, h, np, blk, nblk);
+}
+
+}  // namespace kf
+
+namespace
+{
+using namespace kf;
+
+int fail(int rc, const char *name, const std::string &what)
+{
+    set_last_error(std::string(name) + ": kf_sgd_update_batch: " + what);
+    return rc;
+}
+
+template <typename T>
+int launch_sgd(void *const *params, const void *const *grads, void *const *moms,
+               const size_t *counts, int nb, int np, const kf_sgd_hyper *hyper, hipStream_t s)
+{
+    using C         = typename SgdElt<T>::C;
+    constexpr int N = SgdVec<T>::N;
+    Div dv;  // as kf_capi.hip's make_div; np == 0 is never divided by
+    dv.f    = static_cast<float>(np);
+    dv.d    = static_cast<double>(np);
+    dv.pow2 = np > 0 && (np & (np - 1)) == 0;
+    dv.fi   = np > 0 ? 1.0f / dv.f : 0.0f;  // exact for powers of two
+    dv.di   = np > 0 ? 1.0 / dv.d : 0.0;
+    const int div = np == 0 ? 0 : (dv.pow2 ? 1 : 2);
+    SgdBatchArgs<C> a;
+    a.nseg          = 0;
+    size_t blocks   = 0, widest = 0;
+    auto flush      = [&]() -> int {
+        if (a.nseg == 0) return KF_OK;
+        a.blk0[a.nseg] = static_cast<unsigned>(blocks);
+        // one row per segment when that at most doubles the grid
+        const bool rows = a.nseg > 1 && widest * a.nseg <= 2 * blocks;
+        const dim3 grid = rows ? dim3(static_cast<unsigned>(widest), a.nseg)
+                               : dim3(static_cast<unsigned>(blocks));
+        sgd_update_kernel<T><<<grid, kSgdBlock, 0, s>>>(a, dv, div);
+        a.nseg = 0;
+        blocks = widest = 0;
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            return fail(KF_ERR_HIP, "KF_ERR_HIP", std::string("launch: ") + hipGetErrorString(e));
+        }
+        return KF_OK;
+    };
+    const size_t tile = static_cast<size_t>(kSgdBlock) * kSgdUnroll;
+    for (int b = 0; b < nb; ++b) {
+        const size_t n = counts[b];
+        if (n == 0) continue;
+        size_t nblk = (n / N + tile - 1) / tile;  // one block per tile
+        if (nblk < 1) nblk = 1;                   // a tail alone
+        if (nblk > 0x400000u) nblk = 0x400000u;   // then blocks stride over the tiles
+        if (blocks + nblk > 0x7fffffu) {          // grid * block stays below 2^32 threads,
+            const int rc = flush();               // also as rows (at most twice the blocks)
+            if (rc != KF_OK) return rc;
+        }
+        const kf_sgd_hyper &h = hyper[b];
+        SgdSeg<C> &g          = a.seg[a.nseg];
+        g.p                   = params[b];
+        g.g                   = grads[b];
+        g.m                   = h.momentum != 0 ? moms[b] : nullptr;
+        g.n                   = n;
+        // computed in double, cast once to the compute type
+        g.nlr   = static_cast<C>(-h.lr);
+        g.mu    = static_cast<C>(h.momentum);
+        g.c     = static_cast<C>(1.0 - h.dampening);
+        g.wd    = static_cast<C>(h.weight_decay);
+        g.flags = (h.nesterov ? SGD_NESTEROV : 0) | (h.first ? SGD_FIRST : 0);
+        a.blk0[a.nseg] = static_cast<unsigned>(blocks);
+        blocks += nblk;
+        if (nblk > widest) widest = nblk;
+        if (++a.nseg == kSgdSeg) {
+            const int rc = flush();
+            if (rc != KF_OK) return rc;
+        }
+    }
+    return flush();
+}
+
+bool off16(const void *p) { return (reinterpret_cast<uintptr_t>(p) % 16) != 0; }
+
+}  // namespace
+
+extern "C" {
+
+int kf_sgd_update_batch(void *const *params, const void *const *grads, void *const *moms,
+                        const size_t *counts, int nb, KungFu_Datatype dt, int np,
+                        const kf_sgd_hyper *hyper, void *stream)
+{
+    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
+    if (nb == 0) return KF_OK;
+    if (!params || !grads || !counts || !hyper) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
+    if (dt != KungFu_FLOAT && dt != KungFu_DOUBLE && dt != KungFu_FLOAT16 && dt != KungFu_BFLOAT16) {
+        return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE", "f32, f16, bf16 and f64 only");
+    }
+    if (np < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "np < 0");
+    for (int b = 0; b < nb; ++b) {
+        if (counts[b] == 0) continue;
+        void *m = moms ? moms[b] : nullptr;
+        if (!params[b] || !grads[b]) {
+            return fail(KF_ERR_ARG, "KF_ERR_ARG", "null pointer in a non-empty segment");
+        }
+        if (hyper[b].momentum != 0 && !m) {
+            return fail(KF_ERR_ARG, "KF_ERR_ARG", "momentum != 0 needs a momentum buffer");
+        }
+        if (off16(params[b]) || off16(grads[b]) || off16(m)) {
+            return fail(KF_ERR_ARG, "KF_ERR_ARG", "pointers must be 16-byte aligned");
+        }
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dt) {
+    case KungFu_FLOAT: return launch_sgd<float>(params, grads, moms, counts, nb, np, hyper, s);
+    case KungFu_DOUBLE: return launch_sgd<double>(params, grads, moms, counts, nb, np, hyper, s);
+    case KungFu_FLOAT16: return launch_sgd<f16_t>(params, grads, moms, counts, nb, np, hyper, s);
+    default: return launch_sgd<bf16_t>(params, grads, moms, counts, nb, np, hyper, s);
+    }
+}
+
+}  // extern "C"

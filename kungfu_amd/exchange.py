@@ -249,6 +249,36 @@ class NativeExchange:
         _lib.check(rc, "kf_exchange_sma_batch")
         return buckets
 
+    def sgd_step_(self, param_buckets, grad_buckets, mom_shards, hypers):
+        """The synchronous step with the SGD update on this rank's shards
+        (kf_exchange_sgd_batch): reduce-scatter of the gradient buckets,
+        ops.sgd_update_batch_'s kernel on the shard of every bucket (the / world
+        inside it), in-place all-gather of the parameter buckets. Queued on
+        the current stream. mom_shards[b] holds numel // world elements (None
+        where hypers[b]'s momentum is 0). The gradient buckets are scratch:
+        they hold nothing defined afterwards."""
+        params, grads = list(param_buckets), list(grad_buckets)
+        moms = [None] * len(params) if mom_shards is None else list(mom_shards)
+        hypers = list(hypers)
+        if not (len(params) == len(grads) == len(moms) == len(hypers)):
+            raise ValueError("sgd_step_: one grad bucket, momentum shard and hyper per bucket")
+        if not params:
+            return params
+        self._check(params + grads + [m for m in moms if m is not None])
+        for p, g, m in zip(params, grads, moms):
+            if g.numel() != p.numel() or \
+                    (m is not None and m.numel() * self.world != p.numel()):
+                raise ValueError("sgd_step_: bucket / shard sizes do not match")
+        rc = self.lib.kf_exchange_sgd_batch(
+            self._h, _lib.ptr_array([p.data_ptr() for p in params]),
+            _lib.ptr_array([g.data_ptr() for g in grads]),
+            _lib.ptr_array([0 if m is None else m.data_ptr() for m in moms]),
+            _arr(ctypes.c_size_t, [p.numel() for p in params]), len(params),
+            int(kungfu_dtype(params[0])), _lib.sgd_hyper_array(hypers), ALGOS[self.algo],
+            torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(rc, "kf_exchange_sgd_batch")
+        return params
+
     def all_reduce_named(self, name, buf, op="sum", average=False, stream=None, callback=None):
         """kf_exchange_all_reduce_named: in place, paired with the peers' calls
         of the same name whatever order each rank starts its names in

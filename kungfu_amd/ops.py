@@ -179,6 +179,41 @@ def sma_blend_batch_(vs, sums, np_, alpha, stream=None):
     return vs
 
 
+def sgd_update_batch_(params, grads, moms, hypers, np_=0, stream=None):
+    """The SGD update of many flat segments of one float dtype in one launch
+    per 32 of them (kf_sgd_update_batch, kungfu_amd/csrc/kf_sgd.hip), in
+    place on params and moms:
+
+      g = grads[b] / np_ (np_ > 0) ; g += wd * p ; m = first ? g : mu * m + (1 - dampening) * g
+      g = nesterov ? g + mu * m : m ; p -= lr * g
+
+    with torch.optim.SGD's single-tensor rounding. hypers[b] is a dict with
+    lr and optionally momentum, dampening, weight_decay, nesterov, first.
+    moms[b] may be None where momentum is 0 (moms itself may be None). Every
+    tensor starts 16-byte aligned. grads are only read."""
+    params, grads, hypers = list(params), list(grads), list(hypers)
+    moms = [None] * len(params) if moms is None else list(moms)
+    if not (len(params) == len(grads) == len(moms) == len(hypers)):
+        raise ValueError("sgd_update_batch_: one grad, momentum and hyper per param segment")
+    if not params:
+        return params
+    live = [m for m in moms if m is not None]
+    _check_dev(params + grads + live)
+    for p, g, m in zip(params, grads, moms):
+        if g.numel() != p.numel() or g.dtype != params[0].dtype or p.dtype != g.dtype or \
+                (m is not None and (m.numel() != p.numel() or m.dtype != p.dtype)):
+            raise ValueError("sgd_update_batch_: shape/dtype mismatch")
+    lib = _lib.load()
+    cnt = (ctypes.c_size_t * len(params))(*[p.numel() for p in params])
+    rc = lib.kf_sgd_update_batch(_lib.ptr_array([p.data_ptr() for p in params]),
+                                 _lib.ptr_array([g.data_ptr() for g in grads]),
+                                 _lib.ptr_array([0 if m is None else m.data_ptr() for m in moms]),
+                                 cnt, len(params), int(kungfu_dtype(params[0])), int(np_),
+                                 _lib.sgd_hyper_array(hypers), _stream(stream, params[0].device))
+    _lib.check(rc, "kf_sgd_update_batch", source="")
+    return params
+
+
 _NORM_DTYPES = (torch.float32, torch.float16, torch.bfloat16, torch.float64)
 
 

@@ -22,6 +22,10 @@ Operator surface kept from the reference:
   (async_sgd.py): asynchronous; every step averages the variables with one
   peer's latest published model, read out of that peer's HBM through a
   device-side model store (``pairavg.PeerModelStore``), with no collective.
+* ``ShardedSGDOptimizer(optimizer, named_parameters=None, ...)`` — S-SGD with
+  the SGD update itself moved onto each rank's shard, between the gradients'
+  reduce-scatter and an all-gather of the parameters; the momentum state is
+  sharded over the ranks. The package's own (the reference has none).
 
 Buckets: parameters are grouped (in registration order, per dtype/device) into
 flat padded device buckets (``collective.GradBuckets``); ``p.grad`` (S-SGD) or
@@ -637,4 +641,186 @@ def PairAveragingOptimizer(optimizer, named_parameters=None, bucket_bytes=32 << 
     RCCL plays no part."""
     opt = _wrap(optimizer, _PairAveraging)
     opt._kf_setup_pair(named_parameters, bucket_bytes, slots, seed, peer_selector)
+    return opt
+
+
+class _ShardedSGD(_Bucketed):
+    """reduce-scatter(grads) -> SGD update on the own shard -> all-gather(params).
+    Parameters and gradients live in two GradBuckets of identical layout per
+    (param group, dtype, device); the momentum is one shard per bucket."""
+
+    def _kf_build_sharded(self):
+        import torch
+        mine = {id(p) for p in self._kf_params}
+        self._kf_groups = []
+        for gi, group in enumerate(self.param_groups):
+            by = {}
+            for p in group["params"]:
+                if id(p) in mine:
+                    by.setdefault((p.dtype, p.device), []).append(p)
+            for (dtype, device), ps in by.items():
+                if dtype not in (torch.float32, torch.float16, torch.bfloat16, torch.float64):
+                    raise TypeError("ShardedSGDOptimizer updates f32, f16, bf16 and f64 "
+                                    "parameters, not %s" % dtype)
+                numels = [p.numel() for p in ps]
+                pb = GradBuckets(numels, dtype, device, self._kf_ex.world,
+                                 bucket_bytes=self._kf_bucket_bytes)
+                gb = GradBuckets(numels, dtype, device, self._kf_ex.world,
+                                 bucket_bytes=self._kf_bucket_bytes)
+                for p, view in zip(ps, pb.views):  # move the variables into buckets
+                    v = view.view_as(p)
+                    v.copy_(p.data)
+                    p.data = v
+                self._kf_groups.append({"gi": gi, "ps": ps, "pb": pb, "gb": gb, "moms": None,
+                                        "first": True})
+
+    def _kf_moms(self, G):
+        """The group's zeroed momentum shards, allocated when first needed."""
+        if G["moms"] is None:
+            import torch
+            world = self._kf_ex.world
+            G["moms"] = [torch.zeros(b.numel() // world, dtype=b.dtype, device=b.device)
+                         for b in G["pb"].buckets]
+            G["first"] = True
+        return G["moms"]
+
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            import torch
+            with torch.enable_grad():
+                loss = closure()
+        if self._kf_groups is None:
+            self._kf_build_sharded()
+        for G in self._kf_groups:
+            _SyncSGD._kf_place(G["ps"], G["gb"])
+        for G in self._kf_groups:
+            pg = self.param_groups[G["gi"]]  # read at every step: schedulers change them
+            mu = float(pg["momentum"])
+            moms = self._kf_moms(G) if mu != 0 else None
+            h = {"lr": float(pg["lr"]), "momentum": mu, "dampening": float(pg["dampening"]),
+                 "weight_decay": float(pg["weight_decay"]), "nesterov": bool(pg["nesterov"]),
+                 "first": G["first"]}
+            nb = len(G["pb"].buckets)
+            self._kf_ex.sgd_step_(G["pb"].buckets, G["gb"].buckets, moms, [h] * nb)
+            if mu != 0:
+                G["first"] = False
+        _finish(self._kf_ex)
+        return loss
+
+    def _kf_gather(self, shard):
+        """All ranks' shards of one bucket, in rank order. The shards travel
+        as integers through the exchange's sum, with zeros everywhere else, so
+        every bit arrives as it is (16-bit patterns widened to int32, which
+        every transport sums)."""
+        import torch
+        ex = self._kf_ex
+        q = shard.numel()
+        if ex.world == 1:
+            return shard.clone()
+        if shard.element_size() == 2:
+            full = torch.zeros(q * ex.world, dtype=torch.int32, device=shard.device)
+            full[ex.rank * q:(ex.rank + 1) * q].copy_(shard.view(torch.int16))
+            ex.all_reduce_([full], op="sum", average=False)
+            return full.to(torch.int16).view(shard.dtype)
+        ints = torch.int32 if shard.element_size() == 4 else torch.int64
+        full = torch.zeros(q * ex.world, dtype=shard.dtype, device=shard.device)
+        full[ex.rank * q:(ex.rank + 1) * q].copy_(shard)
+        ex.all_reduce_([full.view(ints)], op="sum", average=False)
+        return full
+
+    def momentum_buffers(self):
+        """Collective: {parameter: its full momentum buffer}, gathered from
+        the ranks' shards (a new tensor each; empty for a group that has not
+        yet stepped with momentum). With load_momentum_buffers, the
+        checkpoint path: `state` stays empty, so state_dict() carries no
+        momentum."""
+        out = {}
+        for G in self._kf_groups or []:
+            if G["moms"] is None or G["first"]:
+                continue
+            off = {}
+            for p, v in zip(G["ps"], G["pb"].views):
+                off[id(p)] = v.data_ptr()
+            for b, m in zip(G["pb"].buckets, G["moms"]):
+                full = self._kf_gather(m)
+                lo, hi = b.data_ptr(), b.data_ptr() + b.numel() * b.element_size()
+                for p in G["ps"]:
+                    at = off[id(p)]
+                    if lo <= at < hi and p.numel():
+                        i = (at - lo) // b.element_size()
+                        out[p] = full[i:i + p.numel()].view_as(p).clone()
+        _finish(self._kf_ex)
+        return out
+
+    def load_momentum_buffers(self, mapping):
+        """{parameter: full momentum buffer} (momentum_buffers' result, on
+        every rank): each rank keeps its own slice of every bucket, and the
+        next step is no longer a group's first. A group none of whose
+        parameters is in `mapping` is left as it is; a parameter missing from
+        a loaded group gets zeros."""
+        import torch
+        if self._kf_groups is None:
+            self._kf_build_sharded()
+        ex = self._kf_ex
+        for G in self._kf_groups:
+            if not any(p in mapping for p in G["ps"]):
+                continue
+            moms = self._kf_moms(G)
+            for b, m in zip(G["pb"].buckets, moms):
+                full = torch.zeros_like(b)
+                lo, hi = b.data_ptr(), b.data_ptr() + b.numel() * b.element_size()
+                for p, v in zip(G["ps"], G["pb"].views):
+                    if lo <= v.data_ptr() < hi and p.numel() and p in mapping:
+                        i = (v.data_ptr() - lo) // b.element_size()
+                        full[i:i + p.numel()].copy_(mapping[p].reshape(-1))
+                q = m.numel()
+                m.copy_(full[ex.rank * q:(ex.rank + 1) * q])
+            G["first"] = False
+
+
+def ShardedSGDOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20):
+    """Synchronous SGD with the optimizer update sharded over the ranks
+    (sharded optimizer state): every step is
+
+      reduce-scatter(grads) -> [own shard: g / np, weight decay, momentum,
+                                p -= lr * g] -> all-gather(params)
+
+    in one call of the exchange's `sgd_step_` per (param group, dtype): the
+    same xGMI bytes as S-SGD's gradient all-reduce, the update over 1 / np
+    of the model per rank in one batched HIP launch (ops.sgd_update_batch_),
+    and a momentum buffer of 1 / np of the model per rank. The arithmetic is
+    torch.optim.SGD's single-tensor path (foreach=False) on the averaged
+    gradient, rounded as include/kungfu_amd.h kf_sgd_update_batch states.
+
+    `optimizer` must be a torch.optim.SGD (TypeError otherwise); it only
+    lends its class and its param_groups: its own step() is never called and
+    `state` stays empty. lr, momentum, dampening, weight_decay and nesterov
+    are read from param_groups at every step, so LR schedulers work.
+
+    Two differences from torch.optim.SGD:
+      * a parameter without a gradient is updated as with a zero gradient
+        (weight decay and momentum still move it); torch skips it;
+      * after step(), p.grad does not hold the averaged gradient: the
+        gradient buckets are scratch of the exchange.
+
+    momentum_buffers() (collective) and load_momentum_buffers(mapping) are
+    the checkpoint path for the sharded momentum.
+
+    Not offered: overlap=True, the hierarchical (multi-host) path, maximize,
+    differentiable, and any optimizer other than SGD."""
+    import torch
+    if not isinstance(optimizer, torch.optim.SGD):
+        raise TypeError("ShardedSGDOptimizer wraps a torch.optim.SGD, not %s"
+                        % type(optimizer).__name__)
+    for g in optimizer.param_groups:
+        if g.get("maximize", False):
+            raise ValueError("ShardedSGDOptimizer: maximize=True is not supported")
+        if g.get("differentiable", False):
+            raise ValueError("ShardedSGDOptimizer: differentiable=True is not supported")
+    opt = _wrap(optimizer, _ShardedSGD)
+    opt._kf_setup(named_parameters, exchange, bucket_bytes)
+    if not hasattr(opt._kf_ex, "sgd_step_"):
+        raise ValueError("ShardedSGDOptimizer needs an exchange with sgd_step_() "
+                         "(collective.Exchange or exchange.NativeExchange)")
     return opt

@@ -20,13 +20,17 @@ reference has no torch version, so it is the package's own.
 
 ``PairAveragingOptimizer`` (async_sgd.py; TF only in the reference) likewise
 takes ``named_parameters`` positionally.
+
+``ShardedSGDOptimizer`` (the package's own: S-SGD with the SGD update and its
+momentum sharded over the ranks) likewise takes ``named_parameters``
+positionally.
 """
 from .. import optimizers as _opt
 from ..optimizers import SynchronousAveragingOptimizer
 
 __all__ = ["SynchronousSGDOptimizer", "SynchronousAveragingOptimizer",
            "MonitorGradientNoiseScaleOptimizer", "MonitorGradientVarianceOptimizer",
-           "PairAveragingOptimizer"]
+           "PairAveragingOptimizer", "ShardedSGDOptimizer"]
 
 
 def SynchronousSGDOptimizer(optimizer, named_parameters, op=None, **kwargs):
@@ -58,3 +62,9 @@ def PairAveragingOptimizer(optimizer, named_parameters, **kwargs):
     """kungfu_amd.optimizers.PairAveragingOptimizer with `named_parameters`
     positional."""
     return _opt.PairAveragingOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
+
+
+def ShardedSGDOptimizer(optimizer, named_parameters, **kwargs):
+    """kungfu_amd.optimizers.ShardedSGDOptimizer with `named_parameters`
+    positional."""
+    return _opt.ShardedSGDOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
