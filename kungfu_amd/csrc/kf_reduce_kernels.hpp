@@ -66,6 +66,21 @@ __device__ __forceinline__ uint16_t f32_to_f16(float f)
     return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f));
 }
 
+// RNE narrow of an fp32 PRODUCT. Handed a bare multiply, the compiler selects
+// v_fma_mixlo_f16 (x * y + 0, rounded once to fp16) for the multiply and the
+// convert together, and under round-to-nearest a -0 product plus the +0
+// addend is +0: the sign of a zero result is lost. The empty asm keeps the
+// product an fp32 value of its own, so the narrow stays v_cvt_f16_f32. For
+// the element-at-a-time narrow of a multiply's result (Elt<f16_t>::div,
+// SgdElt<f16_t>::rnd); where the compiler packs or goes native instead, the
+// call site says so. tests/test_isa.py looks for the x * y + 0 form in every
+// kernel of the built library.
+__device__ __forceinline__ uint16_t f32_product_to_f16(float p)
+{
+    asm("" : "+v"(p));
+    return f32_to_f16(p);
+}
+
 __device__ __forceinline__ float bf16_to_f32(uint16_t h)
 {
     return __uint_as_float(static_cast<uint32_t>(h) << 16);
@@ -179,10 +194,22 @@ template <> struct Elt<f16_t> {
         static_assert(OP == OP_SUM, "fp16 supports SUM only");
         return f32_to_f16(__fadd_rn(f16_to_f32(a), f16_to_f32(b)));
     }
-    template <bool P2> __device__ static S div(Acc a, const Div &dv)
+    // LANE: one lane of a 16-B vector (Lane<f16_t>::emit). The vector bodies
+    // multiply their lanes in pairs (v_pk_mul_f32, which has no mixed form)
+    // and narrow them with v_cvt_pk_f16_f32; an asm on every lane's product
+    // splits the pairs (the k = 2 average: 22 v_pk_mul_f32 -> 0), so only the
+    // element-at-a-time callers, whose scalar multiply is the one the compiler
+    // fuses with the narrow, go through f32_product_to_f16.
+    template <bool P2, bool LANE = false> __device__ static S div(Acc a, const Div &dv)
     {
         const float x = f16_to_f32(a);
-        return f32_to_f16(P2 ? __fmul_rn(x, dv.fi) : __fdiv_rn(x, dv.f));
+        if constexpr (!P2) {
+            return f32_to_f16(__fdiv_rn(x, dv.f));
+        } else if constexpr (LANE) {
+            return f32_to_f16(__fmul_rn(x, dv.fi));
+        } else {
+            return f32_product_to_f16(__fmul_rn(x, dv.fi));
+        }
     }
 };
 
@@ -251,7 +278,11 @@ template <typename T, typename = void> struct Lane {
     template <int OP, int EPI> __device__ static W emit(const Acc &a, const Div &np)
     {
         if constexpr (EPI == EPI_DIV || EPI == EPI_MUL) {
-            return Elt<T>::template div<EPI == EPI_MUL>(a, np);
+            if constexpr (std::is_same<T, f16_t>::value) {
+                return Elt<T>::template div<EPI == EPI_MUL, true>(a, np);
+            } else {
+                return Elt<T>::template div<EPI == EPI_MUL>(a, np);
+            }
         } else {
             return finish<T, OP>(a);
         }

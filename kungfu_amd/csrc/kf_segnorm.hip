@@ -73,6 +73,8 @@ template <> struct NormElt<f16_t> {
     __device__ static double var(S a, S b)
     {
         const float fb = f16_to_f32(b);
+        // compiled to the native v_mul_f16 / v_sub_f16 (same value); a square
+        // is never -0, so the x * y + 0 form could not hurt it either
         const float p  = f16_to_f32(f32_to_f16(__fmul_rn(fb, fb)));
         return static_cast<double>(f16_to_f32(f32_to_f16(__fsub_rn(f16_to_f32(a), p))));
     }

@@ -139,14 +139,11 @@ template <> struct SgdElt<f16_t> {
     using X = f32x2;
     __device__ static C widen(S s) { return f16_to_f32(s); }
     __device__ static S narrow(C c) { return f32_to_f16(c); }
-    // The empty asm keeps a product from reaching the narrowing convert as a
-    // multiply: the compiler then selects v_fma_mixlo_f16 (x * y + 0), and
-    // the +0 addend turns a -0 product into +0.
-    __device__ static C rnd(C c)
-    {
-        asm("" : "+v"(c));
-        return f16_to_f32(f32_to_f16(c));
-    }
+    // rnd() is handed products: f32_product_to_f16 (kf_reduce_kernels.hpp)
+    // keeps them from reaching the narrowing convert as a multiply, which
+    // the compiler would select as v_fma_mixlo_f16 (x * y + 0): the +0
+    // addend turns a -0 product into +0.
+    __device__ static C rnd(C c) { return f16_to_f32(f32_product_to_f16(c)); }
     __device__ static X rnd(X x) { return X{rnd(x.x), rnd(x.y)}; }
     template <bool P2> __device__ static C div(C a, const Div &d)
     {

@@ -346,6 +346,7 @@ def test_k1_copy_and_empty(lib, dev):
 @pytest.mark.parametrize("np_", [1, 2, 3, 4, 7, 8])
 @pytest.mark.parametrize("dt", ["f32", "f64", "f16", "bf16"])
 def test_avg_epilogue(orc, dev, np_, dt):
+    """Standard-normal data; IEEE specials: tests/test_epilogue_specials_gpu.py."""
     from kungfu_amd import ops
     rng = np.random.default_rng(np_ * 7)
     n = 300001
@@ -371,6 +372,7 @@ def test_avg_epilogue(orc, dev, np_, dt):
 
 @pytest.mark.parametrize("dt", ["f32", "f64", "f16", "bf16"])
 def test_sma_blend(orc, dev, dt):
+    """Standard-normal data; IEEE specials: tests/test_epilogue_specials_gpu.py."""
     from kungfu_amd import ops
     rng = np.random.default_rng(13)
     n = 250007

@@ -264,3 +264,35 @@ def test_two_input_reduce_issues_all_loads_first(kernels):
         assert best >= 8, (name, best)
         checked += 1
     assert checked >= 40, checked
+
+
+MIX_FMA = re.compile(r"^v_(fma|mad)_mix(lo|hi)?_f(16|32)\s+(.*)$")
+
+
+def test_no_mixed_fma_adds_a_constant_zero(kernels):
+    """No kernel of any code object in the library holds a mixed-precision
+    FMA (v_fma_mix* / v_mad_mix*) whose addend is the inline constant 0.
+
+    That is how the compiler selects a multiply followed by a narrowing
+    convert: x * y + (+0), rounded once. Under round-to-nearest a -0 product
+    plus +0 is +0, so the sign of a zero result is lost. Seven fp16 / np
+    kernels carried one such instruction each, in the scalar head and tail of
+    the power-of-two average (reduce_kernel<f16_t, SUM, EPI_DIV> for k = 1, 2
+    and runtime k, the three reduce_batch_kernel forms and
+    reduce_spread_kernel), before Elt<f16_t>::div narrowed its product through
+    f32_product_to_f16 (kf_reduce_kernels.hpp; DESIGN.md section 3, "The fp16
+    narrow of a product").
+    A mixed FMA with a real addend, should one ever be wanted, passes."""
+    assert len(kernels) >= 300, len(kernels)  # every code object was read
+    bad = []
+    for name, lines in kernels.items():
+        for ins in lines:
+            m = MIX_FMA.match(ins)
+            if not m:
+                continue
+            # dst, src0, src1, src2, then modifiers after a space
+            ops = [o.strip() for o in m.group(4).split(",")]
+            assert len(ops) >= 4, ins
+            if ops[3].split()[0] in ("0", "0.0", "-0", "0x0"):
+                bad.append((name, ins))
+    assert not bad, (len(bad), bad[:7])
