@@ -478,6 +478,16 @@ class _SMA(_Bucketed):
             self._kf_start_sums()
         return out
 
+    def wait_overlap(self):
+        """overlap=True leaves the next step's sum in flight when step()
+        returns. After the last step, wait for it here (collective: every
+        rank) before the process group or the exchange is torn down under
+        it. A later step() starts the sum again, so the values are the same
+        either way."""
+        for h in self._kf_pending or []:
+            h.wait()
+        self._kf_pending = None
+
 
 def SynchronousAveragingOptimizer(optimizer, named_parameters=None, alpha=0.1,
                                   exchange=None, bucket_bytes=32 << 20, overlap=False):
@@ -488,7 +498,8 @@ def SynchronousAveragingOptimizer(optimizer, named_parameters=None, alpha=0.1,
     end of step() on the exchange's stream, so it runs during that step's
     forward and backward; step() then waits for it and blends. Same values as
     overlap=False, provided the variables change only through step() (the
-    first step reduces synchronously)."""
+    first step reduces synchronously). The last step leaves a sum in flight:
+    call wait_overlap() before destroying the process group."""
     opt = _wrap(optimizer, _SMA)
     opt._kf_setup(named_parameters, exchange, bucket_bytes)
     opt._kf_alpha = float(alpha)

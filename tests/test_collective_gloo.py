@@ -221,7 +221,11 @@ def body_sma(rank, world, use_gpu):
 def body_sma_overlap(rank, world, use_gpu):
     """SMA with overlap=True (the next step's sum started at the end of
     step()) gives the same parameters, bit for bit, as overlap=False, over
-    three SGD steps from replicas that start different."""
+    three SGD steps from replicas that start different. The sum the last
+    step leaves in flight is waited for after the second step (the third
+    then starts it again: same bits) and at the end, so that no collective
+    is still running when the caller destroys the process group (a rank
+    once aborted at exit there)."""
     from kungfu_amd.collective import Exchange
     from kungfu_amd.optimizers import SynchronousAveragingOptimizer
     ms = [_model(seed=rank), _model(seed=rank)]
@@ -236,6 +240,9 @@ def body_sma_overlap(rank, world, use_gpu):
             opt.step()
         for a, b in zip(ms[0].parameters(), ms[1].parameters()):
             assert torch.equal(a.detach(), b.detach()), step
+        if step >= 1:
+            opts[1].wait_overlap()
+            assert opts[1]._kf_pending is None
 
 
 # ---- tests -------------------------------------------------------------------

@@ -305,9 +305,11 @@ def test_alignment_and_aliasing(lib, orc, dev):
 @pytest.mark.parametrize("dt,k", [("f32", 5), ("f32", 8), ("bf16", 4), ("f16", 3), ("u8", 6)])
 def test_k_fold_inputs_at_other_residues(lib, orc, dev, dt, k):
     """The runtime-k fold with inputs at 16-B residues other than the
-    output's: inputs 2..k-1 go through the one-in-flight inline-asm loads
-    (ld_vec_serial) at unaligned addresses; the left fold in input order must
-    equal the oracle's chain."""
+    output's, on a small grid (74 blocks, 19 for u8: below kSerialMinBlocks,
+    so every input's four vectors are loaded together at unaligned
+    addresses); the left fold in input order must equal the oracle's chain.
+    The one-in-flight inline-asm loads (ld_vec_serial) at these residues need
+    a launch of 2048 blocks: tests/test_large_launch_gpu.py."""
     from kungfu_amd import _lib
     from oracle.oracle import DT, NP
     rng = np.random.default_rng(zlib.crc32(("res" + dt).encode()) + k)
