@@ -182,6 +182,38 @@ int kf_sgd_update_batch(void *const *params, const void *const *grads, void *con
                         const size_t *counts, int nb, KungFu_Datatype dt, int np,
                         const kf_sgd_hyper *hyper, void *stream);
 
+/* Adam / AdamW update of nb segments of one dtype in one launch per 24 of
+ * them (kungfu_amd/csrc/kf_adam.hip): torch.optim.Adam / AdamW's single-tensor
+ * arithmetic on a summed gradient. Each parenthesised operation is one IEEE
+ * operation, no contraction:
+ *   g = np > 0 ? grads[b][i] / np : grads[b][i]     (kf_bucket_div's rounding)
+ *   weight_decay != 0, decoupled == 0 (Adam, L2):  g = g + (wd*p)
+ *   weight_decay != 0, decoupled != 0 (AdamW):     p = dk*p        dk = 1 - lr*wd
+ *   m = (b1*m) + (c1*g)                          c1 = 1 - beta1
+ *   v = (b2*v) + (c2*(g*g))                      c2 = 1 - beta2
+ *   d = (sqrt(v) / s2) + eps                     s2 = sqrt(bias_correction2)
+ *   p = p + (nss*(m / d))                        nss = -(lr / bias_correction1)
+ * dk, c1, c2, s2 and nss are computed in double on the host and cast once to
+ * the compute type. The caller passes the bias corrections 1 - beta^t of its
+ * step t >= 1, computed in double (both must be > 0). The sqrt and both
+ * divisions are correctly rounded. f32 / f64 round every operation in that
+ * type. bf16 computes in fp32 and rounds to bf16 where torch's tensor ops
+ * do: after the /np, after the L2 add or the decay multiply, after m (once:
+ * torch's lerp_ is one op), after b2*v, after the v add, after the sqrt,
+ * after the / s2, after the + eps and after the final add. m is two products
+ * and a sum, not torch's lerp.
+ * f32, f64 and bf16 only; the state (exp_avgs, exp_avg_sqs) has the
+ * parameters' dtype and starts as zeros. f16 is KF_ERR_DTYPE: eps = 1e-8
+ * rounds to 0 in f16, so every element with v == 0 would be 0 / 0.
+ * Segment b is counts[b] elements at params[b], grads[b] (read only),
+ * exp_avgs[b] and exp_avg_sqs[b] with its own hyper[b] (a host array of nb,
+ * read before the call returns). Every pointer is 16-byte aligned. g, p, m
+ * and v are read once, p, m and v written once. */
+typedef struct { double lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2; int decoupled; } kf_adam_hyper;
+int kf_adam_update_batch(void *const *params, const void *const *grads, void *const *exp_avgs,
+                         void *const *exp_avg_sqs, const size_t *counts, int nb,
+                         KungFu_Datatype dt, int np, const kf_adam_hyper *hyper, void *stream);
+
 /* ---- gradient monitors: segmented squared norms ------------------------- */
 
 /* What MonitorGradientNoiseScaleOptimizer and MonitorGradientVarianceOptimizer
@@ -704,6 +736,22 @@ int kf_exchange_sma_batch(kf_exchange_t *ex, void *const *vs, void *const *sums,
 int kf_exchange_sgd_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
                           void *const *mom_shards, const size_t *counts, int nb,
                           KungFu_Datatype dt, const kf_sgd_hyper *hyper, int algo, void *stream);
+/* kf_exchange_sgd_batch with the Adam / AdamW update (kf_adam_update_batch)
+ * on the shard: reduce-scatter of the gradient buckets (under auto, bf16
+ * takes the all-to-all and the rank-order fold), the update on params[b] +
+ * rank * q, grads[b] + rank * q, exp_avg_shards[b] and exp_avg_sq_shards[b]
+ * of q = counts[b] / world elements (np = world after a plain reduce-scatter,
+ * 0 after the fold or under rs_avg), in-place all-gather of the PARAMETER
+ * buckets. World 1 on the built-in transport runs the update over the whole
+ * buckets with np = 1. f32, f64 and bf16. Every counts[b] is a multiple of
+ * the world, buckets and shards start 16-byte aligned and both state shards
+ * are there for every non-empty bucket, or KF_ERR_ARG before any collective.
+ * hyper[b].lr etc. as kf_adam_update_batch. Un-pipelined; follows
+ * kf_exchange_set_timing as kf_exchange_sgd_batch does. */
+int kf_exchange_adam_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
+                           void *const *exp_avg_shards, void *const *exp_avg_sq_shards,
+                           const size_t *counts, int nb, KungFu_Datatype dt,
+                           const kf_adam_hyper *hyper, int algo, void *stream);
 /* Pipelined schedule for the batch calls (default 1 = off): the buckets of a
  * call are split into `groups` groups of consecutive buckets of about equal
  * bytes; the RCCL phases stay on the caller's stream in the same order on

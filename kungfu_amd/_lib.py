@@ -119,6 +119,8 @@ EXPORTED = (
     "kf_pairavg_last_error",
     "kf_sgd_update_batch",
     "kf_exchange_sgd_batch",
+    "kf_adam_update_batch",
+    "kf_exchange_adam_batch",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -157,6 +159,30 @@ def sgd_hyper_array(hypers):
         a.lr, a.momentum = float(h["lr"]), float(h.get("momentum", 0.0))
         a.dampening, a.weight_decay = float(h.get("dampening", 0.0)), float(h.get("weight_decay", 0.0))
         a.nesterov, a.first = int(bool(h.get("nesterov", False))), int(bool(h.get("first", False)))
+    return arr
+
+
+class AdamHyper(ctypes.Structure):
+    """kf_adam_hyper (include/kungfu_amd.h): one segment's Adam scalars."""
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("bias_correction1", ctypes.c_double), ("bias_correction2", ctypes.c_double),
+                ("decoupled", ctypes.c_int)]
+
+
+def adam_hyper_array(hypers):
+    """A kf_adam_hyper[] from dicts with lr, betas = (beta1, beta2), eps,
+    weight_decay (torch.optim.Adam's param-group keys), `decoupled` (AdamW)
+    and `step` (>= 1): the bias corrections 1 - beta**step are taken here, in
+    Python doubles, as torch takes them."""
+    arr = (AdamHyper * max(1, len(hypers)))()
+    for a, h in zip(arr, hypers):
+        b1, b2 = (float(b) for b in h.get("betas", (0.9, 0.999)))
+        t = int(h["step"])
+        a.lr, a.beta1, a.beta2 = float(h["lr"]), b1, b2
+        a.eps, a.weight_decay = float(h.get("eps", 1e-8)), float(h.get("weight_decay", 0.0))
+        a.bias_correction1, a.bias_correction2 = 1.0 - b1 ** t, 1.0 - b2 ** t
+        a.decoupled = int(bool(h.get("decoupled", False)))
     return arr
 
 
@@ -429,6 +455,13 @@ def load():
     lib.kf_exchange_sgd_batch.argtypes = [c_void_p, P(c_void_p), P(c_void_p), P(c_void_p),
                                           P(c_size_t), c_int, c_int, P(SgdHyper), c_int, c_void_p]
     lib.kf_exchange_sgd_batch.restype = c_int
+    lib.kf_adam_update_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_void_p),
+                                         P(c_size_t), c_int, c_int, c_int, P(AdamHyper), c_void_p]
+    lib.kf_adam_update_batch.restype = c_int
+    lib.kf_exchange_adam_batch.argtypes = [c_void_p, P(c_void_p), P(c_void_p), P(c_void_p),
+                                           P(c_void_p), P(c_size_t), c_int, c_int, P(AdamHyper),
+                                           c_int, c_void_p]
+    lib.kf_exchange_adam_batch.restype = c_int
     _lib = lib
     # HIP resources go back while the runtime is alive, before the C exit
     # handlers run (include/kungfu_amd.h kf_shutdown)

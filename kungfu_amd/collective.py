@@ -65,6 +65,10 @@ class HipEpilogue:
         """The SGD update of the shards (ops.sgd_update_batch_), one launch."""
         return ops.sgd_update_batch_(params, grads, moms, hypers, np_)
 
+    def adam_update_(self, params, grads, exp_avgs, exp_avg_sqs, hypers, np_):
+        """The Adam / AdamW update of the shards (ops.adam_update_batch_), one launch."""
+        return ops.adam_update_batch_(params, grads, exp_avgs, exp_avg_sqs, hypers, np_)
+
 
 def coalesce_runs(buckets):
     """Maximal runs of buckets that are consecutive in one storage, each as
@@ -373,6 +377,63 @@ class Exchange:
         for np_, (ps, gs, ms, hs) in sets.items():
             if ps:
                 self.epilogue.sgd_update_(ps, gs, ms, hs, np_)
+        self._mark(marks, "epilogue")
+        gathers = []
+        for p in params:
+            q = p.numel() // self.world
+            gathers.append(dist.all_gather_into_tensor(p, p[self.rank * q:(self.rank + 1) * q],
+                                                       group=self.group, async_op=True))
+        for w in gathers:
+            w.wait()
+        self._mark(marks, "all_gather")
+        return params
+
+    def adam_step_(self, param_buckets, grad_buckets, exp_avg_shards, exp_avg_sq_shards, hypers):
+        """sgd_step_ with the Adam / AdamW update on this rank's shards (the
+        native exchange's kf_exchange_adam_batch, for this path): every
+        gradient bucket is reduce-scattered (or all-to-all'ed and folded in
+        rank order with the / world), epilogue.adam_update_ runs once over the
+        shards — parameters, summed gradients, both state shards — and every
+        parameter bucket is all-gathered in place. Both state shards of
+        bucket b hold numel // world elements. hypers[b] as
+        ops.adam_update_batch_ takes them. The gradient buckets are only read
+        here; callers must not rely on that."""
+        params, grads = list(param_buckets), list(grad_buckets)
+        ms, vs, hypers = list(exp_avg_shards), list(exp_avg_sq_shards), list(hypers)
+        if not (len(params) == len(grads) == len(ms) == len(vs) == len(hypers)):
+            raise ValueError("adam_step_: one grad bucket, two state shards and a hyper per bucket")
+        for p, g, m, v in zip(params, grads, ms, vs):
+            self._check(p)
+            self._check(g)
+            if g.numel() != p.numel() or g.dtype != p.dtype or \
+                    m.numel() * self.world != p.numel() or v.numel() != m.numel():
+                raise ValueError("adam_step_: bucket / shard sizes do not match")
+        if not params:
+            return params
+        if self.world == 1:
+            self.epilogue.adam_update_(params, grads, ms, vs, hypers, 1)
+            return params
+        marks = self._marks()
+        works = []
+        for i, g in enumerate(grads):
+            shard = self._workspace(("adam", "rs", i), g.numel() // self.world, g)
+            works.append((shard, self._scatter(g, shard, OP.SUM, ("adam", "a2a", i))))
+        # one update launch over all shards: the / world is the fold's where
+        # the shards were folded here, the update's own after a reduce-scatter
+        sets = {0: ([], [], [], [], []), self.world: ([], [], [], [], [])}
+        for _, (w, _) in works:
+            w.wait()
+        self._mark(marks, "reduce_scatter")
+        for p, m, v, h, (shard, (w, recv)) in zip(params, ms, vs, hypers, works):
+            if recv is not None:
+                self.epilogue.fold_(list(recv.chunk(self.world)), shard, OP.SUM, self.world)
+            q = shard.numel()
+            dst = sets[0 if recv is not None else self.world]
+            for lst, x in zip(dst, (p[self.rank * q:(self.rank + 1) * q], shard, m, v, h)):
+                lst.append(x)
+        for np_, (ps, gs, m_, v_, hs) in sets.items():
+            if ps:
+                self.epilogue.adam_update_(ps, gs, m_, v_, hs, np_)
         self._mark(marks, "epilogue")
         gathers = []
         for p in params:

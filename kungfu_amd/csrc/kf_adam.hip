@@ -1,0 +1,401 @@
+// kf_adam.hip — the Adam / AdamW update fused into the shard step of a
+// synchronous exchange (include/kungfu_amd.h kf_adam_update_batch, DESIGN.md
+// §14):
+//
+//   reduce-scatter(grads) -> [own shard: g/np, weight decay, m, v,
+//                             p -= step * m / (sqrt(v) / s2 + eps)] -> all-gather(params)
+//
+// One batched element-wise launch over up to kAdamSeg segments of one dtype,
+// kf_sgd.hip's shape with two state streams. Every segment has its own param /
+// grad / exp_avg / exp_avg_sq pointers, its count and its scalars, all in the
+// kernarg segment (lr and the bias corrections change every step). A segment
+// reads g, p, m and v once and writes p, m and v once: 7 accesses per element.
+//
+// Arithmetic: torch.optim.Adam / AdamW's single-tensor path with m as two
+// products and a sum (torch's lerp_ is one fused op), one IEEE operation per
+// parenthesis, no contraction (the pragma of kf_reduce_kernels.hpp and the
+// Makefile's -ffp-contract=off):
+//
+//   g = np > 0 ? sum / np : sum                (np a power of two: sum * 2^-k)
+//   wd != 0, decoupled == 0 (Adam, L2):  g = g + (wd*p)
+//   wd != 0, decoupled != 0 (AdamW):     p = dk*p              dk = 1 - lr*wd
+//   m = (b1*m) + (c1*g)                        c1 = 1 - beta1
+//   v = (b2*v) + (c2*(g*g))                    c2 = 1 - beta2
+//   d = (sqrt(v) / s2) + eps                   s2 = sqrt(bias_correction2)
+//   p = p + (nss*(m / d))                      nss = -(lr / bias_correction1)
+//
+// dk, c1, c2, s2 and nss are computed in double on the host and cast once to
+// the compute type; the bias corrections 1 - beta^t come from the caller (no
+// pow here or on the device). f32 / f64 round every operation in that type.
+// bf16 computes in fp32 and rounds to bf16 where torch's tensor ops do: after
+// the /np, after the L2 add or the decay multiply, after m (once), after
+// b2*v, after the v add, after the sqrt, after the / s2, after the + eps and
+// after the final add. The sqrt and both divisions are correctly rounded:
+// sqrtf (not __fsqrt_rn, which is a bare v_sqrt_f32 here), __fdiv_rn,
+// __dsqrt_rn, __ddiv_rn.
+//
+// f16 is refused: eps = 1e-8 rounds to 0 in f16, so every element with v == 0
+// (bucket padding, a parameter that never had a gradient) would be 0 / 0.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+
+#include "kf_sgd_elt.hpp"
+#include "kungfu_amd.h"
+
+// Load / store policy of the streams, 1 = non-temporal: kf_sgd.hip's measured
+// one. g is dead after this kernel; p, m and v are read and written in place.
+#ifndef KF_ADAM_G_NT
+#define KF_ADAM_G_NT 1
+#endif
+#ifndef KF_ADAM_PMV_NT
+#define KF_ADAM_PMV_NT 0
+#endif
+#ifndef KF_ADAM_ST_NT
+#define KF_ADAM_ST_NT 0
+#endif
+
+namespace kf
+{
+void set_last_error(const std::string &msg);  // kf_capi.hip: kf_last_error's text
+
+constexpr int kAdamSeg   = 24;
+constexpr int kAdamBlock = 256;
+#ifndef KF_ADAM_UNROLL
+#define KF_ADAM_UNROLL 4  // 16-B vectors per lane per stream per tile
+#endif
+constexpr int kAdamUnroll = KF_ADAM_UNROLL;
+
+enum { ADAM_NO_DECAY = 0, ADAM_L2 = 1, ADAM_DECOUPLED = 2 };
+
+// C: the compute type (float for f32 / bf16, double for f64). One segment's
+// entries sit together, as kf_sgd.hip's SgdSeg.
+template <typename C> struct AdamSeg {
+    void *p;
+    const void *g;
+    void *m, *v;
+    size_t n;
+    C w;  // ADAM_L2: weight_decay; ADAM_DECOUPLED: dk = 1 - lr*weight_decay
+    C b1, c1, b2, c2, s2, eps, nss;
+    int decay;
+};
+template <typename C> struct AdamBatchArgs {
+    AdamSeg<C> seg[kAdamSeg];
+    unsigned blk0[kAdamSeg + 1];  // the search table (1-D grids only)
+    int nseg;
+};
+// kf_sgd.hip's SgdBatchArgs budget: an entry is 112 bytes for f64, so 24 of them
+static_assert(sizeof(AdamBatchArgs<double>) + sizeof(Div) <= 3072, "kernarg budget");
+
+// Correctly rounded sqrt and division of the compute scalar or of a lane pair.
+__device__ __forceinline__ float adam_sqrt(float x) { return sqrtf(x); }
+__device__ __forceinline__ double adam_sqrt(double x) { return __dsqrt_rn(x); }
+__device__ __forceinline__ float adam_div(float a, float b) { return __fdiv_rn(a, b); }
+__device__ __forceinline__ double adam_div(double a, double b) { return __ddiv_rn(a, b); }
+__device__ __forceinline__ f32x2 adam_sqrt(f32x2 x) { return f32x2{sqrtf(x.x), sqrtf(x.y)}; }
+__device__ __forceinline__ f64x2 adam_sqrt(f64x2 x)
+{
+    return f64x2{__dsqrt_rn(x.x), __dsqrt_rn(x.y)};
+}
+__device__ __forceinline__ f32x2 adam_div(f32x2 a, float b)
+{
+    return f32x2{__fdiv_rn(a.x, b), __fdiv_rn(a.y, b)};
+}
+__device__ __forceinline__ f64x2 adam_div(f64x2 a, double b)
+{
+    return f64x2{__ddiv_rn(a.x, b), __ddiv_rn(a.y, b)};
+}
+__device__ __forceinline__ f32x2 adam_div(f32x2 a, f32x2 b)
+{
+    return f32x2{__fdiv_rn(a.x, b.x), __fdiv_rn(a.y, b.y)};
+}
+__device__ __forceinline__ f64x2 adam_div(f64x2 a, f64x2 b)
+{
+    return f64x2{__ddiv_rn(a.x, b.x), __ddiv_rn(a.y, b.y)};
+}
+
+// The update of H values (V = C) or of H lane pairs (V = X); g holds the
+// summed gradients on entry; h is the segment's kernarg entry, whose scalars
+// are wave-uniform. DECAY is the segment's choice, made once per block.
+template <typename T, int DIV, int DECAY, int H, typename V>
+__device__ __forceinline__ void adam_math(V (&p)[H], V (&g)[H], V (&m)[H], V (&v)[H],
+                                          const AdamSeg<typename SgdElt<T>::C> &h, const Div &d)
+{
+    using E = SgdElt<T>;
+#pragma unroll
+    for (int i = 0; i < H; ++i) g[i] = SgdDiv<T, DIV>::run(g[i], d);
+    if constexpr (DECAY == ADAM_L2) {
+#pragma unroll
+        for (int i = 0; i < H; ++i) g[i] = E::rnd(g[i] + h.w * p[i]);
+    } else if constexpr (DECAY == ADAM_DECOUPLED) {
+#pragma unroll
+        for (int i = 0; i < H; ++i) p[i] = E::rnd(h.w * p[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < H; ++i) {
+        const V t = h.b1 * m[i];
+        m[i]      = E::rnd(t + h.c1 * g[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < H; ++i) {
+        const V t = E::rnd(h.b2 * v[i]);
+        const V q = g[i] * g[i];
+        v[i]      = E::rnd(t + h.c2 * q);
+    }
+#pragma unroll
+    for (int i = 0; i < H; ++i) {
+        const V r = E::rnd(adam_sqrt(v[i]));
+        const V e = E::rnd(adam_div(r, h.s2));
+        const V f = E::rnd(e + h.eps);
+        const V u = adam_div(m[i], f);
+        p[i]      = E::rnd(p[i] + h.nss * u);
+    }
+}
+
+// one vector: p, m and v updated and stored
+template <typename T, int DIV, int DECAY>
+__device__ __forceinline__ void adam_vec(void *pp, void *pm, void *pv, size_t vi, const u32x4 &rp,
+                                         const u32x4 &rg, const u32x4 &rm, const u32x4 &rv,
+                                         const AdamSeg<typename SgdElt<T>::C> &h, const Div &d)
+{
+    using SV        = SgdVec<T>;
+    using X         = typename SV::X;
+    constexpr int H = SV::N / 2;
+    X p[H], g[H], m[H], v[H];
+    SV::unpack(rp, p);
+    SV::unpack(rg, g);
+    SV::unpack(rm, m);
+    SV::unpack(rv, v);
+    adam_math<T, DIV, DECAY, H, X>(p, g, m, v, h, d);
+    st_u4<KF_ADAM_ST_NT>(pp, vi, SV::pack(p));
+    st_u4<KF_ADAM_ST_NT>(pm, vi, SV::pack(m));
+    st_u4<KF_ADAM_ST_NT>(pv, vi, SV::pack(v));
+}
+
+// Block `blk` of `nblk` on one segment.
+template <typename T, int DIV, int DECAY>
+__device__ __forceinline__ void adam_body(const AdamSeg<typename SgdElt<T>::C> &h, const Div &d,
+                                          size_t blk, size_t nblk)
+{
+    using E         = SgdElt<T>;
+    using S         = typename E::S;
+    using C         = typename E::C;
+    constexpr int N = SgdVec<T>::N;
+    constexpr int U = kAdamUnroll, B = kAdamBlock;
+    void *pp = h.p, *pm = h.m, *pv = h.v;
+    const void *pg    = h.g;
+    const size_t n    = h.n;
+    const size_t nvec = n / N;
+
+    // the scalar tail: fewer than N elements, on the segment's first block
+    const size_t ti = nvec * N + threadIdx.x;
+    if (blk == 0 && ti < n) {
+        S *sp       = reinterpret_cast<S *>(pp);
+        const S *sq = reinterpret_cast<const S *>(pg);
+        S *sm       = reinterpret_cast<S *>(pm);
+        S *sv       = reinterpret_cast<S *>(pv);
+        C p[1] = {E::widen(sp[ti])}, g[1] = {E::widen(sq[ti])};
+        C m[1] = {E::widen(sm[ti])}, v[1] = {E::widen(sv[ti])};
+        adam_math<T, DIV, DECAY, 1, C>(p, g, m, v, h, d);
+        sp[ti] = E::narrow(p[0]);
+        sm[ti] = E::narrow(m[0]);
+        sv[ti] = E::narrow(v[0]);
+    }
+
+    const size_t tile   = static_cast<size_t>(B) * U;
+    const size_t ntiles = (nvec + tile - 1) / tile;
+    for (size_t t = blk; t < ntiles; t += nblk) {
+        const size_t v0 = t * tile + threadIdx.x;
+        if (v0 + (U - 1) * B < nvec) {
+            // full tile: every load issued before the first use
+            u32x4 rp[U], rg[U], rm[U], rv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) rg[u] = ld_u4<KF_ADAM_G_NT>(pg, v0 + u * B);
+#pragma unroll
+            for (int u = 0; u < U; ++u) rp[u] = ld_u4<KF_ADAM_PMV_NT>(pp, v0 + u * B);
+#pragma unroll
+            for (int u = 0; u < U; ++u) rm[u] = ld_u4<KF_ADAM_PMV_NT>(pm, v0 + u * B);
+#pragma unroll
+            for (int u = 0; u < U; ++u) rv[u] = ld_u4<KF_ADAM_PMV_NT>(pv, v0 + u * B);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                adam_vec<T, DIV, DECAY>(pp, pm, pv, v0 + u * B, rp[u], rg[u], rm[u], rv[u], h, d);
+            }
+        } else {
+            // ragged last tile
+            for (int u = 0; u < U; ++u) {
+                const size_t vi = v0 + u * B;
+                if (vi >= nvec) break;
+                const u32x4 rg = ld_u4<KF_ADAM_G_NT>(pg, vi), rp = ld_u4<KF_ADAM_PMV_NT>(pp, vi);
+                const u32x4 rm = ld_u4<KF_ADAM_PMV_NT>(pm, vi), rv = ld_u4<KF_ADAM_PMV_NT>(pv, vi);
+                adam_vec<T, DIV, DECAY>(pp, pm, pv, vi, rp, rg, rm, rv, h, d);
+            }
+        }
+    }
+}
+
+// The segment's decay, chosen once per block: a choice inside the update would
+// be made per vector, and in the scalar tail it kept p and g in scratch.
+template <typename T, int DIV>
+__device__ __forceinline__ void adam_seg(const AdamSeg<typename SgdElt<T>::C> &h, const Div &d,
+                                         size_t blk, size_t nblk)
+{
+    if (h.decay == ADAM_NO_DECAY) adam_body<T, DIV, ADAM_NO_DECAY>(h, d, blk, nblk);
+    else if (h.decay == ADAM_L2) adam_body<T, DIV, ADAM_L2>(h, d, blk, nblk);
+    else adam_body<T, DIV, ADAM_DECOUPLED>(h, d, blk, nblk);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kAdamBlock)
+    adam_update_kernel(AdamBatchArgs<typename SgdElt<T>::C> a, Div np, int div)
+{
+    using C = typename SgdElt<T>::C;
+    // kf_sgd.hip's two grids: segments of about equal size are the rows of a
+    // 2-D grid; otherwise the segment of block b is the last s with
+    // blk0[s] <= b, searched in the kernarg table.
+    const bool rows = gridDim.y > 1;
+    int s           = static_cast<int>(blockIdx.y);
+    size_t blk = blockIdx.x, nblk = gridDim.x;
+    if (!rows) {
+        const unsigned b = blockIdx.x;
+        int lo = 0, hi = a.nseg - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (b >= a.blk0[mid]) lo = mid;
+            else hi = mid - 1;
+        }
+        s    = lo;
+        blk  = b - a.blk0[s];
+        nblk = a.blk0[s + 1] - a.blk0[s];
+    }
+    const AdamSeg<C> &g = a.seg[s];
+    // the /np choice made once per kernel (kf_reduce_kernels.hpp EPI_MUL)
+    if (div == 0) adam_seg<T, 0>(g, np, blk, nblk);
+    else if (div == 1) adam_seg<T, 1>(g, np, blk, nblk);
+    else adam_seg<T, 2>(g, np, blk, nblk);
+}
+
+}  // namespace kf
+
+namespace
+{
+using namespace kf;
+
+int fail(int rc, const char *name, const std::string &what)
+{
+    set_last_error(std::string(name) + ": kf_adam_update_batch: " + what);
+    return rc;
+}
+
+template <typename T>
+int launch_adam(void *const *params, const void *const *grads, void *const *ms, void *const *vs,
+                const size_t *counts, int nb, int np, const kf_adam_hyper *hyper, hipStream_t s)
+{
+    using C         = typename SgdElt<T>::C;
+    constexpr int N = SgdVec<T>::N;
+    const Div dv    = update_div(np);
+    const int div   = np == 0 ? 0 : (dv.pow2 ? 1 : 2);
+    AdamBatchArgs<C> a;
+    a.nseg        = 0;
+    size_t blocks = 0, widest = 0;
+    auto flush    = [&]() -> int {
+        if (a.nseg == 0) return KF_OK;
+        a.blk0[a.nseg] = static_cast<unsigned>(blocks);
+        // one row per segment when that at most doubles the grid
+        const bool rows = a.nseg > 1 && widest * a.nseg <= 2 * blocks;
+        const dim3 grid = rows ? dim3(static_cast<unsigned>(widest), a.nseg)
+                               : dim3(static_cast<unsigned>(blocks));
+        adam_update_kernel<T><<<grid, kAdamBlock, 0, s>>>(a, dv, div);
+        a.nseg = 0;
+        blocks = widest = 0;
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            return fail(KF_ERR_HIP, "KF_ERR_HIP", std::string("launch: ") + hipGetErrorString(e));
+        }
+        return KF_OK;
+    };
+    const size_t tile = static_cast<size_t>(kAdamBlock) * kAdamUnroll;
+    for (int b = 0; b < nb; ++b) {
+        const size_t n = counts[b];
+        if (n == 0) continue;
+        size_t nblk = (n / N + tile - 1) / tile;  // one block per tile
+        if (nblk < 1) nblk = 1;                   // a tail alone
+        if (nblk > 0x400000u) nblk = 0x400000u;   // then blocks stride over the tiles
+        if (blocks + nblk > 0x7fffffu) {          // grid * block stays below 2^32 threads,
+            const int rc = flush();               // also as rows (at most twice the blocks)
+            if (rc != KF_OK) return rc;
+        }
+        const kf_adam_hyper &h = hyper[b];
+        AdamSeg<C> &g          = a.seg[a.nseg];
+        g.p                    = params[b];
+        g.g                    = grads[b];
+        g.m                    = ms[b];
+        g.v                    = vs[b];
+        g.n                    = n;
+        // computed in double, cast once to the compute type
+        g.decay = h.weight_decay == 0 ? ADAM_NO_DECAY : (h.decoupled ? ADAM_DECOUPLED : ADAM_L2);
+        g.w     = static_cast<C>(h.decoupled ? 1.0 - h.lr * h.weight_decay : h.weight_decay);
+        g.b1    = static_cast<C>(h.beta1);
+        g.c1    = static_cast<C>(1.0 - h.beta1);
+        g.b2    = static_cast<C>(h.beta2);
+        g.c2    = static_cast<C>(1.0 - h.beta2);
+        g.s2    = static_cast<C>(std::sqrt(h.bias_correction2));
+        g.eps   = static_cast<C>(h.eps);
+        g.nss   = static_cast<C>(-(h.lr / h.bias_correction1));
+        a.blk0[a.nseg] = static_cast<unsigned>(blocks);
+        blocks += nblk;
+        if (nblk > widest) widest = nblk;
+        if (++a.nseg == kAdamSeg) {
+            const int rc = flush();
+            if (rc != KF_OK) return rc;
+        }
+    }
+    return flush();
+}
+
+bool off16(const void *p) { return (reinterpret_cast<uintptr_t>(p) % 16) != 0; }
+
+}  // namespace
+
+extern "C" {
+
+int kf_adam_update_batch(void *const *params, const void *const *grads, void *const *exp_avgs,
+                         void *const *exp_avg_sqs, const size_t *counts, int nb,
+                         KungFu_Datatype dt, int np, const kf_adam_hyper *hyper, void *stream)
+{
+    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
+    if (nb == 0) return KF_OK;
+    if (!params || !grads || !exp_avgs || !exp_avg_sqs || !counts || !hyper) {
+        return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
+    }
+    if (dt != KungFu_FLOAT && dt != KungFu_DOUBLE && dt != KungFu_BFLOAT16) {
+        return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
+                    "f32, bf16 and f64 only (eps = 1e-8 is 0 in f16: 0 / 0 where v == 0)");
+    }
+    if (np < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "np < 0");
+    for (int b = 0; b < nb; ++b) {
+        if (counts[b] == 0) continue;
+        if (!params[b] || !grads[b] || !exp_avgs[b] || !exp_avg_sqs[b]) {
+            return fail(KF_ERR_ARG, "KF_ERR_ARG", "null pointer in a non-empty segment");
+        }
+        if (off16(params[b]) || off16(grads[b]) || off16(exp_avgs[b]) || off16(exp_avg_sqs[b])) {
+            return fail(KF_ERR_ARG, "KF_ERR_ARG", "pointers must be 16-byte aligned");
+        }
+        if (!(hyper[b].bias_correction1 > 0) || !(hyper[b].bias_correction2 > 0)) {
+            return fail(KF_ERR_ARG, "KF_ERR_ARG", "bias corrections must be > 0");
+        }
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dt) {
+    case KungFu_FLOAT:
+        return launch_adam<float>(params, grads, exp_avgs, exp_avg_sqs, counts, nb, np, hyper, s);
+    case KungFu_DOUBLE:
+        return launch_adam<double>(params, grads, exp_avgs, exp_avg_sqs, counts, nb, np, hyper, s);
+    default:
+        return launch_adam<bf16_t>(params, grads, exp_avgs, exp_avg_sqs, counts, nb, np, hyper, s);
+    }
+}
+
+}  // extern "C"

@@ -345,11 +345,27 @@ struct NamedTask {
     void *arg        = nullptr;
 };
 
-// kf_exchange_sgd_batch's tables (one entry per bucket)
-struct SgdStep {
+// The optimizer update on the shards (kf_exchange_sgd_batch,
+// kf_exchange_adam_batch): the tables, one entry per bucket, and the batched
+// kernel that takes them. Exactly one of sgd / adam is set.
+struct ShardUpdate {
     void *const *params;
-    void *const *moms;  // this rank's momentum shards
-    const kf_sgd_hyper *hyper;
+    void *const *state;   // this rank's momentum (SGD) or exp_avg (Adam) shards
+    void *const *state2;  // Adam: this rank's exp_avg_sq shards
+    const kf_sgd_hyper *sgd;
+    const kf_adam_hyper *adam;
+
+    const char *kernel() const { return sgd ? "kf_sgd_update_batch" : "kf_adam_update_batch"; }
+    // buckets b0 .. b0 + n - 1: ps / gs are the shards (or the whole buckets)
+    int run(void *const *ps, const void *const *gs, const size_t *cnts, int b0, int n,
+            KungFu_Datatype dt, int np, hipStream_t s) const
+    {
+        if (sgd) {
+            return kf_sgd_update_batch(ps, gs, state ? state + b0 : nullptr, cnts, n, dt, np,
+                                       sgd + b0, s);
+        }
+        return kf_adam_update_batch(ps, gs, state + b0, state2 + b0, cnts, n, dt, np, adam + b0, s);
+    }
 };
 
 struct kf_exchange {
@@ -435,12 +451,14 @@ struct kf_exchange {
     // each variable blended once its sum is gathered
     // phases: which of the three to run (kAll; the hierarchical all-reduce
     // runs 1+2, its cross-host step, then 3)
-    // sgd != nullptr: the sharded SGD step (kf_exchange_sgd_batch), sends ==
-    // recvs = the gradient buckets, average set; the update runs on the
-    // shards in phase 2 and phase 3 gathers the parameter buckets
+    // upd != nullptr: the sharded optimizer step (kf_exchange_sgd_batch,
+    // kf_exchange_adam_batch), sends == recvs = the gradient buckets, average
+    // set; the update runs on the shards in phase 2 and phase 3 gathers the
+    // parameter buckets
     int batch(const void *const *sends, void *const *recvs, const size_t *counts, int nb,
               KungFu_Datatype dt, KungFu_Op op, int average, int algo, hipStream_t s,
-              const double *sma_alpha = nullptr, int phases = 7, const SgdStep *sgd = nullptr);
+              const double *sma_alpha = nullptr, int phases = 7,
+              const ShardUpdate *upd = nullptr);
     int hier(kf_session_t *cross, const void *send, void *recv, size_t count, KungFu_Datatype dt,
              KungFu_Op op, int average, int algo, const std::string &name, hipStream_t s);
     kf_exchange *split(int color, int key, int *status);  // caller holds mu
@@ -533,15 +551,14 @@ static int resolve_algo(int algo, KungFu_Datatype dt, KungFu_Op op, int world, i
 
 int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_t *counts,
                        int nb, KungFu_Datatype dt, KungFu_Op op, int average, int algo,
-                       hipStream_t s, const double *sma_alpha, int phases, const SgdStep *sgd)
+                       hipStream_t s, const double *sma_alpha, int phases, const ShardUpdate *upd)
 {
     const int sz = tsize(dt);
     const int W = world, r = rank;
     const bool sma = sma_alpha != nullptr;
-    if (W == 1 && builtin && sgd) {  // a single peer: the update over the whole buckets
-        const int rc = kf_sgd_update_batch(sgd->params, sends, sgd->moms, counts, nb, dt, 1,
-                                           sgd->hyper, s);
-        if (rc != KF_OK) return fail(rc, std::string("kf_sgd_update_batch: ") + kf_last_error());
+    if (W == 1 && builtin && upd) {  // a single peer: the update over the whole buckets
+        const int rc = upd->run(upd->params, sends, counts, 0, nb, dt, 1, s);
+        if (rc != KF_OK) return fail(rc, std::string(upd->kernel()) + ": " + kf_last_error());
         return KF_OK;
     }
     if (W == 1 && builtin) {  // a single peer: the sum is the bucket, x / 1 == x
@@ -622,7 +639,7 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
         std::vector<const void *> ins;
         std::vector<void *> outs;
         std::vector<size_t> cnts;
-        if (a == KF_ALGO_REDUCE_SCATTER && average && !sgd) {
+        if (a == KF_ALGO_REDUCE_SCATTER && average && !upd) {
             for (int b = b0; b < b1; ++b) {
                 const size_t q = counts[b] / W;
                 if (!q) continue;
@@ -661,25 +678,23 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
                                                  average ? W : 0, cs);
             if (e != KF_OK) return fail(e, "rank-order fold of the received shards");
         }
-        if (sgd) {
+        if (upd) {
             // the update on this rank's shard of every bucket; after a plain
             // reduce-scatter the shard holds the sum and the kernel divides
             // (the shard is read once, no /np pass); the fold and ncclAvg
             // have divided already
-            std::vector<void *> ps, ms;
+            std::vector<void *> ps;
             std::vector<const void *> gs;
             cnts.clear();
             for (int b = b0; b < b1; ++b) {
                 const size_t q = counts[b] / W;
-                ps.push_back(static_cast<char *>(sgd->params[b]) + r * q * sz);
+                ps.push_back(static_cast<char *>(upd->params[b]) + r * q * sz);
                 gs.push_back(static_cast<const char *>(recvs[b]) + r * q * sz);
-                ms.push_back(sgd->moms ? sgd->moms[b] : nullptr);
                 cnts.push_back(q);
             }
-            const int e = kf_sgd_update_batch(ps.data(), gs.data(), ms.data(), cnts.data(), b1 - b0,
-                                              dt, a == KF_ALGO_REDUCE_SCATTER ? W : 0,
-                                              sgd->hyper + b0, cs);
-            if (e != KF_OK) return fail(e, std::string("kf_sgd_update_batch: ") + kf_last_error());
+            const int e = upd->run(ps.data(), gs.data(), cnts.data(), b0, b1 - b0, dt,
+                                   a == KF_ALGO_REDUCE_SCATTER ? W : 0, cs);
+            if (e != KF_OK) return fail(e, std::string(upd->kernel()) + ": " + kf_last_error());
         }
         return KF_OK;
     };
@@ -692,7 +707,7 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
         for (int b = b0; b < b1 && rc3 == KF_OK; ++b) {
             const size_t q = counts[b] / W;
             if (!q) continue;
-            char *rcv   = static_cast<char *>(sgd ? sgd->params[b] : recvs[b]);
+            char *rcv   = static_cast<char *>(upd ? upd->params[b] : recvs[b]);
             const int e = T->all_gather(rcv + r * q * sz, rcv, q * sz, comm, s);
             if (e != 0) rc3 = tfail(e, "all_gather");
         }
@@ -711,7 +726,7 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
         return KF_OK;
     };
 
-    const int G = phases == 7 && !sgd ? std::min(groups, nb) : 1;
+    const int G = phases == 7 && !upd ? std::min(groups, nb) : 1;
     if (G <= 1) {
         Marks *mk = timing ? take_marks() : nullptr;
         auto mark = [&](int k) {
@@ -1668,7 +1683,51 @@ int kf_exchange_sgd_batch(kf_exchange_t *ex, void *const *params, void *const *g
     }
     DeviceGuard g(ex->device);
     std::lock_guard<std::mutex> lk(ex->mu);
-    const SgdStep step{params, mom_shards, hyper};
+    const ShardUpdate step{params, mom_shards, nullptr, hyper, nullptr};
+    return ex->batch(grads, grads, counts, nb, dt, KungFu_SUM, 1, algo,
+                     static_cast<hipStream_t>(stream), nullptr, 7, &step);
+}
+
+int kf_exchange_adam_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
+                           void *const *exp_avg_shards, void *const *exp_avg_sq_shards,
+                           const size_t *counts, int nb, KungFu_Datatype dt,
+                           const kf_adam_hyper *hyper, int algo, void *stream)
+{
+    if (!ex || nb < 0) return fail(KF_ERR_ARG, "kf_exchange_adam_batch: bad arguments");
+    if (dt != KungFu_FLOAT && dt != KungFu_DOUBLE && dt != KungFu_BFLOAT16) {
+        return fail(KF_ERR_DTYPE, "kf_exchange_adam_batch: f32, bf16 and f64 only");
+    }
+    if (nb == 0) return KF_OK;
+    if (!params || !grads || !exp_avg_shards || !exp_avg_sq_shards || !counts || !hyper) {
+        return fail(KF_ERR_ARG, "kf_exchange_adam_batch: null table");
+    }
+    if (algo < KF_ALGO_AUTO || algo > KF_ALGO_REDUCE_SCATTER_AVG) return fail(KF_ERR_ARG, "unknown algo");
+    // every rank must reach the same verdict before any collective is queued
+    const size_t W = static_cast<size_t>(ex->world), sz = static_cast<size_t>(tsize(dt));
+    auto off16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) % 16) != 0; };
+    for (int b = 0; b < nb; ++b) {
+        if (counts[b] == 0) continue;
+        if (!params[b] || !grads[b]) return fail(KF_ERR_ARG, "kf_exchange_adam_batch: null bucket");
+        if (counts[b] % W) {
+            return fail(KF_ERR_ARG, "kf_exchange_adam_batch: counts must be multiples of the world "
+                                    "(padded buckets, no tails)");
+        }
+        if (!exp_avg_shards[b] || !exp_avg_sq_shards[b]) {
+            return fail(KF_ERR_ARG, "kf_exchange_adam_batch: every non-empty bucket needs both "
+                                    "state shards");
+        }
+        if (off16(params[b]) || off16(grads[b]) || off16(exp_avg_shards[b]) ||
+            off16(exp_avg_sq_shards[b]) || (W > 1 && (counts[b] / W * sz) % 16)) {
+            return fail(KF_ERR_ARG, "kf_exchange_adam_batch: buckets and their shards must start "
+                                    "16-byte aligned");
+        }
+        if (!(hyper[b].bias_correction1 > 0) || !(hyper[b].bias_correction2 > 0)) {
+            return fail(KF_ERR_ARG, "kf_exchange_adam_batch: bias corrections must be > 0");
+        }
+    }
+    DeviceGuard g(ex->device);
+    std::lock_guard<std::mutex> lk(ex->mu);
+    const ShardUpdate step{params, exp_avg_shards, exp_avg_sq_shards, nullptr, hyper};
     return ex->batch(grads, grads, counts, nb, dt, KungFu_SUM, 1, algo,
                      static_cast<hipStream_t>(stream), nullptr, 7, &step);
 }

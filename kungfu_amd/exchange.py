@@ -279,6 +279,37 @@ class NativeExchange:
         _lib.check(rc, "kf_exchange_sgd_batch")
         return params
 
+    def adam_step_(self, param_buckets, grad_buckets, exp_avg_shards, exp_avg_sq_shards, hypers):
+        """sgd_step_ with the Adam / AdamW update on this rank's shards
+        (kf_exchange_adam_batch): reduce-scatter of the gradient buckets,
+        ops.adam_update_batch_'s kernel on the shard of every bucket (the
+        / world inside it), in-place all-gather of the parameter buckets.
+        Queued on the current stream. Both state shards of bucket b hold
+        numel // world elements of the parameters' dtype (f32, bf16 or f64).
+        The gradient buckets are scratch: they hold nothing defined
+        afterwards."""
+        params, grads = list(param_buckets), list(grad_buckets)
+        ms, vs, hypers = list(exp_avg_shards), list(exp_avg_sq_shards), list(hypers)
+        if not (len(params) == len(grads) == len(ms) == len(vs) == len(hypers)):
+            raise ValueError("adam_step_: one grad bucket, two state shards and a hyper per bucket")
+        if not params:
+            return params
+        self._check(params + grads + ms + vs)
+        for p, g, m, v in zip(params, grads, ms, vs):
+            if g.numel() != p.numel() or m.numel() * self.world != p.numel() or \
+                    v.numel() != m.numel():
+                raise ValueError("adam_step_: bucket / shard sizes do not match")
+        rc = self.lib.kf_exchange_adam_batch(
+            self._h, _lib.ptr_array([p.data_ptr() for p in params]),
+            _lib.ptr_array([g.data_ptr() for g in grads]),
+            _lib.ptr_array([m.data_ptr() for m in ms]),
+            _lib.ptr_array([v.data_ptr() for v in vs]),
+            _arr(ctypes.c_size_t, [p.numel() for p in params]), len(params),
+            int(kungfu_dtype(params[0])), _lib.adam_hyper_array(hypers), ALGOS[self.algo],
+            torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(rc, "kf_exchange_adam_batch")
+        return params
+
     def all_reduce_named(self, name, buf, op="sum", average=False, stream=None, callback=None):
         """kf_exchange_all_reduce_named: in place, paired with the peers' calls
         of the same name whatever order each rank starts its names in

@@ -214,6 +214,42 @@ def sgd_update_batch_(params, grads, moms, hypers, np_=0, stream=None):
     return params
 
 
+def adam_update_batch_(params, grads, exp_avgs, exp_avg_sqs, hypers, np_=0, stream=None):
+    """The Adam / AdamW update of many flat segments of one dtype (f32, bf16
+    or f64) in one launch per 24 of them (kf_adam_update_batch,
+    kungfu_amd/csrc/kf_adam.hip), in place on params and both states:
+
+      g = grads[b] / np_ (np_ > 0) ; L2: g += wd * p ; decoupled: p *= 1 - lr * wd
+      m = b1 * m + (1 - b1) * g ; v = b2 * v + (1 - b2) * g * g
+      p -= lr / (1 - b1**step) * m / (sqrt(v) / sqrt(1 - b2**step) + eps)
+
+    rounded as include/kungfu_amd.h states. hypers[b] is a dict with lr,
+    step (>= 1) and optionally betas, eps, weight_decay, decoupled. Every
+    tensor starts 16-byte aligned. grads are only read."""
+    params, grads, hypers = list(params), list(grads), list(hypers)
+    ms, vs = list(exp_avgs), list(exp_avg_sqs)
+    if not (len(params) == len(grads) == len(ms) == len(vs) == len(hypers)):
+        raise ValueError("adam_update_batch_: one grad, exp_avg, exp_avg_sq and hyper "
+                         "per param segment")
+    if not params:
+        return params
+    _check_dev(params + grads + ms + vs)
+    for p, g, m, v in zip(params, grads, ms, vs):
+        if p.dtype != params[0].dtype or \
+                any(x.numel() != p.numel() or x.dtype != p.dtype for x in (g, m, v)):
+            raise ValueError("adam_update_batch_: shape/dtype mismatch")
+    lib = _lib.load()
+    cnt = (ctypes.c_size_t * len(params))(*[p.numel() for p in params])
+    rc = lib.kf_adam_update_batch(_lib.ptr_array([p.data_ptr() for p in params]),
+                                  _lib.ptr_array([g.data_ptr() for g in grads]),
+                                  _lib.ptr_array([m.data_ptr() for m in ms]),
+                                  _lib.ptr_array([v.data_ptr() for v in vs]),
+                                  cnt, len(params), int(kungfu_dtype(params[0])), int(np_),
+                                  _lib.adam_hyper_array(hypers), _stream(stream, params[0].device))
+    _lib.check(rc, "kf_adam_update_batch", source="")
+    return params
+
+
 _NORM_DTYPES = (torch.float32, torch.float16, torch.bfloat16, torch.float64)
 
 

@@ -26,6 +26,8 @@ Operator surface kept from the reference:
   the SGD update itself moved onto each rank's shard, between the gradients'
   reduce-scatter and an all-gather of the parameters; the momentum state is
   sharded over the ranks. The package's own (the reference has none).
+* ``ShardedAdamOptimizer(optimizer, named_parameters=None, ...)`` — the same
+  for torch.optim.Adam / AdamW: exp_avg and exp_avg_sq sharded over the ranks.
 
 Buckets: parameters are grouped (in registration order, per dtype/device) into
 flat padded device buckets (``collective.GradBuckets``); ``p.grad`` (S-SGD) or
@@ -655,10 +657,19 @@ def PairAveragingOptimizer(optimizer, named_parameters=None, bucket_bytes=32 << 
     return opt
 
 
-class _ShardedSGD(_Bucketed):
-    """reduce-scatter(grads) -> SGD update on the own shard -> all-gather(params).
-    Parameters and gradients live in two GradBuckets of identical layout per
-    (param group, dtype, device); the momentum is one shard per bucket."""
+class _Sharded(_Bucketed):
+    """What the sharded optimizers share. Parameters and gradients live in
+    two GradBuckets of identical layout per (param group, dtype, device); the
+    optimizer state is one shard (1 / world of the elements) per bucket and
+    state tensor."""
+
+    _kf_name = ""          # the public constructor, for messages
+    _kf_dtypes = ()        # torch dtype names the update kernel takes
+    _kf_dtype_words = ""
+
+    def _kf_new_group(self):
+        """The state entries of a new bucket group."""
+        return {}
 
     def _kf_build_sharded(self):
         import torch
@@ -670,9 +681,9 @@ class _ShardedSGD(_Bucketed):
                 if id(p) in mine:
                     by.setdefault((p.dtype, p.device), []).append(p)
             for (dtype, device), ps in by.items():
-                if dtype not in (torch.float32, torch.float16, torch.bfloat16, torch.float64):
-                    raise TypeError("ShardedSGDOptimizer updates f32, f16, bf16 and f64 "
-                                    "parameters, not %s" % dtype)
+                if dtype not in tuple(getattr(torch, n) for n in self._kf_dtypes):
+                    raise TypeError("%s updates %s parameters, not %s"
+                                    % (self._kf_name, self._kf_dtype_words, dtype))
                 numels = [p.numel() for p in ps]
                 pb = GradBuckets(numels, dtype, device, self._kf_ex.world,
                                  bucket_bytes=self._kf_bucket_bytes)
@@ -682,42 +693,23 @@ class _ShardedSGD(_Bucketed):
                     v = view.view_as(p)
                     v.copy_(p.data)
                     p.data = v
-                self._kf_groups.append({"gi": gi, "ps": ps, "pb": pb, "gb": gb, "moms": None,
-                                        "first": True})
+                G = {"gi": gi, "ps": ps, "pb": pb, "gb": gb}
+                G.update(self._kf_new_group())
+                self._kf_groups.append(G)
 
-    def _kf_moms(self, G):
-        """The group's zeroed momentum shards, allocated when first needed."""
-        if G["moms"] is None:
-            import torch
-            world = self._kf_ex.world
-            G["moms"] = [torch.zeros(b.numel() // world, dtype=b.dtype, device=b.device)
-                         for b in G["pb"].buckets]
-            G["first"] = True
-        return G["moms"]
+    def _kf_zero_shards(self, G):
+        """One zeroed state shard per bucket of the group."""
+        import torch
+        world = self._kf_ex.world
+        return [torch.zeros(b.numel() // world, dtype=b.dtype, device=b.device)
+                for b in G["pb"].buckets]
 
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            import torch
-            with torch.enable_grad():
-                loss = closure()
-        if self._kf_groups is None:
-            self._kf_build_sharded()
-        for G in self._kf_groups:
-            _SyncSGD._kf_place(G["ps"], G["gb"])
-        for G in self._kf_groups:
-            pg = self.param_groups[G["gi"]]  # read at every step: schedulers change them
-            mu = float(pg["momentum"])
-            moms = self._kf_moms(G) if mu != 0 else None
-            h = {"lr": float(pg["lr"]), "momentum": mu, "dampening": float(pg["dampening"]),
-                 "weight_decay": float(pg["weight_decay"]), "nesterov": bool(pg["nesterov"]),
-                 "first": G["first"]}
-            nb = len(G["pb"].buckets)
-            self._kf_ex.sgd_step_(G["pb"].buckets, G["gb"].buckets, moms, [h] * nb)
-            if mu != 0:
-                G["first"] = False
-        _finish(self._kf_ex)
-        return loss
+    def _kf_closure(self, closure):
+        if closure is None:
+            return None
+        import torch
+        with torch.enable_grad():
+            return closure()
 
     def _kf_gather(self, shard):
         """All ranks' shards of one bucket, in rank order. The shards travel
@@ -740,6 +732,78 @@ class _ShardedSGD(_Bucketed):
         ex.all_reduce_([full.view(ints)], op="sum", average=False)
         return full
 
+    def _kf_unshard(self, G, shards):
+        """Collective: {parameter: its full state tensor} of one group, from
+        the ranks' shards of one state (a new tensor each)."""
+        out = {}
+        off = {}
+        for p, v in zip(G["ps"], G["pb"].views):
+            off[id(p)] = v.data_ptr()
+        for b, m in zip(G["pb"].buckets, shards):
+            full = self._kf_gather(m)
+            lo, hi = b.data_ptr(), b.data_ptr() + b.numel() * b.element_size()
+            for p in G["ps"]:
+                at = off[id(p)]
+                if lo <= at < hi and p.numel():
+                    i = (at - lo) // b.element_size()
+                    out[p] = full[i:i + p.numel()].view_as(p).clone()
+        return out
+
+    def _kf_reshard(self, G, shards, tensor_of):
+        """This rank's slice of every bucket of one state into `shards`:
+        tensor_of(p) is the parameter's full state tensor, or None (zeros)."""
+        import torch
+        ex = self._kf_ex
+        for b, m in zip(G["pb"].buckets, shards):
+            full = torch.zeros_like(b)
+            lo, hi = b.data_ptr(), b.data_ptr() + b.numel() * b.element_size()
+            for p, v in zip(G["ps"], G["pb"].views):
+                t = tensor_of(p) if lo <= v.data_ptr() < hi and p.numel() else None
+                if t is not None:
+                    i = (v.data_ptr() - lo) // b.element_size()
+                    full[i:i + p.numel()].copy_(t.reshape(-1))
+            q = m.numel()
+            m.copy_(full[ex.rank * q:(ex.rank + 1) * q])
+
+
+class _ShardedSGD(_Sharded):
+    """reduce-scatter(grads) -> SGD update on the own shard -> all-gather(params).
+    The momentum is one shard per bucket."""
+
+    _kf_name = "ShardedSGDOptimizer"
+    _kf_dtypes = ("float32", "float16", "bfloat16", "float64")
+    _kf_dtype_words = "f32, f16, bf16 and f64"
+
+    def _kf_new_group(self):
+        return {"moms": None, "first": True}
+
+    def _kf_moms(self, G):
+        """The group's zeroed momentum shards, allocated when first needed."""
+        if G["moms"] is None:
+            G["moms"] = self._kf_zero_shards(G)
+            G["first"] = True
+        return G["moms"]
+
+    def step(self, closure=None):
+        loss = self._kf_closure(closure)
+        if self._kf_groups is None:
+            self._kf_build_sharded()
+        for G in self._kf_groups:
+            _SyncSGD._kf_place(G["ps"], G["gb"])
+        for G in self._kf_groups:
+            pg = self.param_groups[G["gi"]]  # read at every step: schedulers change them
+            mu = float(pg["momentum"])
+            moms = self._kf_moms(G) if mu != 0 else None
+            h = {"lr": float(pg["lr"]), "momentum": mu, "dampening": float(pg["dampening"]),
+                 "weight_decay": float(pg["weight_decay"]), "nesterov": bool(pg["nesterov"]),
+                 "first": G["first"]}
+            nb = len(G["pb"].buckets)
+            self._kf_ex.sgd_step_(G["pb"].buckets, G["gb"].buckets, moms, [h] * nb)
+            if mu != 0:
+                G["first"] = False
+        _finish(self._kf_ex)
+        return loss
+
     def momentum_buffers(self):
         """Collective: {parameter: its full momentum buffer}, gathered from
         the ranks' shards (a new tensor each; empty for a group that has not
@@ -750,17 +814,7 @@ class _ShardedSGD(_Bucketed):
         for G in self._kf_groups or []:
             if G["moms"] is None or G["first"]:
                 continue
-            off = {}
-            for p, v in zip(G["ps"], G["pb"].views):
-                off[id(p)] = v.data_ptr()
-            for b, m in zip(G["pb"].buckets, G["moms"]):
-                full = self._kf_gather(m)
-                lo, hi = b.data_ptr(), b.data_ptr() + b.numel() * b.element_size()
-                for p in G["ps"]:
-                    at = off[id(p)]
-                    if lo <= at < hi and p.numel():
-                        i = (at - lo) // b.element_size()
-                        out[p] = full[i:i + p.numel()].view_as(p).clone()
+            out.update(self._kf_unshard(G, G["moms"]))
         _finish(self._kf_ex)
         return out
 
@@ -770,24 +824,89 @@ class _ShardedSGD(_Bucketed):
         next step is no longer a group's first. A group none of whose
         parameters is in `mapping` is left as it is; a parameter missing from
         a loaded group gets zeros."""
-        import torch
         if self._kf_groups is None:
             self._kf_build_sharded()
-        ex = self._kf_ex
         for G in self._kf_groups:
             if not any(p in mapping for p in G["ps"]):
                 continue
-            moms = self._kf_moms(G)
-            for b, m in zip(G["pb"].buckets, moms):
-                full = torch.zeros_like(b)
-                lo, hi = b.data_ptr(), b.data_ptr() + b.numel() * b.element_size()
-                for p, v in zip(G["ps"], G["pb"].views):
-                    if lo <= v.data_ptr() < hi and p.numel() and p in mapping:
-                        i = (v.data_ptr() - lo) // b.element_size()
-                        full[i:i + p.numel()].copy_(mapping[p].reshape(-1))
-                q = m.numel()
-                m.copy_(full[ex.rank * q:(ex.rank + 1) * q])
+            self._kf_reshard(G, self._kf_moms(G), mapping.get)
             G["first"] = False
+
+
+class _ShardedAdam(_Sharded):
+    """reduce-scatter(grads) -> Adam / AdamW update on the own shard ->
+    all-gather(params). exp_avg and exp_avg_sq are one shard each per bucket;
+    one step counter per bucket group."""
+
+    _kf_name = "ShardedAdamOptimizer"
+    _kf_dtypes = ("float32", "bfloat16", "float64")
+    _kf_dtype_words = "f32, bf16 and f64"
+    _kf_decoupled = False
+
+    def _kf_new_group(self):
+        return {"m": None, "v": None, "step": 0}
+
+    def _kf_states(self, G):
+        """The group's zeroed exp_avg / exp_avg_sq shards, allocated on the
+        first step."""
+        if G["m"] is None:
+            G["m"], G["v"] = self._kf_zero_shards(G), self._kf_zero_shards(G)
+        return G["m"], G["v"]
+
+    def step(self, closure=None):
+        loss = self._kf_closure(closure)
+        if self._kf_groups is None:
+            self._kf_build_sharded()
+        for G in self._kf_groups:
+            _SyncSGD._kf_place(G["ps"], G["gb"])
+        for G in self._kf_groups:
+            pg = self.param_groups[G["gi"]]  # read at every step: schedulers change them
+            ms, vs = self._kf_states(G)
+            G["step"] += 1
+            h = {"lr": float(pg["lr"]), "betas": tuple(float(b) for b in pg["betas"]),
+                 "eps": float(pg["eps"]), "weight_decay": float(pg["weight_decay"]),
+                 "decoupled": self._kf_decoupled, "step": G["step"]}
+            nb = len(G["pb"].buckets)
+            self._kf_ex.adam_step_(G["pb"].buckets, G["gb"].buckets, ms, vs, [h] * nb)
+        _finish(self._kf_ex)
+        return loss
+
+    def state_buffers(self):
+        """Collective: {parameter: {"step": int, "exp_avg": tensor,
+        "exp_avg_sq": tensor}}, the full state tensors gathered from the
+        ranks' shards (new tensors; empty for a group that has not stepped).
+        With load_state_buffers, the checkpoint path: `state` stays empty, so
+        state_dict() carries no Adam state."""
+        out = {}
+        for G in self._kf_groups or []:
+            if G["m"] is None or G["step"] == 0:
+                continue
+            m, v = self._kf_unshard(G, G["m"]), self._kf_unshard(G, G["v"])
+            for p in m:
+                out[p] = {"step": G["step"], "exp_avg": m[p], "exp_avg_sq": v[p]}
+        _finish(self._kf_ex)
+        return out
+
+    def load_state_buffers(self, mapping):
+        """{parameter: {"step", "exp_avg", "exp_avg_sq"}} (state_buffers'
+        result, on every rank): each rank keeps its own slice of every
+        bucket, and the group goes on from `step`. A group none of whose
+        parameters is in `mapping` is left as it is; a parameter missing from
+        a loaded group gets zeros. The parameters of one group must agree on
+        `step` (ValueError otherwise)."""
+        if self._kf_groups is None:
+            self._kf_build_sharded()
+        for G in self._kf_groups:
+            steps = {int(mapping[p]["step"]) for p in G["ps"] if p in mapping}
+            if not steps:
+                continue
+            if len(steps) > 1:
+                raise ValueError("load_state_buffers: the parameters of one group differ in "
+                                 "step: %s" % sorted(steps))
+            ms, vs = self._kf_states(G)
+            self._kf_reshard(G, ms, lambda p: mapping[p]["exp_avg"] if p in mapping else None)
+            self._kf_reshard(G, vs, lambda p: mapping[p]["exp_avg_sq"] if p in mapping else None)
+            G["step"] = steps.pop()
 
 
 def ShardedSGDOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20):
@@ -833,5 +952,66 @@ def ShardedSGDOptimizer(optimizer, named_parameters=None, exchange=None, bucket_
     opt._kf_setup(named_parameters, exchange, bucket_bytes)
     if not hasattr(opt._kf_ex, "sgd_step_"):
         raise ValueError("ShardedSGDOptimizer needs an exchange with sgd_step_() "
+                         "(collective.Exchange or exchange.NativeExchange)")
+    return opt
+
+
+def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20):
+    """Synchronous Adam / AdamW with the optimizer update and its state
+    sharded over the ranks, as ShardedSGDOptimizer does for SGD: every step is
+
+      reduce-scatter(grads) -> [own shard: g / np, weight decay, exp_avg,
+                                exp_avg_sq, p -= step_size * m / denom] -> all-gather(params)
+
+    in one call of the exchange's `adam_step_` per (param group, dtype): the
+    same xGMI bytes as S-SGD's gradient all-reduce, the update over 1 / np of
+    the model per rank in one batched HIP launch (ops.adam_update_batch_),
+    and exp_avg / exp_avg_sq of 1 / np of the model each per rank. The
+    arithmetic source is torch.optim.Adam / AdamW's single-tensor path
+    (foreach=False) on the averaged gradient, rounded as include/kungfu_amd.h
+    kf_adam_update_batch states.
+
+    `optimizer` must be a torch.optim.Adam or torch.optim.AdamW (TypeError
+    otherwise); an AdamW decays the weights decoupled (p *= 1 - lr * wd), an
+    Adam adds wd * p to the gradient. It only lends its class and its
+    param_groups: its own step() is never called and `state` stays empty. lr,
+    betas, eps and weight_decay are read from param_groups at every step, so
+    LR schedulers work. Every (param group, dtype) bucket group counts its
+    own steps from 1; the bias corrections 1 - beta ** step are taken in
+    Python doubles.
+
+    Differences from torch.optim.Adam / AdamW:
+      * a parameter without a gradient is updated as with a zero gradient
+        (its state decays, and AdamW's decay still applies); torch skips it;
+      * after step(), p.grad does not hold the averaged gradient: the
+        gradient buckets are scratch of the exchange;
+      * exp_avg is b1*m + (1 - b1)*g, two products and a sum, not torch's
+        lerp: the results differ from torch's in the last bits;
+      * no f16 parameters (TypeError on the first step): eps = 1e-8 rounds
+        to 0 in f16, so every element with exp_avg_sq == 0 would be 0 / 0.
+        The state has the parameters' dtype (f32, bf16 or f64).
+
+    state_buffers() (collective) and load_state_buffers(mapping) are the
+    checkpoint path for the sharded state.
+
+    Not offered: overlap=True, the hierarchical (multi-host) path, amsgrad,
+    maximize, differentiable, and any optimizer other than Adam / AdamW."""
+    import torch
+    if isinstance(optimizer, torch.optim.AdamW):  # first: newer torch derives it from Adam
+        decoupled = True
+    elif isinstance(optimizer, torch.optim.Adam):
+        decoupled = False
+    else:
+        raise TypeError("ShardedAdamOptimizer wraps a torch.optim.Adam or AdamW, not %s"
+                        % type(optimizer).__name__)
+    for g in optimizer.param_groups:
+        for option in ("amsgrad", "maximize", "differentiable"):
+            if g.get(option, False):
+                raise ValueError("ShardedAdamOptimizer: %s=True is not supported" % option)
+    opt = _wrap(optimizer, _ShardedAdam)
+    opt._kf_decoupled = decoupled
+    opt._kf_setup(named_parameters, exchange, bucket_bytes)
+    if not hasattr(opt._kf_ex, "adam_step_"):
+        raise ValueError("ShardedAdamOptimizer needs an exchange with adam_step_() "
                          "(collective.Exchange or exchange.NativeExchange)")
     return opt

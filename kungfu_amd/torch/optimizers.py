@@ -23,14 +23,15 @@ takes ``named_parameters`` positionally.
 
 ``ShardedSGDOptimizer`` (the package's own: S-SGD with the SGD update and its
 momentum sharded over the ranks) likewise takes ``named_parameters``
-positionally.
+positionally, and so does ``ShardedAdamOptimizer`` (the same for
+torch.optim.Adam / AdamW and their two state tensors).
 """
 from .. import optimizers as _opt
 from ..optimizers import SynchronousAveragingOptimizer
 
 __all__ = ["SynchronousSGDOptimizer", "SynchronousAveragingOptimizer",
            "MonitorGradientNoiseScaleOptimizer", "MonitorGradientVarianceOptimizer",
-           "PairAveragingOptimizer", "ShardedSGDOptimizer"]
+           "PairAveragingOptimizer", "ShardedSGDOptimizer", "ShardedAdamOptimizer"]
 
 
 def SynchronousSGDOptimizer(optimizer, named_parameters, op=None, **kwargs):
@@ -68,3 +69,9 @@ def ShardedSGDOptimizer(optimizer, named_parameters, **kwargs):
     """kungfu_amd.optimizers.ShardedSGDOptimizer with `named_parameters`
     positional."""
     return _opt.ShardedSGDOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
+
+
+def ShardedAdamOptimizer(optimizer, named_parameters, **kwargs):
+    """kungfu_amd.optimizers.ShardedAdamOptimizer with `named_parameters`
+    positional."""
+    return _opt.ShardedAdamOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
