@@ -214,6 +214,29 @@ int kf_adam_update_batch(void *const *params, const void *const *grads, void *co
                          void *const *exp_avg_sqs, const size_t *counts, int nb,
                          KungFu_Datatype dt, int np, const kf_adam_hyper *hyper, void *stream);
 
+/* kf_adam_update_batch for 16-bit parameters with an fp32 master copy and
+ * fp32 state (kungfu_amd/csrc/kf_adam_master.hip, one launch per 32 segments).
+ * dt is the storage type of params16 / grads16, KungFu_BFLOAT16 or
+ * KungFu_FLOAT16 (anything else is KF_ERR_DTYPE); masters, exp_avgs and
+ * exp_avg_sqs are fp32. Per element:
+ *   g = widen(grads16[b][i])                       (exact)
+ *   (master, m, v) = kf_adam_update_batch's f32 arithmetic above, operation
+ *                    for operation, on (master, g, m, v); the /np is the fp32
+ *                    one and is not rounded to 16 bits
+ *   params16[b][i] = narrow(master)                (round-to-nearest-even)
+ * There is no other rounding to 16 bits anywhere, and the old value of
+ * params16 is never read: the caller keeps params16 == narrow(masters). eps
+ * stays fp32, so f16 parameters are taken; their gradients must be finite
+ * (no loss scaling here). Segment b is counts[b] elements with its own
+ * hyper[b]; every pointer is 16-byte aligned. g (2 bytes), master, m and v
+ * are read once; master, m, v and params16 (2 bytes) written once: 28 bytes
+ * per element. */
+int kf_adam_master_update_batch(void *const *params16, const void *const *grads16,
+                                void *const *masters, void *const *exp_avgs,
+                                void *const *exp_avg_sqs, const size_t *counts, int nb,
+                                KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
+                                void *stream);
+
 /* ---- gradient monitors: segmented squared norms ------------------------- */
 
 /* What MonitorGradientNoiseScaleOptimizer and MonitorGradientVarianceOptimizer
@@ -752,6 +775,20 @@ int kf_exchange_adam_batch(kf_exchange_t *ex, void *const *params, void *const *
                            void *const *exp_avg_shards, void *const *exp_avg_sq_shards,
                            const size_t *counts, int nb, KungFu_Datatype dt,
                            const kf_adam_hyper *hyper, int algo, void *stream);
+/* kf_exchange_adam_batch for 16-bit parameter and gradient buckets (dt bf16 or
+ * f16, KF_ERR_DTYPE otherwise) with fp32 master weights and state
+ * (kf_adam_master_update_batch) on the shard: phases 1 and 3 are the Adam
+ * call's on the 16-bit buckets; phase 2 runs on params[b] + rank * q, the
+ * received gradient shard, and master_shards[b], exp_avg_shards[b] and
+ * exp_avg_sq_shards[b] of q = counts[b] / world fp32 elements. The same
+ * up-front checks on every rank, and the master shard must be there for every
+ * non-empty bucket. World 1 on the built-in transport runs the update over
+ * the whole buckets with np = 1. Un-pipelined; follows kf_exchange_set_timing. */
+int kf_exchange_adam_master_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
+                                  void *const *master_shards, void *const *exp_avg_shards,
+                                  void *const *exp_avg_sq_shards, const size_t *counts, int nb,
+                                  KungFu_Datatype dt, const kf_adam_hyper *hyper, int algo,
+                                  void *stream);
 /* Pipelined schedule for the batch calls (default 1 = off): the buckets of a
  * call are split into `groups` groups of consecutive buckets of about equal
  * bytes; the RCCL phases stay on the caller's stream in the same order on

@@ -121,6 +121,8 @@ EXPORTED = (
     "kf_exchange_sgd_batch",
     "kf_adam_update_batch",
     "kf_exchange_adam_batch",
+    "kf_adam_master_update_batch",
+    "kf_exchange_adam_master_batch",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -462,6 +464,14 @@ def load():
                                            P(c_void_p), P(c_size_t), c_int, c_int, P(AdamHyper),
                                            c_int, c_void_p]
     lib.kf_exchange_adam_batch.restype = c_int
+    lib.kf_adam_master_update_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_void_p),
+                                                P(c_void_p), P(c_size_t), c_int, c_int, c_int,
+                                                P(AdamHyper), c_void_p]
+    lib.kf_adam_master_update_batch.restype = c_int
+    lib.kf_exchange_adam_master_batch.argtypes = [c_void_p, P(c_void_p), P(c_void_p), P(c_void_p),
+                                                  P(c_void_p), P(c_void_p), P(c_size_t), c_int,
+                                                  c_int, P(AdamHyper), c_int, c_void_p]
+    lib.kf_exchange_adam_master_batch.restype = c_int
     _lib = lib
     # HIP resources go back while the runtime is alive, before the C exit
     # handlers run (include/kungfu_amd.h kf_shutdown)

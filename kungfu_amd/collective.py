@@ -69,6 +69,12 @@ class HipEpilogue:
         """The Adam / AdamW update of the shards (ops.adam_update_batch_), one launch."""
         return ops.adam_update_batch_(params, grads, exp_avgs, exp_avg_sqs, hypers, np_)
 
+    def adam_master_update_(self, params16, grads16, masters, exp_avgs, exp_avg_sqs, hypers, np_):
+        """The Adam / AdamW update of 16-bit shards through their fp32 master
+        and state shards (ops.adam_master_update_batch_), one launch."""
+        return ops.adam_master_update_batch_(params16, grads16, masters, exp_avgs, exp_avg_sqs,
+                                             hypers, np_)
+
 
 def coalesce_runs(buckets):
     """Maximal runs of buckets that are consecutive in one storage, each as
@@ -398,20 +404,41 @@ class Exchange:
         bucket b hold numel // world elements. hypers[b] as
         ops.adam_update_batch_ takes them. The gradient buckets are only read
         here; callers must not rely on that."""
-        params, grads = list(param_buckets), list(grad_buckets)
-        ms, vs, hypers = list(exp_avg_shards), list(exp_avg_sq_shards), list(hypers)
-        if not (len(params) == len(grads) == len(ms) == len(vs) == len(hypers)):
-            raise ValueError("adam_step_: one grad bucket, two state shards and a hyper per bucket")
-        for p, g, m, v in zip(params, grads, ms, vs):
+        return self._adam_schedule("adam_step_", param_buckets, grad_buckets,
+                                   (exp_avg_shards, exp_avg_sq_shards), hypers,
+                                   self.epilogue.adam_update_)
+
+    def adam_master_step_(self, param_buckets, grad_buckets, master_shards, exp_avg_shards,
+                          exp_avg_sq_shards, hypers):
+        """adam_step_ for bf16 / f16 buckets with fp32 master weights and state
+        (the native exchange's kf_exchange_adam_master_batch, for this path):
+        the same schedule on the 16-bit buckets; epilogue.adam_master_update_
+        runs once over the shards (16-bit parameters, summed 16-bit gradients,
+        and this rank's fp32 master, exp_avg and exp_avg_sq shards of
+        numel // world elements each)."""
+        return self._adam_schedule("adam_master_step_", param_buckets, grad_buckets,
+                                   (master_shards, exp_avg_shards, exp_avg_sq_shards), hypers,
+                                   self.epilogue.adam_master_update_)
+
+    def _adam_schedule(self, name, param_buckets, grad_buckets, state_shards, hypers, update):
+        """What adam_step_ and adam_master_step_ share: update(params, grads,
+        *states, hypers, np_) on this rank's shards between the gradients'
+        reduce-scatter and the parameters' all-gather."""
+        params, grads, hypers = list(param_buckets), list(grad_buckets), list(hypers)
+        states = [list(s) for s in state_shards]
+        if not all(len(x) == len(params) for x in [grads, hypers] + states):
+            raise ValueError("%s: one grad bucket, %d state shards and a hyper per bucket"
+                             % (name, len(states)))
+        for i, (p, g) in enumerate(zip(params, grads)):
             self._check(p)
             self._check(g)
             if g.numel() != p.numel() or g.dtype != p.dtype or \
-                    m.numel() * self.world != p.numel() or v.numel() != m.numel():
-                raise ValueError("adam_step_: bucket / shard sizes do not match")
+                    any(s[i].numel() * self.world != p.numel() for s in states):
+                raise ValueError("%s: bucket / shard sizes do not match" % name)
         if not params:
             return params
         if self.world == 1:
-            self.epilogue.adam_update_(params, grads, ms, vs, hypers, 1)
+            update(params, grads, *states, hypers, 1)
             return params
         marks = self._marks()
         works = []
@@ -420,20 +447,22 @@ class Exchange:
             works.append((shard, self._scatter(g, shard, OP.SUM, ("adam", "a2a", i))))
         # one update launch over all shards: the / world is the fold's where
         # the shards were folded here, the update's own after a reduce-scatter
-        sets = {0: ([], [], [], [], []), self.world: ([], [], [], [], [])}
+        width = 3 + len(states)
+        sets = {0: tuple([] for _ in range(width)), self.world: tuple([] for _ in range(width))}
         for _, (w, _) in works:
             w.wait()
         self._mark(marks, "reduce_scatter")
-        for p, m, v, h, (shard, (w, recv)) in zip(params, ms, vs, hypers, works):
+        for i, (p, h, (shard, (w, recv))) in enumerate(zip(params, hypers, works)):
             if recv is not None:
                 self.epilogue.fold_(list(recv.chunk(self.world)), shard, OP.SUM, self.world)
             q = shard.numel()
             dst = sets[0 if recv is not None else self.world]
-            for lst, x in zip(dst, (p[self.rank * q:(self.rank + 1) * q], shard, m, v, h)):
+            row = (p[self.rank * q:(self.rank + 1) * q], shard) + tuple(s[i] for s in states) + (h,)
+            for lst, x in zip(dst, row):
                 lst.append(x)
-        for np_, (ps, gs, m_, v_, hs) in sets.items():
-            if ps:
-                self.epilogue.adam_update_(ps, gs, m_, v_, hs, np_)
+        for np_, lists in sets.items():
+            if lists[0]:
+                update(*lists, np_)
         self._mark(marks, "epilogue")
         gathers = []
         for p in params:

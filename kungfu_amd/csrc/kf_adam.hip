@@ -38,11 +38,9 @@
 // (bucket padding, a parameter that never had a gradient) would be 0 / 0.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <string>
 
-#include "kf_sgd_elt.hpp"
-#include "kungfu_amd.h"
+#include "kf_adam_math.hpp"  // the update itself, shared with kf_adam_master.hip
 
 // Load / store policy of the streams, 1 = non-temporal: kf_sgd.hip's measured
 // one. g is dead after this kernel; p, m and v are read and written in place.
@@ -67,8 +65,6 @@ constexpr int kAdamBlock = 256;
 #endif
 constexpr int kAdamUnroll = KF_ADAM_UNROLL;
 
-enum { ADAM_NO_DECAY = 0, ADAM_L2 = 1, ADAM_DECOUPLED = 2 };
-
 // C: the compute type (float for f32 / bf16, double for f64). One segment's
 // entries sit together, as kf_sgd.hip's SgdSeg.
 template <typename C> struct AdamSeg {
@@ -87,71 +83,6 @@ template <typename C> struct AdamBatchArgs {
 };
 // kf_sgd.hip's SgdBatchArgs budget: an entry is 112 bytes for f64, so 24 of them
 static_assert(sizeof(AdamBatchArgs<double>) + sizeof(Div) <= 3072, "kernarg budget");
-
-// Correctly rounded sqrt and division of the compute scalar or of a lane pair.
-__device__ __forceinline__ float adam_sqrt(float x) { return sqrtf(x); }
-__device__ __forceinline__ double adam_sqrt(double x) { return __dsqrt_rn(x); }
-__device__ __forceinline__ float adam_div(float a, float b) { return __fdiv_rn(a, b); }
-__device__ __forceinline__ double adam_div(double a, double b) { return __ddiv_rn(a, b); }
-__device__ __forceinline__ f32x2 adam_sqrt(f32x2 x) { return f32x2{sqrtf(x.x), sqrtf(x.y)}; }
-__device__ __forceinline__ f64x2 adam_sqrt(f64x2 x)
-{
-    return f64x2{__dsqrt_rn(x.x), __dsqrt_rn(x.y)};
-}
-__device__ __forceinline__ f32x2 adam_div(f32x2 a, float b)
-{
-    return f32x2{__fdiv_rn(a.x, b), __fdiv_rn(a.y, b)};
-}
-__device__ __forceinline__ f64x2 adam_div(f64x2 a, double b)
-{
-    return f64x2{__ddiv_rn(a.x, b), __ddiv_rn(a.y, b)};
-}
-__device__ __forceinline__ f32x2 adam_div(f32x2 a, f32x2 b)
-{
-    return f32x2{__fdiv_rn(a.x, b.x), __fdiv_rn(a.y, b.y)};
-}
-__device__ __forceinline__ f64x2 adam_div(f64x2 a, f64x2 b)
-{
-    return f64x2{__ddiv_rn(a.x, b.x), __ddiv_rn(a.y, b.y)};
-}
-
-// The update of H values (V = C) or of H lane pairs (V = X); g holds the
-// summed gradients on entry; h is the segment's kernarg entry, whose scalars
-// are wave-uniform. DECAY is the segment's choice, made once per block.
-template <typename T, int DIV, int DECAY, int H, typename V>
-__device__ __forceinline__ void adam_math(V (&p)[H], V (&g)[H], V (&m)[H], V (&v)[H],
-                                          const AdamSeg<typename SgdElt<T>::C> &h, const Div &d)
-{
-    using E = SgdElt<T>;
-#pragma unroll
-    for (int i = 0; i < H; ++i) g[i] = SgdDiv<T, DIV>::run(g[i], d);
-    if constexpr (DECAY == ADAM_L2) {
-#pragma unroll
-        for (int i = 0; i < H; ++i) g[i] = E::rnd(g[i] + h.w * p[i]);
-    } else if constexpr (DECAY == ADAM_DECOUPLED) {
-#pragma unroll
-        for (int i = 0; i < H; ++i) p[i] = E::rnd(h.w * p[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < H; ++i) {
-        const V t = h.b1 * m[i];
-        m[i]      = E::rnd(t + h.c1 * g[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < H; ++i) {
-        const V t = E::rnd(h.b2 * v[i]);
-        const V q = g[i] * g[i];
-        v[i]      = E::rnd(t + h.c2 * q);
-    }
-#pragma unroll
-    for (int i = 0; i < H; ++i) {
-        const V r = E::rnd(adam_sqrt(v[i]));
-        const V e = E::rnd(adam_div(r, h.s2));
-        const V f = E::rnd(e + h.eps);
-        const V u = adam_div(m[i], f);
-        p[i]      = E::rnd(p[i] + h.nss * u);
-    }
-}
 
 // one vector: p, m and v updated and stored
 template <typename T, int DIV, int DECAY>
@@ -334,16 +265,7 @@ int launch_adam(void *const *params, const void *const *grads, void *const *ms, 
         g.m                    = ms[b];
         g.v                    = vs[b];
         g.n                    = n;
-        // computed in double, cast once to the compute type
-        g.decay = h.weight_decay == 0 ? ADAM_NO_DECAY : (h.decoupled ? ADAM_DECOUPLED : ADAM_L2);
-        g.w     = static_cast<C>(h.decoupled ? 1.0 - h.lr * h.weight_decay : h.weight_decay);
-        g.b1    = static_cast<C>(h.beta1);
-        g.c1    = static_cast<C>(1.0 - h.beta1);
-        g.b2    = static_cast<C>(h.beta2);
-        g.c2    = static_cast<C>(1.0 - h.beta2);
-        g.s2    = static_cast<C>(std::sqrt(h.bias_correction2));
-        g.eps   = static_cast<C>(h.eps);
-        g.nss   = static_cast<C>(-(h.lr / h.bias_correction1));
+        adam_scalars<C>(g, h);
         a.blk0[a.nseg] = static_cast<unsigned>(blocks);
         blocks += nblk;
         if (nblk > widest) widest = nblk;

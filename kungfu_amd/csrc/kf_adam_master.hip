@@ -1,0 +1,379 @@
+// kf_adam_master.hip — the Adam / AdamW update of 16-bit parameters through an
+// fp32 master copy and fp32 state (include/kungfu_amd.h
+// kf_adam_master_update_batch):
+//
+//   reduce-scatter(grads16) -> [own shard: widen g, kf_adam.hip's f32 update
+//                               on (master, g, m, v), p16 = narrow(master)]
+//                           -> all-gather(params16)
+//
+// kf_adam.hip's shape: one batched element-wise launch over up to
+// kAdamMasterSeg segments, every segment with its own pointers, count and
+// scalars in the kernarg segment. A segment reads g (2 B) and master, m, v
+// (12 B) and writes master, m, v (12 B) and p16 (2 B): 28 bytes per element,
+// the f32 kernel's 7 x 4. The old 16-bit parameter value is never read.
+//
+// Arithmetic: adam_math<float, ...> of kf_adam_math.hpp, the f32 kernel's own,
+// on the widened gradient (the widening is exact); the /np is the fp32 one and
+// is not rounded to 16 bits. The only rounding to 16 bits is the last:
+// p16 = narrow(master'), round-to-nearest-even (SgdElt<T>::narrow). The
+// narrowed value is a sum, so f16's v_fma_mixlo_f16 -0 hazard (kf_sgd_elt.hpp)
+// does not arise; tests/test_sharded_adam_master_gpu.py's narrowing grid
+// checks both zeros.
+//
+// One unit is kAdamMasterElts consecutive elements of a lane. 4 (the default):
+// an 8-byte access on the 16-bit streams and one 16-byte access on each fp32
+// stream, so every wave instruction is contiguous. 8: one 16-byte access on
+// the 16-bit streams and two 16-byte accesses, 32 bytes apart per lane, on
+// each fp32 stream. DESIGN.md §15 has both measured.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "kf_adam_math.hpp"
+
+// Load / store policy of the streams, 1 = non-temporal: kf_adam.hip's. g is
+// dead after this kernel; master, m and v are read and written in place; p16
+// is what the all-gather sends next.
+#ifndef KF_ADAM_MASTER_G_NT
+#define KF_ADAM_MASTER_G_NT 1
+#endif
+#ifndef KF_ADAM_MASTER_WMV_NT
+#define KF_ADAM_MASTER_WMV_NT 0
+#endif
+#ifndef KF_ADAM_MASTER_ST_NT
+#define KF_ADAM_MASTER_ST_NT 0
+#endif
+
+namespace kf
+{
+void set_last_error(const std::string &msg);  // kf_capi.hip: kf_last_error's text
+
+constexpr int kAdamMasterSeg   = 32;
+constexpr int kAdamMasterBlock = 256;
+#ifndef KF_ADAM_MASTER_ELTS
+#define KF_ADAM_MASTER_ELTS 4  // elements per unit: 4 or 8
+#endif
+constexpr int kAdamMasterElts = KF_ADAM_MASTER_ELTS;
+static_assert(kAdamMasterElts == 4 || kAdamMasterElts == 8, "a unit is 4 or 8 elements");
+// Units per lane per tile. A unit's loads are 3.5 (4 elements) or 7 (8
+// elements) 16-byte equivalents, so 14 are in flight per lane where
+// kf_adam.hip has 16.
+#ifndef KF_ADAM_MASTER_UNROLL
+#define KF_ADAM_MASTER_UNROLL (16 / KF_ADAM_MASTER_ELTS)
+#endif
+constexpr int kAdamMasterUnroll = KF_ADAM_MASTER_UNROLL;
+
+struct AdamMasterSeg {
+    void *p16;      // the 16-bit parameters, written only
+    const void *g;  // the 16-bit summed gradients
+    void *p, *m, *v;  // fp32: master, exp_avg, exp_avg_sq
+    size_t n;
+    float w;  // ADAM_L2: weight_decay; ADAM_DECOUPLED: dk = 1 - lr*weight_decay
+    float b1, c1, b2, c2, s2, eps, nss;
+    int decay;
+};
+struct AdamMasterArgs {
+    AdamMasterSeg seg[kAdamMasterSeg];
+    unsigned blk0[kAdamMasterSeg + 1];  // the search table (1-D grids only)
+    int nseg;
+};
+// kf_adam.hip's budget: an entry is 88 bytes (one pointer more than
+// AdamSeg<float>'s 80), so 32 of them; 33 would be 3,076 bytes
+static_assert(sizeof(AdamMasterSeg) == 88, "kernarg entry");
+static_assert(sizeof(AdamMasterArgs) + sizeof(Div) <= 3072, "kernarg budget");
+static_assert(sizeof(AdamMasterArgs) + sizeof(AdamMasterSeg) + 4 + sizeof(Div) > 3072,
+              "kAdamMasterSeg is the most the budget holds");
+
+constexpr int kMH = kAdamMasterElts / 2;  // lane pairs (and 16-bit words) per unit
+constexpr int kMK = kAdamMasterElts / 4;  // 16-byte fp32 vectors per stream per unit
+typedef unsigned int u32xh __attribute__((ext_vector_type(kMH)));  // a unit of a 16-bit stream
+
+template <int NT> __device__ __forceinline__ u32xh ld_h(const void *base, size_t ui)
+{
+    const u32xh *p = reinterpret_cast<const u32xh *>(base) + ui;
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+
+// two 16-bit lanes of a 32-bit word <-> a lane pair
+template <typename T> __device__ __forceinline__ f32x2 widen2(unsigned w)
+{
+    if constexpr (std::is_same<T, bf16_t>::value) {
+        return f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
+    } else {
+        return f32x2{SgdElt<T>::widen(static_cast<uint16_t>(w)),
+                     SgdElt<T>::widen(static_cast<uint16_t>(w >> 16))};
+    }
+}
+template <typename T> __device__ __forceinline__ unsigned narrow2(f32x2 x)
+{
+    return static_cast<unsigned>(SgdElt<T>::narrow(x.x)) |
+           (static_cast<unsigned>(SgdElt<T>::narrow(x.y)) << 16);
+}
+
+__device__ __forceinline__ void unpack_f32(const u32x4 (&raw)[kMK], f32x2 (&x)[kMH])
+{
+#pragma unroll
+    for (int j = 0; j < kMK; ++j) {
+        x[2 * j]     = f32x2{__uint_as_float(raw[j][0]), __uint_as_float(raw[j][1])};
+        x[2 * j + 1] = f32x2{__uint_as_float(raw[j][2]), __uint_as_float(raw[j][3])};
+    }
+}
+__device__ __forceinline__ void store_f32(void *base, size_t ui, const f32x2 (&x)[kMH])
+{
+#pragma unroll
+    for (int j = 0; j < kMK; ++j) {
+        const u32x4 raw = {__float_as_uint(x[2 * j].x), __float_as_uint(x[2 * j].y),
+                           __float_as_uint(x[2 * j + 1].x), __float_as_uint(x[2 * j + 1].y)};
+        st_u4<KF_ADAM_MASTER_ST_NT>(base, ui * kMK + j, raw);
+    }
+}
+
+// one unit: master, m, v and the narrowed parameters updated and stored
+template <typename T, int DIV, int DECAY>
+__device__ __forceinline__ void master_unit(const AdamMasterSeg &h, const Div &d, size_t ui,
+                                            const u32xh &rg, const u32x4 (&rp)[kMK],
+                                            const u32x4 (&rm)[kMK], const u32x4 (&rv)[kMK])
+{
+    f32x2 p[kMH], g[kMH], m[kMH], v[kMH];
+#pragma unroll
+    for (int w = 0; w < kMH; ++w) g[w] = widen2<T>(rg[w]);
+    unpack_f32(rp, p);
+    unpack_f32(rm, m);
+    unpack_f32(rv, v);
+    adam_math<float, DIV, DECAY, kMH, f32x2>(p, g, m, v, h, d);
+    store_f32(h.p, ui, p);
+    store_f32(h.m, ui, m);
+    store_f32(h.v, ui, v);
+    u32xh out;
+#pragma unroll
+    for (int w = 0; w < kMH; ++w) out[w] = narrow2<T>(p[w]);
+    u32xh *dst = reinterpret_cast<u32xh *>(h.p16) + ui;
+    if constexpr (KF_ADAM_MASTER_ST_NT) __builtin_nontemporal_store(out, dst);
+    else *dst = out;
+}
+
+template <int NT>
+__device__ __forceinline__ void ld_f32(const void *base, size_t ui, u32x4 (&raw)[kMK])
+{
+#pragma unroll
+    for (int j = 0; j < kMK; ++j) raw[j] = ld_u4<NT>(base, ui * kMK + j);
+}
+
+// Block `blk` of `nblk` on one segment.
+template <typename T, int DIV, int DECAY>
+__device__ __forceinline__ void master_body(const AdamMasterSeg &h, const Div &d, size_t blk,
+                                            size_t nblk)
+{
+    using E         = SgdElt<T>;
+    constexpr int N = kAdamMasterElts;
+    constexpr int U = kAdamMasterUnroll, B = kAdamMasterBlock;
+    constexpr int WNT = KF_ADAM_MASTER_WMV_NT;
+    const size_t n     = h.n;
+    const size_t nunit = n / N;
+
+    // the scalar tail: fewer than N elements, on the segment's first block
+    const size_t ti = nunit * N + threadIdx.x;
+    if (blk == 0 && ti < n) {
+        uint16_t *s16       = reinterpret_cast<uint16_t *>(h.p16);
+        const uint16_t *sg  = reinterpret_cast<const uint16_t *>(h.g);
+        float *sp = reinterpret_cast<float *>(h.p), *sm = reinterpret_cast<float *>(h.m);
+        float *sv = reinterpret_cast<float *>(h.v);
+        float p[1] = {sp[ti]}, g[1] = {E::widen(sg[ti])}, m[1] = {sm[ti]}, v[1] = {sv[ti]};
+        adam_math<float, DIV, DECAY, 1, float>(p, g, m, v, h, d);
+        sp[ti]  = p[0];
+        sm[ti]  = m[0];
+        sv[ti]  = v[0];
+        s16[ti] = E::narrow(p[0]);
+    }
+
+    const size_t tile   = static_cast<size_t>(B) * U;
+    const size_t ntiles = (nunit + tile - 1) / tile;
+    for (size_t t = blk; t < ntiles; t += nblk) {
+        const size_t u0 = t * tile + threadIdx.x;
+        if (u0 + (U - 1) * B < nunit) {
+            // full tile: every load issued before the first use
+            u32xh rg[U];
+            u32x4 rp[U][kMK], rm[U][kMK], rv[U][kMK];
+#pragma unroll
+            for (int u = 0; u < U; ++u) rg[u] = ld_h<KF_ADAM_MASTER_G_NT>(h.g, u0 + u * B);
+#pragma unroll
+            for (int u = 0; u < U; ++u) ld_f32<WNT>(h.p, u0 + u * B, rp[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u) ld_f32<WNT>(h.m, u0 + u * B, rm[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u) ld_f32<WNT>(h.v, u0 + u * B, rv[u]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                master_unit<T, DIV, DECAY>(h, d, u0 + u * B, rg[u], rp[u], rm[u], rv[u]);
+            }
+        } else {
+            // ragged last tile
+            for (int u = 0; u < U; ++u) {
+                const size_t ui = u0 + u * B;
+                if (ui >= nunit) break;
+                const u32xh rg = ld_h<KF_ADAM_MASTER_G_NT>(h.g, ui);
+                u32x4 rp[kMK], rm[kMK], rv[kMK];
+                ld_f32<WNT>(h.p, ui, rp);
+                ld_f32<WNT>(h.m, ui, rm);
+                ld_f32<WNT>(h.v, ui, rv);
+                master_unit<T, DIV, DECAY>(h, d, ui, rg, rp, rm, rv);
+            }
+        }
+    }
+}
+
+// The segment's decay, chosen once per block (kf_adam.hip adam_seg).
+template <typename T, int DIV>
+__device__ __forceinline__ void master_seg(const AdamMasterSeg &h, const Div &d, size_t blk,
+                                           size_t nblk)
+{
+    if (h.decay == ADAM_NO_DECAY) master_body<T, DIV, ADAM_NO_DECAY>(h, d, blk, nblk);
+    else if (h.decay == ADAM_L2) master_body<T, DIV, ADAM_L2>(h, d, blk, nblk);
+    else master_body<T, DIV, ADAM_DECOUPLED>(h, d, blk, nblk);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kAdamMasterBlock)
+    adam_master_kernel(AdamMasterArgs a, Div np, int div)
+{
+    // kf_adam.hip's two grids: segments of about equal size are the rows of a
+    // 2-D grid; otherwise the segment of block b is the last s with
+    // blk0[s] <= b, searched in the kernarg table.
+    const bool rows = gridDim.y > 1;
+    int s           = static_cast<int>(blockIdx.y);
+    size_t blk = blockIdx.x, nblk = gridDim.x;
+    if (!rows) {
+        const unsigned b = blockIdx.x;
+        int lo = 0, hi = a.nseg - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (b >= a.blk0[mid]) lo = mid;
+            else hi = mid - 1;
+        }
+        s    = lo;
+        blk  = b - a.blk0[s];
+        nblk = a.blk0[s + 1] - a.blk0[s];
+    }
+    const AdamMasterSeg &g = a.seg[s];
+    // the /np choice made once per kernel
+    if (div == 0) master_seg<T, 0>(g, np, blk, nblk);
+    else if (div == 1) master_seg<T, 1>(g, np, blk, nblk);
+    else master_seg<T, 2>(g, np, blk, nblk);
+}
+
+}  // namespace kf
+
+namespace
+{
+using namespace kf;
+
+int fail(int rc, const char *name, const std::string &what)
+{
+    set_last_error(std::string(name) + ": kf_adam_master_update_batch: " + what);
+    return rc;
+}
+
+template <typename T>
+int launch_master(void *const *params16, const void *const *grads16, void *const *masters,
+                  void *const *ms, void *const *vs, const size_t *counts, int nb, int np,
+                  const kf_adam_hyper *hyper, hipStream_t s)
+{
+    constexpr int N = kAdamMasterElts;
+    const Div dv    = update_div(np);
+    const int div   = np == 0 ? 0 : (dv.pow2 ? 1 : 2);
+    AdamMasterArgs a;
+    a.nseg        = 0;
+    size_t blocks = 0, widest = 0;
+    auto flush    = [&]() -> int {
+        if (a.nseg == 0) return KF_OK;
+        a.blk0[a.nseg] = static_cast<unsigned>(blocks);
+        // one row per segment when that at most doubles the grid
+        const bool rows = a.nseg > 1 && widest * a.nseg <= 2 * blocks;
+        const dim3 grid = rows ? dim3(static_cast<unsigned>(widest), a.nseg)
+                               : dim3(static_cast<unsigned>(blocks));
+        adam_master_kernel<T><<<grid, kAdamMasterBlock, 0, s>>>(a, dv, div);
+        a.nseg = 0;
+        blocks = widest = 0;
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            return fail(KF_ERR_HIP, "KF_ERR_HIP", std::string("launch: ") + hipGetErrorString(e));
+        }
+        return KF_OK;
+    };
+    const size_t tile = static_cast<size_t>(kAdamMasterBlock) * kAdamMasterUnroll;
+    for (int b = 0; b < nb; ++b) {
+        const size_t n = counts[b];
+        if (n == 0) continue;
+        size_t nblk = (n / N + tile - 1) / tile;  // one block per tile
+        if (nblk < 1) nblk = 1;                   // a tail alone
+        if (nblk > 0x400000u) nblk = 0x400000u;   // then blocks stride over the tiles
+        if (blocks + nblk > 0x7fffffu) {          // grid * block stays below 2^32 threads,
+            const int rc = flush();               // also as rows (at most twice the blocks)
+            if (rc != KF_OK) return rc;
+        }
+        AdamMasterSeg &g = a.seg[a.nseg];
+        g.p16            = params16[b];
+        g.g              = grads16[b];
+        g.p              = masters[b];
+        g.m              = ms[b];
+        g.v              = vs[b];
+        g.n              = n;
+        adam_scalars<float>(g, hyper[b]);
+        a.blk0[a.nseg] = static_cast<unsigned>(blocks);
+        blocks += nblk;
+        if (nblk > widest) widest = nblk;
+        if (++a.nseg == kAdamMasterSeg) {
+            const int rc = flush();
+            if (rc != KF_OK) return rc;
+        }
+    }
+    return flush();
+}
+
+bool off16(const void *p) { return (reinterpret_cast<uintptr_t>(p) % 16) != 0; }
+
+}  // namespace
+
+extern "C" {
+
+int kf_adam_master_update_batch(void *const *params16, const void *const *grads16,
+                                void *const *masters, void *const *exp_avgs,
+                                void *const *exp_avg_sqs, const size_t *counts, int nb,
+                                KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
+                                void *stream)
+{
+    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
+    if (nb == 0) return KF_OK;
+    if (!params16 || !grads16 || !masters || !exp_avgs || !exp_avg_sqs || !counts || !hyper) {
+        return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
+    }
+    if (dt != KungFu_BFLOAT16 && dt != KungFu_FLOAT16) {
+        return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
+                    "bf16 and f16 parameters only (f32 and f64 take kf_adam_update_batch)");
+    }
+    if (np < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "np < 0");
+    for (int b = 0; b < nb; ++b) {
+        if (counts[b] == 0) continue;
+        if (!params16[b] || !grads16[b] || !masters[b] || !exp_avgs[b] || !exp_avg_sqs[b]) {
+            return fail(KF_ERR_ARG, "KF_ERR_ARG", "null pointer in a non-empty segment");
+        }
+        if (off16(params16[b]) || off16(grads16[b]) || off16(masters[b]) || off16(exp_avgs[b]) ||
+            off16(exp_avg_sqs[b])) {
+            return fail(KF_ERR_ARG, "KF_ERR_ARG", "pointers must be 16-byte aligned");
+        }
+        if (!(hyper[b].bias_correction1 > 0) || !(hyper[b].bias_correction2 > 0)) {
+            return fail(KF_ERR_ARG, "KF_ERR_ARG", "bias corrections must be > 0");
+        }
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dt == KungFu_BFLOAT16) {
+        return launch_master<bf16_t>(params16, grads16, masters, exp_avgs, exp_avg_sqs, counts, nb,
+                                     np, hyper, s);
+    }
+    return launch_master<f16_t>(params16, grads16, masters, exp_avgs, exp_avg_sqs, counts, nb, np,
+                                hyper, s);
+}
+
+}  // extern "C"

@@ -346,16 +346,22 @@ struct NamedTask {
 };
 
 // The optimizer update on the shards (kf_exchange_sgd_batch,
-// kf_exchange_adam_batch): the tables, one entry per bucket, and the batched
-// kernel that takes them. Exactly one of sgd / adam is set.
+// kf_exchange_adam_batch, kf_exchange_adam_master_batch): the tables, one
+// entry per bucket, and the batched kernel that takes them. Exactly one of
+// sgd / adam is set.
 struct ShardUpdate {
     void *const *params;
     void *const *state;   // this rank's momentum (SGD) or exp_avg (Adam) shards
     void *const *state2;  // Adam: this rank's exp_avg_sq shards
     const kf_sgd_hyper *sgd;
     const kf_adam_hyper *adam;
+    void *const *master = nullptr;  // Adam on 16-bit buckets: this rank's fp32 master shards
 
-    const char *kernel() const { return sgd ? "kf_sgd_update_batch" : "kf_adam_update_batch"; }
+    const char *kernel() const
+    {
+        return sgd ? "kf_sgd_update_batch"
+                   : (master ? "kf_adam_master_update_batch" : "kf_adam_update_batch");
+    }
     // buckets b0 .. b0 + n - 1: ps / gs are the shards (or the whole buckets)
     int run(void *const *ps, const void *const *gs, const size_t *cnts, int b0, int n,
             KungFu_Datatype dt, int np, hipStream_t s) const
@@ -363,6 +369,10 @@ struct ShardUpdate {
         if (sgd) {
             return kf_sgd_update_batch(ps, gs, state ? state + b0 : nullptr, cnts, n, dt, np,
                                        sgd + b0, s);
+        }
+        if (master) {
+            return kf_adam_master_update_batch(ps, gs, master + b0, state + b0, state2 + b0, cnts,
+                                               n, dt, np, adam + b0, s);
         }
         return kf_adam_update_batch(ps, gs, state + b0, state2 + b0, cnts, n, dt, np, adam + b0, s);
     }
@@ -1688,18 +1698,29 @@ int kf_exchange_sgd_batch(kf_exchange_t *ex, void *const *params, void *const *g
                      static_cast<hipStream_t>(stream), nullptr, 7, &step);
 }
 
-int kf_exchange_adam_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
-                           void *const *exp_avg_shards, void *const *exp_avg_sq_shards,
-                           const size_t *counts, int nb, KungFu_Datatype dt,
-                           const kf_adam_hyper *hyper, int algo, void *stream)
+// kf_exchange_adam_batch and kf_exchange_adam_master_batch: the checks every
+// rank makes before any collective is queued, then the three phases.
+// with_master: 16-bit buckets with fp32 master and state shards; otherwise the
+// state has the buckets' dtype and master_shards is not looked at.
+static int exchange_adam(const char *name, kf_exchange_t *ex, void *const *params,
+                         void *const *grads, void *const *master_shards, bool with_master,
+                         void *const *exp_avg_shards, void *const *exp_avg_sq_shards,
+                         const size_t *counts, int nb, KungFu_Datatype dt,
+                         const kf_adam_hyper *hyper, int algo, void *stream)
 {
-    if (!ex || nb < 0) return fail(KF_ERR_ARG, "kf_exchange_adam_batch: bad arguments");
-    if (dt != KungFu_FLOAT && dt != KungFu_DOUBLE && dt != KungFu_BFLOAT16) {
-        return fail(KF_ERR_DTYPE, "kf_exchange_adam_batch: f32, bf16 and f64 only");
+    const std::string fn = std::string(name) + ": ";
+    if (!ex || nb < 0) return fail(KF_ERR_ARG, fn + "bad arguments");
+    if (with_master) {
+        if (dt != KungFu_BFLOAT16 && dt != KungFu_FLOAT16) {
+            return fail(KF_ERR_DTYPE, fn + "bf16 and f16 only");
+        }
+    } else if (dt != KungFu_FLOAT && dt != KungFu_DOUBLE && dt != KungFu_BFLOAT16) {
+        return fail(KF_ERR_DTYPE, fn + "f32, bf16 and f64 only");
     }
     if (nb == 0) return KF_OK;
-    if (!params || !grads || !exp_avg_shards || !exp_avg_sq_shards || !counts || !hyper) {
-        return fail(KF_ERR_ARG, "kf_exchange_adam_batch: null table");
+    if (!params || !grads || !exp_avg_shards || !exp_avg_sq_shards || !counts || !hyper ||
+        (with_master && !master_shards)) {
+        return fail(KF_ERR_ARG, fn + "null table");
     }
     if (algo < KF_ALGO_AUTO || algo > KF_ALGO_REDUCE_SCATTER_AVG) return fail(KF_ERR_ARG, "unknown algo");
     // every rank must reach the same verdict before any collective is queued
@@ -1707,29 +1728,51 @@ int kf_exchange_adam_batch(kf_exchange_t *ex, void *const *params, void *const *
     auto off16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) % 16) != 0; };
     for (int b = 0; b < nb; ++b) {
         if (counts[b] == 0) continue;
-        if (!params[b] || !grads[b]) return fail(KF_ERR_ARG, "kf_exchange_adam_batch: null bucket");
+        if (!params[b] || !grads[b]) return fail(KF_ERR_ARG, fn + "null bucket");
         if (counts[b] % W) {
-            return fail(KF_ERR_ARG, "kf_exchange_adam_batch: counts must be multiples of the world "
-                                    "(padded buckets, no tails)");
+            return fail(KF_ERR_ARG, fn + "counts must be multiples of the world "
+                                         "(padded buckets, no tails)");
         }
         if (!exp_avg_shards[b] || !exp_avg_sq_shards[b]) {
-            return fail(KF_ERR_ARG, "kf_exchange_adam_batch: every non-empty bucket needs both "
-                                    "state shards");
+            return fail(KF_ERR_ARG, fn + "every non-empty bucket needs both state shards");
+        }
+        if (with_master && !master_shards[b]) {
+            return fail(KF_ERR_ARG, fn + "every non-empty bucket needs its master shard");
         }
         if (off16(params[b]) || off16(grads[b]) || off16(exp_avg_shards[b]) ||
-            off16(exp_avg_sq_shards[b]) || (W > 1 && (counts[b] / W * sz) % 16)) {
-            return fail(KF_ERR_ARG, "kf_exchange_adam_batch: buckets and their shards must start "
-                                    "16-byte aligned");
+            off16(exp_avg_sq_shards[b]) || (with_master && off16(master_shards[b])) ||
+            (W > 1 && (counts[b] / W * sz) % 16)) {
+            return fail(KF_ERR_ARG, fn + "buckets and their shards must start 16-byte aligned");
         }
         if (!(hyper[b].bias_correction1 > 0) || !(hyper[b].bias_correction2 > 0)) {
-            return fail(KF_ERR_ARG, "kf_exchange_adam_batch: bias corrections must be > 0");
+            return fail(KF_ERR_ARG, fn + "bias corrections must be > 0");
         }
     }
     DeviceGuard g(ex->device);
     std::lock_guard<std::mutex> lk(ex->mu);
-    const ShardUpdate step{params, exp_avg_shards, exp_avg_sq_shards, nullptr, hyper};
+    const ShardUpdate step{params, exp_avg_shards, exp_avg_sq_shards, nullptr, hyper,
+                           with_master ? master_shards : nullptr};
     return ex->batch(grads, grads, counts, nb, dt, KungFu_SUM, 1, algo,
                      static_cast<hipStream_t>(stream), nullptr, 7, &step);
+}
+
+int kf_exchange_adam_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
+                           void *const *exp_avg_shards, void *const *exp_avg_sq_shards,
+                           const size_t *counts, int nb, KungFu_Datatype dt,
+                           const kf_adam_hyper *hyper, int algo, void *stream)
+{
+    return exchange_adam("kf_exchange_adam_batch", ex, params, grads, nullptr, false,
+                         exp_avg_shards, exp_avg_sq_shards, counts, nb, dt, hyper, algo, stream);
+}
+
+int kf_exchange_adam_master_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
+                                  void *const *master_shards, void *const *exp_avg_shards,
+                                  void *const *exp_avg_sq_shards, const size_t *counts, int nb,
+                                  KungFu_Datatype dt, const kf_adam_hyper *hyper, int algo,
+                                  void *stream)
+{
+    return exchange_adam("kf_exchange_adam_master_batch", ex, params, grads, master_shards, true,
+                         exp_avg_shards, exp_avg_sq_shards, counts, nb, dt, hyper, algo, stream);
 }
 
 int kf_exchange_set_pipeline(kf_exchange_t *ex, int groups)

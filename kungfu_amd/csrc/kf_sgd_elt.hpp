@@ -1,6 +1,7 @@
 // kf_sgd_elt.hpp — what the batched optimizer-update kernels share
-// (kf_sgd.hip, kf_adam.hip): the storage <-> compute traits of the four float
-// dtypes, the /np of kf_bucket_div, and a 16-byte vector's unpack / pack.
+// (kf_sgd.hip, kf_adam.hip, kf_adam_master.hip): the storage <-> compute
+// traits of the four float dtypes, the /np of kf_bucket_div, and a 16-byte
+// vector's unpack / pack.
 #pragma once
 #include "kf_reduce_kernels.hpp"
 

@@ -288,26 +288,50 @@ class NativeExchange:
         numel // world elements of the parameters' dtype (f32, bf16 or f64).
         The gradient buckets are scratch: they hold nothing defined
         afterwards."""
-        params, grads = list(param_buckets), list(grad_buckets)
-        ms, vs, hypers = list(exp_avg_shards), list(exp_avg_sq_shards), list(hypers)
-        if not (len(params) == len(grads) == len(ms) == len(vs) == len(hypers)):
-            raise ValueError("adam_step_: one grad bucket, two state shards and a hyper per bucket")
+        return self._adam_call("adam_step_", self.lib.kf_exchange_adam_batch,
+                               "kf_exchange_adam_batch", param_buckets, grad_buckets,
+                               (exp_avg_shards, exp_avg_sq_shards), hypers)
+
+    def adam_master_step_(self, param_buckets, grad_buckets, master_shards, exp_avg_shards,
+                          exp_avg_sq_shards, hypers):
+        """adam_step_ for bf16 / f16 buckets with fp32 master weights and state
+        (kf_exchange_adam_master_batch): the reduce-scatter and the all-gather
+        carry the 16-bit buckets; ops.adam_master_update_batch_'s kernel runs
+        on this rank's shard of every bucket with its fp32 master, exp_avg and
+        exp_avg_sq shards of numel // world elements each. The gradient
+        buckets are scratch."""
+        return self._adam_call("adam_master_step_", self.lib.kf_exchange_adam_master_batch,
+                               "kf_exchange_adam_master_batch", param_buckets, grad_buckets,
+                               (master_shards, exp_avg_shards, exp_avg_sq_shards), hypers)
+
+    def _adam_call(self, name, fn, cname, param_buckets, grad_buckets, state_shards, hypers):
+        params, grads, hypers = list(param_buckets), list(grad_buckets), list(hypers)
+        states = [list(s) for s in state_shards]
+        if not all(len(x) == len(params) for x in [grads, hypers] + states):
+            raise ValueError("%s: one grad bucket, %d state shards and a hyper per bucket"
+                             % (name, len(states)))
         if not params:
             return params
-        self._check(params + grads + ms + vs)
-        for p, g, m, v in zip(params, grads, ms, vs):
-            if g.numel() != p.numel() or m.numel() * self.world != p.numel() or \
-                    v.numel() != m.numel():
-                raise ValueError("adam_step_: bucket / shard sizes do not match")
-        rc = self.lib.kf_exchange_adam_batch(
-            self._h, _lib.ptr_array([p.data_ptr() for p in params]),
-            _lib.ptr_array([g.data_ptr() for g in grads]),
-            _lib.ptr_array([m.data_ptr() for m in ms]),
-            _lib.ptr_array([v.data_ptr() for v in vs]),
-            _arr(ctypes.c_size_t, [p.numel() for p in params]), len(params),
-            int(kungfu_dtype(params[0])), _lib.adam_hyper_array(hypers), ALGOS[self.algo],
-            torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(rc, "kf_exchange_adam_batch")
+        flat = [t for s in states for t in s]
+        if len(states) == 3:  # master weights: fp32 shards beside 16-bit buckets
+            self._check(params + grads)
+            self._check(flat)
+            if flat[0].dtype != torch.float32 or \
+                    params[0].dtype not in (torch.bfloat16, torch.float16):
+                raise ValueError("%s: bf16 or f16 buckets and fp32 shards" % name)
+        else:
+            self._check(params + grads + flat)
+        for i, (p, g) in enumerate(zip(params, grads)):
+            if g.numel() != p.numel() or \
+                    any(s[i].numel() * self.world != p.numel() for s in states):
+                raise ValueError("%s: bucket / shard sizes do not match" % name)
+        rc = fn(self._h, _lib.ptr_array([p.data_ptr() for p in params]),
+                _lib.ptr_array([g.data_ptr() for g in grads]),
+                *[_lib.ptr_array([t.data_ptr() for t in s]) for s in states],
+                _arr(ctypes.c_size_t, [p.numel() for p in params]), len(params),
+                int(kungfu_dtype(params[0])), _lib.adam_hyper_array(hypers), ALGOS[self.algo],
+                torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(rc, cname)
         return params
 
     def all_reduce_named(self, name, buf, op="sum", average=False, stream=None, callback=None):

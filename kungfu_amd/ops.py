@@ -250,6 +250,40 @@ def adam_update_batch_(params, grads, exp_avgs, exp_avg_sqs, hypers, np_=0, stre
     return params
 
 
+def adam_master_update_batch_(params16, grads16, masters, exp_avgs, exp_avg_sqs, hypers, np_=0,
+                              stream=None):
+    """adam_update_batch_ for bf16 or f16 parameters with fp32 master weights
+    and fp32 state, one launch per 32 segments (kf_adam_master_update_batch,
+    kungfu_amd/csrc/kf_adam_master.hip): the gradient is widened, the f32
+    update of adam_update_batch_ runs on (masters, g, exp_avgs, exp_avg_sqs)
+    in place, and params16 = masters narrowed, round-to-nearest-even, the only
+    rounding to 16 bits. params16 is written, never read; grads16 only read.
+    hypers[b] as adam_update_batch_ takes them. Every tensor starts 16-byte
+    aligned."""
+    params, grads, hypers = list(params16), list(grads16), list(hypers)
+    ws, ms, vs = list(masters), list(exp_avgs), list(exp_avg_sqs)
+    if not (len(params) == len(grads) == len(ws) == len(ms) == len(vs) == len(hypers)):
+        raise ValueError("adam_master_update_batch_: one grad, master, exp_avg, exp_avg_sq and "
+                         "hyper per param segment")
+    if not params:
+        return params
+    _check_dev(params + grads + ws + ms + vs)
+    if params[0].dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("adam_master_update_batch_: bf16 or f16 parameters")
+    for p, g, w, m, v in zip(params, grads, ws, ms, vs):
+        if p.dtype != params[0].dtype or g.dtype != p.dtype or g.numel() != p.numel() or \
+                any(x.numel() != p.numel() or x.dtype != torch.float32 for x in (w, m, v)):
+            raise ValueError("adam_master_update_batch_: shape/dtype mismatch")
+    lib = _lib.load()
+    cnt = (ctypes.c_size_t * len(params))(*[p.numel() for p in params])
+    rc = lib.kf_adam_master_update_batch(
+        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (params, grads, ws, ms, vs)],
+        cnt, len(params), int(kungfu_dtype(params[0])), int(np_),
+        _lib.adam_hyper_array(hypers), _stream(stream, params[0].device))
+    _lib.check(rc, "kf_adam_master_update_batch", source="")
+    return params
+
+
 _NORM_DTYPES = (torch.float32, torch.float16, torch.bfloat16, torch.float64)
 
 

@@ -697,11 +697,12 @@ class _Sharded(_Bucketed):
                 G.update(self._kf_new_group())
                 self._kf_groups.append(G)
 
-    def _kf_zero_shards(self, G):
-        """One zeroed state shard per bucket of the group."""
+    def _kf_zero_shards(self, G, dtype=None):
+        """One zeroed state shard per bucket of the group, of the buckets'
+        dtype or of `dtype`."""
         import torch
         world = self._kf_ex.world
-        return [torch.zeros(b.numel() // world, dtype=b.dtype, device=b.device)
+        return [torch.zeros(b.numel() // world, dtype=dtype or b.dtype, device=b.device)
                 for b in G["pb"].buckets]
 
     def _kf_closure(self, closure):
@@ -755,7 +756,7 @@ class _Sharded(_Bucketed):
         import torch
         ex = self._kf_ex
         for b, m in zip(G["pb"].buckets, shards):
-            full = torch.zeros_like(b)
+            full = torch.zeros(b.numel(), dtype=m.dtype, device=b.device)
             lo, hi = b.data_ptr(), b.data_ptr() + b.numel() * b.element_size()
             for p, v in zip(G["ps"], G["pb"].views):
                 t = tensor_of(p) if lo <= v.data_ptr() < hi and p.numel() else None
@@ -836,21 +837,39 @@ class _ShardedSGD(_Sharded):
 class _ShardedAdam(_Sharded):
     """reduce-scatter(grads) -> Adam / AdamW update on the own shard ->
     all-gather(params). exp_avg and exp_avg_sq are one shard each per bucket;
-    one step counter per bucket group."""
+    one step counter per bucket group. With master weights a bf16 / f16 group
+    has a third shard per bucket, "w", the fp32 master copy of this rank's
+    slice of the parameters, and its exp_avg / exp_avg_sq shards are fp32."""
 
     _kf_name = "ShardedAdamOptimizer"
     _kf_dtypes = ("float32", "bfloat16", "float64")
     _kf_dtype_words = "f32, bf16 and f64"
     _kf_decoupled = False
+    _kf_master = False
 
     def _kf_new_group(self):
-        return {"m": None, "v": None, "step": 0}
+        return {"m": None, "v": None, "w": None, "step": 0}
+
+    def _kf_build_sharded(self):
+        import torch
+        super()._kf_build_sharded()
+        if not self._kf_master:
+            return
+        ex = self._kf_ex
+        for G in self._kf_groups:
+            if G["pb"].buckets and G["pb"].buckets[0].element_size() == 2:
+                G["w"] = self._kf_zero_shards(G, torch.float32)
+                for b, w in zip(G["pb"].buckets, G["w"]):  # the widening is exact
+                    q = w.numel()
+                    w.copy_(b[ex.rank * q:(ex.rank + 1) * q])
 
     def _kf_states(self, G):
         """The group's zeroed exp_avg / exp_avg_sq shards, allocated on the
-        first step."""
+        first step (fp32 where the group has master weights)."""
         if G["m"] is None:
-            G["m"], G["v"] = self._kf_zero_shards(G), self._kf_zero_shards(G)
+            import torch
+            dtype = torch.float32 if G["w"] is not None else None
+            G["m"], G["v"] = self._kf_zero_shards(G, dtype), self._kf_zero_shards(G, dtype)
         return G["m"], G["v"]
 
     def step(self, closure=None):
@@ -867,7 +886,11 @@ class _ShardedAdam(_Sharded):
                  "eps": float(pg["eps"]), "weight_decay": float(pg["weight_decay"]),
                  "decoupled": self._kf_decoupled, "step": G["step"]}
             nb = len(G["pb"].buckets)
-            self._kf_ex.adam_step_(G["pb"].buckets, G["gb"].buckets, ms, vs, [h] * nb)
+            if G["w"] is not None:
+                self._kf_ex.adam_master_step_(G["pb"].buckets, G["gb"].buckets, G["w"], ms, vs,
+                                              [h] * nb)
+            else:
+                self._kf_ex.adam_step_(G["pb"].buckets, G["gb"].buckets, ms, vs, [h] * nb)
         _finish(self._kf_ex)
         return loss
 
@@ -876,7 +899,9 @@ class _ShardedAdam(_Sharded):
         "exp_avg_sq": tensor}}, the full state tensors gathered from the
         ranks' shards (new tensors; empty for a group that has not stepped).
         With load_state_buffers, the checkpoint path: `state` stays empty, so
-        state_dict() carries no Adam state."""
+        state_dict() carries no Adam state. A bf16 / f16 group with master
+        weights gives fp32 exp_avg and exp_avg_sq and a third entry, "master",
+        the fp32 master copy of the parameter."""
         out = {}
         for G in self._kf_groups or []:
             if G["m"] is None or G["step"] == 0:
@@ -884,6 +909,9 @@ class _ShardedAdam(_Sharded):
             m, v = self._kf_unshard(G, G["m"]), self._kf_unshard(G, G["v"])
             for p in m:
                 out[p] = {"step": G["step"], "exp_avg": m[p], "exp_avg_sq": v[p]}
+            if G["w"] is not None:
+                for p, w in self._kf_unshard(G, G["w"]).items():
+                    out[p]["master"] = w
         _finish(self._kf_ex)
         return out
 
@@ -893,7 +921,13 @@ class _ShardedAdam(_Sharded):
         bucket, and the group goes on from `step`. A group none of whose
         parameters is in `mapping` is left as it is; a parameter missing from
         a loaded group gets zeros. The parameters of one group must agree on
-        `step` (ValueError otherwise)."""
+        `step` (ValueError otherwise). In a group with master weights a
+        parameter's "master" entry becomes its master copy; where the entry
+        (or the parameter) is absent, the master is the current 16-bit
+        parameter widened again, which drops what the master held below the
+        16-bit precision. The parameters themselves are not touched: the
+        caller restores them as usual, and the next step rewrites them from
+        the master."""
         if self._kf_groups is None:
             self._kf_build_sharded()
         for G in self._kf_groups:
@@ -906,6 +940,8 @@ class _ShardedAdam(_Sharded):
             ms, vs = self._kf_states(G)
             self._kf_reshard(G, ms, lambda p: mapping[p]["exp_avg"] if p in mapping else None)
             self._kf_reshard(G, vs, lambda p: mapping[p]["exp_avg_sq"] if p in mapping else None)
+            if G["w"] is not None:
+                self._kf_reshard(G, G["w"], lambda p: mapping.get(p, {}).get("master", p.data))
             G["step"] = steps.pop()
 
 
@@ -956,7 +992,8 @@ def ShardedSGDOptimizer(optimizer, named_parameters=None, exchange=None, bucket_
     return opt
 
 
-def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20):
+def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20,
+                         master_weights=False):
     """Synchronous Adam / AdamW with the optimizer update and its state
     sharded over the ranks, as ShardedSGDOptimizer does for SGD: every step is
 
@@ -989,7 +1026,26 @@ def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket
         lerp: the results differ from torch's in the last bits;
       * no f16 parameters (TypeError on the first step): eps = 1e-8 rounds
         to 0 in f16, so every element with exp_avg_sq == 0 would be 0 / 0.
-        The state has the parameters' dtype (f32, bf16 or f64).
+        The state has the parameters' dtype (f32, bf16 or f64). Both hold
+        without master_weights; see below.
+
+    master_weights=True: every bf16 or f16 bucket group keeps
+    an fp32 master copy of this rank's shard of the parameters and fp32
+    exp_avg / exp_avg_sq shards, 12 / world bytes of state per element and
+    rank. The master is taken from the parameters when the buckets are built
+    (the widening is exact). The 16-bit parameters and gradients travel as
+    before; the update (the exchange's `adam_master_step_`,
+    ops.adam_master_update_batch_) widens the gradient, runs the f32
+    arithmetic on the master and the state, and writes the parameters as the
+    master narrowed, round-to-nearest-even: after every step() each 16-bit
+    parameter equals the narrowing of its master on every rank, and no other
+    rounding to 16 bits happens (kf_adam_master_update_batch). Updates below
+    half a 16-bit ulp accumulate in the master instead of being rounded away.
+    f16 parameters are accepted; there is no loss scaling, no inf / NaN step
+    skipping and no gradient clipping here, so f16 users must keep their
+    gradients finite themselves. f32 and f64 groups take the path above and
+    give the same bits as without the flag. state_buffers() carries the
+    master as a third entry, "master".
 
     state_buffers() (collective) and load_state_buffers(mapping) are the
     checkpoint path for the sharded state.
@@ -1014,4 +1070,11 @@ def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket
     if not hasattr(opt._kf_ex, "adam_step_"):
         raise ValueError("ShardedAdamOptimizer needs an exchange with adam_step_() "
                          "(collective.Exchange or exchange.NativeExchange)")
+    if master_weights:
+        if not hasattr(opt._kf_ex, "adam_master_step_"):
+            raise ValueError("ShardedAdamOptimizer(master_weights=True) needs an exchange with "
+                             "adam_master_step_() (collective.Exchange or exchange.NativeExchange)")
+        opt._kf_master = True
+        opt._kf_dtypes = ("float32", "float16", "bfloat16", "float64")
+        opt._kf_dtype_words = "f32, f16, bf16 and f64"
     return opt

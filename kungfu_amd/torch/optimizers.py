@@ -73,5 +73,7 @@ def ShardedSGDOptimizer(optimizer, named_parameters, **kwargs):
 
 def ShardedAdamOptimizer(optimizer, named_parameters, **kwargs):
     """kungfu_amd.optimizers.ShardedAdamOptimizer with `named_parameters`
-    positional."""
+    positional. Keywords pass through: `exchange`, `bucket_bytes`, and
+    `master_weights=True` for fp32 master weights and fp32 state on the shard
+    of bf16 / f16 parameters."""
     return _opt.ShardedAdamOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
