@@ -346,53 +346,10 @@ class Exchange:
         numel // world elements (None where hypers[b]'s momentum is 0). The
         gradient buckets are only read here; callers must not rely on that
         (the native exchange uses them as scratch)."""
-        params, grads = list(param_buckets), list(grad_buckets)
-        moms = [None] * len(params) if mom_shards is None else list(mom_shards)
-        hypers = list(hypers)
-        if not (len(params) == len(grads) == len(moms) == len(hypers)):
-            raise ValueError("sgd_step_: one grad bucket, momentum shard and hyper per bucket")
-        for p, g, m in zip(params, grads, moms):
-            self._check(p)
-            self._check(g)
-            if g.numel() != p.numel() or g.dtype != p.dtype or \
-                    (m is not None and m.numel() * self.world != p.numel()):
-                raise ValueError("sgd_step_: bucket / shard sizes do not match")
-        if not params:
-            return params
-        if self.world == 1:
-            self.epilogue.sgd_update_(params, grads, moms, hypers, 1)
-            return params
-        marks = self._marks()
-        works = []
-        for i, g in enumerate(grads):
-            shard = self._workspace(("sgd", "rs", i), g.numel() // self.world, g)
-            works.append((shard, self._scatter(g, shard, OP.SUM, ("sgd", "a2a", i))))
-        # one update launch over all shards: the / world is the fold's where
-        # the shards were folded here, the update's own after a reduce-scatter
-        sets = {0: ([], [], [], []), self.world: ([], [], [], [])}
-        for _, (w, _) in works:
-            w.wait()
-        self._mark(marks, "reduce_scatter")
-        for p, m, h, (shard, (w, recv)) in zip(params, moms, hypers, works):
-            if recv is not None:
-                self.epilogue.fold_(list(recv.chunk(self.world)), shard, OP.SUM, self.world)
-            q = shard.numel()
-            dst = sets[0 if recv is not None else self.world]
-            for lst, x in zip(dst, (p[self.rank * q:(self.rank + 1) * q], shard, m, h)):
-                lst.append(x)
-        for np_, (ps, gs, ms, hs) in sets.items():
-            if ps:
-                self.epilogue.sgd_update_(ps, gs, ms, hs, np_)
-        self._mark(marks, "epilogue")
-        gathers = []
-        for p in params:
-            q = p.numel() // self.world
-            gathers.append(dist.all_gather_into_tensor(p, p[self.rank * q:(self.rank + 1) * q],
-                                                       group=self.group, async_op=True))
-        for w in gathers:
-            w.wait()
-        self._mark(marks, "all_gather")
-        return params
+        params = list(param_buckets)
+        moms = [None] * len(params) if mom_shards is None else mom_shards
+        return self._shard_schedule("sgd_step_", "sgd", params, grad_buckets, (moms,),
+                                    hypers, self.epilogue.sgd_update_)
 
     def adam_step_(self, param_buckets, grad_buckets, exp_avg_shards, exp_avg_sq_shards, hypers):
         """sgd_step_ with the Adam / AdamW update on this rank's shards (the
@@ -404,9 +361,9 @@ class Exchange:
         bucket b hold numel // world elements. hypers[b] as
         ops.adam_update_batch_ takes them. The gradient buckets are only read
         here; callers must not rely on that."""
-        return self._adam_schedule("adam_step_", param_buckets, grad_buckets,
-                                   (exp_avg_shards, exp_avg_sq_shards), hypers,
-                                   self.epilogue.adam_update_)
+        return self._shard_schedule("adam_step_", "adam", param_buckets, grad_buckets,
+                                    (exp_avg_shards, exp_avg_sq_shards), hypers,
+                                    self.epilogue.adam_update_)
 
     def adam_master_step_(self, param_buckets, grad_buckets, master_shards, exp_avg_shards,
                           exp_avg_sq_shards, hypers):
@@ -416,14 +373,17 @@ class Exchange:
         runs once over the shards (16-bit parameters, summed 16-bit gradients,
         and this rank's fp32 master, exp_avg and exp_avg_sq shards of
         numel // world elements each)."""
-        return self._adam_schedule("adam_master_step_", param_buckets, grad_buckets,
-                                   (master_shards, exp_avg_shards, exp_avg_sq_shards), hypers,
-                                   self.epilogue.adam_master_update_)
+        return self._shard_schedule("adam_master_step_", "adam", param_buckets, grad_buckets,
+                                    (master_shards, exp_avg_shards, exp_avg_sq_shards), hypers,
+                                    self.epilogue.adam_master_update_)
 
-    def _adam_schedule(self, name, param_buckets, grad_buckets, state_shards, hypers, update):
-        """What adam_step_ and adam_master_step_ share: update(params, grads,
-        *states, hypers, np_) on this rank's shards between the gradients'
-        reduce-scatter and the parameters' all-gather."""
+    def _shard_schedule(self, name, key, param_buckets, grad_buckets, state_shards, hypers,
+                        update):
+        """What sgd_step_, adam_step_ and adam_master_step_ share:
+        update(params, grads, *states, hypers, np_) on this rank's shards
+        between the gradients' reduce-scatter and the parameters' all-gather.
+        A state shard may be None (SGD without momentum); `key` names the
+        workspaces."""
         params, grads, hypers = list(param_buckets), list(grad_buckets), list(hypers)
         states = [list(s) for s in state_shards]
         if not all(len(x) == len(params) for x in [grads, hypers] + states):
@@ -433,7 +393,8 @@ class Exchange:
             self._check(p)
             self._check(g)
             if g.numel() != p.numel() or g.dtype != p.dtype or \
-                    any(s[i].numel() * self.world != p.numel() for s in states):
+                    any(s[i] is not None and s[i].numel() * self.world != p.numel()
+                        for s in states):
                 raise ValueError("%s: bucket / shard sizes do not match" % name)
         if not params:
             return params
@@ -443,8 +404,8 @@ class Exchange:
         marks = self._marks()
         works = []
         for i, g in enumerate(grads):
-            shard = self._workspace(("adam", "rs", i), g.numel() // self.world, g)
-            works.append((shard, self._scatter(g, shard, OP.SUM, ("adam", "a2a", i))))
+            shard = self._workspace((key, "rs", i), g.numel() // self.world, g)
+            works.append((shard, self._scatter(g, shard, OP.SUM, (key, "a2a", i))))
         # one update launch over all shards: the / world is the fold's where
         # the shards were folded here, the update's own after a reduce-scatter
         width = 3 + len(states)

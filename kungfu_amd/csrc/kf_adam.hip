@@ -6,7 +6,8 @@
 //                             p -= step * m / (sqrt(v) / s2 + eps)] -> all-gather(params)
 //
 // One batched element-wise launch over up to kAdamSeg segments of one dtype,
-// kf_sgd.hip's shape with two state streams. Every segment has its own param /
+// kf_sgd.hip's shape with two state streams (the launch planner and the
+// segment lookup are kf_update_batch.hpp's). Every segment has its own param /
 // grad / exp_avg / exp_avg_sq pointers, its count and its scalars, all in the
 // kernarg segment (lr and the bias corrections change every step). A segment
 // reads g, p, m and v once and writes p, m and v once: 7 accesses per element.
@@ -41,6 +42,7 @@
 #include <string>
 
 #include "kf_adam_math.hpp"  // the update itself, shared with kf_adam_master.hip
+#include "kf_update_batch.hpp"
 
 // Load / store policy of the streams, 1 = non-temporal: kf_sgd.hip's measured
 // one. g is dead after this kernel; p, m and v are read and written in place.
@@ -56,8 +58,6 @@
 
 namespace kf
 {
-void set_last_error(const std::string &msg);  // kf_capi.hip: kf_last_error's text
-
 constexpr int kAdamSeg   = 24;
 constexpr int kAdamBlock = 256;
 #ifndef KF_ADAM_UNROLL
@@ -167,45 +167,18 @@ __device__ __forceinline__ void adam_body(const AdamSeg<typename SgdElt<T>::C> &
     }
 }
 
-// The segment's decay, chosen once per block: a choice inside the update would
-// be made per vector, and in the scalar tail it kept p and g in scratch.
-template <typename T, int DIV>
-__device__ __forceinline__ void adam_seg(const AdamSeg<typename SgdElt<T>::C> &h, const Div &d,
-                                         size_t blk, size_t nblk)
-{
-    if (h.decay == ADAM_NO_DECAY) adam_body<T, DIV, ADAM_NO_DECAY>(h, d, blk, nblk);
-    else if (h.decay == ADAM_L2) adam_body<T, DIV, ADAM_L2>(h, d, blk, nblk);
-    else adam_body<T, DIV, ADAM_DECOUPLED>(h, d, blk, nblk);
-}
-
 template <typename T>
 __global__ void __launch_bounds__(kAdamBlock)
     adam_update_kernel(AdamBatchArgs<typename SgdElt<T>::C> a, Div np, int div)
 {
     using C = typename SgdElt<T>::C;
-    // kf_sgd.hip's two grids: segments of about equal size are the rows of a
-    // 2-D grid; otherwise the segment of block b is the last s with
-    // blk0[s] <= b, searched in the kernarg table.
-    const bool rows = gridDim.y > 1;
-    int s           = static_cast<int>(blockIdx.y);
-    size_t blk = blockIdx.x, nblk = gridDim.x;
-    if (!rows) {
-        const unsigned b = blockIdx.x;
-        int lo = 0, hi = a.nseg - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (b >= a.blk0[mid]) lo = mid;
-            else hi = mid - 1;
-        }
-        s    = lo;
-        blk  = b - a.blk0[s];
-        nblk = a.blk0[s + 1] - a.blk0[s];
-    }
-    const AdamSeg<C> &g = a.seg[s];
-    // the /np choice made once per kernel (kf_reduce_kernels.hpp EPI_MUL)
-    if (div == 0) adam_seg<T, 0>(g, np, blk, nblk);
-    else if (div == 1) adam_seg<T, 1>(g, np, blk, nblk);
-    else adam_seg<T, 2>(g, np, blk, nblk);
+    size_t blk, nblk;  // kf_update_batch.hpp's two grids
+    const AdamSeg<C> &g = a.seg[batch_segment(a, blk, nblk)];
+    dispatch_div(div, [&](auto DIV) {
+        dispatch_decay(g.decay, [&](auto DECAY) {
+            adam_body<T, decltype(DIV)::value, decltype(DECAY)::value>(g, np, blk, nblk);
+        });
+    });
 }
 
 }  // namespace kf
@@ -214,70 +187,30 @@ namespace
 {
 using namespace kf;
 
-int fail(int rc, const char *name, const std::string &what)
-{
-    set_last_error(std::string(name) + ": kf_adam_update_batch: " + what);
-    return rc;
-}
+constexpr UpdateFail fail{"kf_adam_update_batch"};
 
 template <typename T>
 int launch_adam(void *const *params, const void *const *grads, void *const *ms, void *const *vs,
                 const size_t *counts, int nb, int np, const kf_adam_hyper *hyper, hipStream_t s)
 {
-    using C         = typename SgdElt<T>::C;
-    constexpr int N = SgdVec<T>::N;
-    const Div dv    = update_div(np);
-    const int div   = np == 0 ? 0 : (dv.pow2 ? 1 : 2);
-    AdamBatchArgs<C> a;
-    a.nseg        = 0;
-    size_t blocks = 0, widest = 0;
-    auto flush    = [&]() -> int {
-        if (a.nseg == 0) return KF_OK;
-        a.blk0[a.nseg] = static_cast<unsigned>(blocks);
-        // one row per segment when that at most doubles the grid
-        const bool rows = a.nseg > 1 && widest * a.nseg <= 2 * blocks;
-        const dim3 grid = rows ? dim3(static_cast<unsigned>(widest), a.nseg)
-                               : dim3(static_cast<unsigned>(blocks));
-        adam_update_kernel<T><<<grid, kAdamBlock, 0, s>>>(a, dv, div);
-        a.nseg = 0;
-        blocks = widest = 0;
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            return fail(KF_ERR_HIP, "KF_ERR_HIP", std::string("launch: ") + hipGetErrorString(e));
-        }
-        return KF_OK;
-    };
-    const size_t tile = static_cast<size_t>(kAdamBlock) * kAdamUnroll;
-    for (int b = 0; b < nb; ++b) {
-        const size_t n = counts[b];
-        if (n == 0) continue;
-        size_t nblk = (n / N + tile - 1) / tile;  // one block per tile
-        if (nblk < 1) nblk = 1;                   // a tail alone
-        if (nblk > 0x400000u) nblk = 0x400000u;   // then blocks stride over the tiles
-        if (blocks + nblk > 0x7fffffu) {          // grid * block stays below 2^32 threads,
-            const int rc = flush();               // also as rows (at most twice the blocks)
-            if (rc != KF_OK) return rc;
-        }
-        const kf_adam_hyper &h = hyper[b];
-        AdamSeg<C> &g          = a.seg[a.nseg];
-        g.p                    = params[b];
-        g.g                    = grads[b];
-        g.m                    = ms[b];
-        g.v                    = vs[b];
-        g.n                    = n;
-        adam_scalars<C>(g, h);
-        a.blk0[a.nseg] = static_cast<unsigned>(blocks);
-        blocks += nblk;
-        if (nblk > widest) widest = nblk;
-        if (++a.nseg == kAdamSeg) {
-            const int rc = flush();
-            if (rc != KF_OK) return rc;
-        }
-    }
-    return flush();
+    using C       = typename SgdElt<T>::C;
+    const Div dv  = update_div(np);
+    const int div = update_div_code(np, dv);
+    return plan_update_batch<AdamBatchArgs<C>>(
+        counts, nb, SgdVec<T>::N, static_cast<size_t>(kAdamBlock) * kAdamUnroll,
+        [&](AdamSeg<C> &g, int b) {
+            g.p = params[b];
+            g.g = grads[b];
+            g.m = ms[b];
+            g.v = vs[b];
+            g.n = counts[b];
+            adam_scalars<C>(g, hyper[b]);
+        },
+        [&](unsigned gx, unsigned gy, const AdamBatchArgs<C> &a) {
+            adam_update_kernel<T><<<dim3(gx, gy), kAdamBlock, 0, s>>>(a, dv, div);
+            return launch_status(fail);
+        });
 }
-
-bool off16(const void *p) { return (reinterpret_cast<uintptr_t>(p) % 16) != 0; }
 
 }  // namespace
 

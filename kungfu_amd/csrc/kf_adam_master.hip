@@ -8,7 +8,8 @@
 //
 // kf_adam.hip's shape: one batched element-wise launch over up to
 // kAdamMasterSeg segments, every segment with its own pointers, count and
-// scalars in the kernarg segment. A segment reads g (2 B) and master, m, v
+// scalars in the kernarg segment (the launch planner and the segment lookup
+// are kf_update_batch.hpp's). A segment reads g (2 B) and master, m, v
 // (12 B) and writes master, m, v (12 B) and p16 (2 B): 28 bytes per element,
 // the f32 kernel's 7 x 4. The old 16-bit parameter value is never read.
 //
@@ -30,6 +31,7 @@
 #include <string>
 
 #include "kf_adam_math.hpp"
+#include "kf_update_batch.hpp"
 
 // Load / store policy of the streams, 1 = non-temporal: kf_adam.hip's. g is
 // dead after this kernel; master, m and v are read and written in place; p16
@@ -46,8 +48,6 @@
 
 namespace kf
 {
-void set_last_error(const std::string &msg);  // kf_capi.hip: kf_last_error's text
-
 constexpr int kAdamMasterSeg   = 32;
 constexpr int kAdamMasterBlock = 256;
 #ifndef KF_ADAM_MASTER_ELTS
@@ -224,43 +224,17 @@ __device__ __forceinline__ void master_body(const AdamMasterSeg &h, const Div &d
     }
 }
 
-// The segment's decay, chosen once per block (kf_adam.hip adam_seg).
-template <typename T, int DIV>
-__device__ __forceinline__ void master_seg(const AdamMasterSeg &h, const Div &d, size_t blk,
-                                           size_t nblk)
-{
-    if (h.decay == ADAM_NO_DECAY) master_body<T, DIV, ADAM_NO_DECAY>(h, d, blk, nblk);
-    else if (h.decay == ADAM_L2) master_body<T, DIV, ADAM_L2>(h, d, blk, nblk);
-    else master_body<T, DIV, ADAM_DECOUPLED>(h, d, blk, nblk);
-}
-
 template <typename T>
 __global__ void __launch_bounds__(kAdamMasterBlock)
     adam_master_kernel(AdamMasterArgs a, Div np, int div)
 {
-    // kf_adam.hip's two grids: segments of about equal size are the rows of a
-    // 2-D grid; otherwise the segment of block b is the last s with
-    // blk0[s] <= b, searched in the kernarg table.
-    const bool rows = gridDim.y > 1;
-    int s           = static_cast<int>(blockIdx.y);
-    size_t blk = blockIdx.x, nblk = gridDim.x;
-    if (!rows) {
-        const unsigned b = blockIdx.x;
-        int lo = 0, hi = a.nseg - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (b >= a.blk0[mid]) lo = mid;
-            else hi = mid - 1;
-        }
-        s    = lo;
-        blk  = b - a.blk0[s];
-        nblk = a.blk0[s + 1] - a.blk0[s];
-    }
-    const AdamMasterSeg &g = a.seg[s];
-    // the /np choice made once per kernel
-    if (div == 0) master_seg<T, 0>(g, np, blk, nblk);
-    else if (div == 1) master_seg<T, 1>(g, np, blk, nblk);
-    else master_seg<T, 2>(g, np, blk, nblk);
+    size_t blk, nblk;  // kf_update_batch.hpp's two grids
+    const AdamMasterSeg &g = a.seg[batch_segment(a, blk, nblk)];
+    dispatch_div(div, [&](auto DIV) {
+        dispatch_decay(g.decay, [&](auto DECAY) {
+            master_body<T, decltype(DIV)::value, decltype(DECAY)::value>(g, np, blk, nblk);
+        });
+    });
 }
 
 }  // namespace kf
@@ -269,70 +243,31 @@ namespace
 {
 using namespace kf;
 
-int fail(int rc, const char *name, const std::string &what)
-{
-    set_last_error(std::string(name) + ": kf_adam_master_update_batch: " + what);
-    return rc;
-}
+constexpr UpdateFail fail{"kf_adam_master_update_batch"};
 
 template <typename T>
 int launch_master(void *const *params16, const void *const *grads16, void *const *masters,
                   void *const *ms, void *const *vs, const size_t *counts, int nb, int np,
                   const kf_adam_hyper *hyper, hipStream_t s)
 {
-    constexpr int N = kAdamMasterElts;
-    const Div dv    = update_div(np);
-    const int div   = np == 0 ? 0 : (dv.pow2 ? 1 : 2);
-    AdamMasterArgs a;
-    a.nseg        = 0;
-    size_t blocks = 0, widest = 0;
-    auto flush    = [&]() -> int {
-        if (a.nseg == 0) return KF_OK;
-        a.blk0[a.nseg] = static_cast<unsigned>(blocks);
-        // one row per segment when that at most doubles the grid
-        const bool rows = a.nseg > 1 && widest * a.nseg <= 2 * blocks;
-        const dim3 grid = rows ? dim3(static_cast<unsigned>(widest), a.nseg)
-                               : dim3(static_cast<unsigned>(blocks));
-        adam_master_kernel<T><<<grid, kAdamMasterBlock, 0, s>>>(a, dv, div);
-        a.nseg = 0;
-        blocks = widest = 0;
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            return fail(KF_ERR_HIP, "KF_ERR_HIP", std::string("launch: ") + hipGetErrorString(e));
-        }
-        return KF_OK;
-    };
-    const size_t tile = static_cast<size_t>(kAdamMasterBlock) * kAdamMasterUnroll;
-    for (int b = 0; b < nb; ++b) {
-        const size_t n = counts[b];
-        if (n == 0) continue;
-        size_t nblk = (n / N + tile - 1) / tile;  // one block per tile
-        if (nblk < 1) nblk = 1;                   // a tail alone
-        if (nblk > 0x400000u) nblk = 0x400000u;   // then blocks stride over the tiles
-        if (blocks + nblk > 0x7fffffu) {          // grid * block stays below 2^32 threads,
-            const int rc = flush();               // also as rows (at most twice the blocks)
-            if (rc != KF_OK) return rc;
-        }
-        AdamMasterSeg &g = a.seg[a.nseg];
-        g.p16            = params16[b];
-        g.g              = grads16[b];
-        g.p              = masters[b];
-        g.m              = ms[b];
-        g.v              = vs[b];
-        g.n              = n;
-        adam_scalars<float>(g, hyper[b]);
-        a.blk0[a.nseg] = static_cast<unsigned>(blocks);
-        blocks += nblk;
-        if (nblk > widest) widest = nblk;
-        if (++a.nseg == kAdamMasterSeg) {
-            const int rc = flush();
-            if (rc != KF_OK) return rc;
-        }
-    }
-    return flush();
+    const Div dv  = update_div(np);
+    const int div = update_div_code(np, dv);
+    return plan_update_batch<AdamMasterArgs>(
+        counts, nb, kAdamMasterElts, static_cast<size_t>(kAdamMasterBlock) * kAdamMasterUnroll,
+        [&](AdamMasterSeg &g, int b) {
+            g.p16 = params16[b];
+            g.g   = grads16[b];
+            g.p   = masters[b];
+            g.m   = ms[b];
+            g.v   = vs[b];
+            g.n   = counts[b];
+            adam_scalars<float>(g, hyper[b]);
+        },
+        [&](unsigned gx, unsigned gy, const AdamMasterArgs &a) {
+            adam_master_kernel<T><<<dim3(gx, gy), kAdamMasterBlock, 0, s>>>(a, dv, div);
+            return launch_status(fail);
+        });
 }
-
-bool off16(const void *p) { return (reinterpret_cast<uintptr_t>(p) % 16) != 0; }
 
 }  // namespace
 

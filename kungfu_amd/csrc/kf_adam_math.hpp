@@ -78,6 +78,16 @@ __device__ __forceinline__ void adam_math(V (&p)[H], V (&g)[H], V (&m)[H], V (&v
     }
 }
 
+// The segment's decay, chosen once per block: a choice inside the update would
+// be made per vector, and in the scalar tail it kept p and g in scratch.
+// f(std::integral_constant<int, DECAY>).
+template <typename F> __device__ __forceinline__ void dispatch_decay(int decay, F &&f)
+{
+    if (decay == ADAM_NO_DECAY) f(std::integral_constant<int, ADAM_NO_DECAY>{});
+    else if (decay == ADAM_L2) f(std::integral_constant<int, ADAM_L2>{});
+    else f(std::integral_constant<int, ADAM_DECOUPLED>{});
+}
+
 // The scalars of a kernarg entry from the caller's hyperparameters: computed
 // in double, cast once to the compute type C.
 template <typename C, typename SEG> inline void adam_scalars(SEG &g, const kf_adam_hyper &h)

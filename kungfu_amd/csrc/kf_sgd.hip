@@ -30,7 +30,8 @@
 // Shape: kf_reduce_kernels.hpp's batched kernels. One 256-thread block per
 // tile of 4 x 256 16-B vectors; all of a tile's loads (up to 12 per lane) are
 // issued before the arithmetic. Segments of about equal size are the rows of
-// a 2-D grid, others share a 1-D grid through a search table. Every pointer
+// a 2-D grid, others share a 1-D grid through a search table
+// (kf_update_batch.hpp's planner, which the Adam kernels use too). Every pointer
 // is 16-byte aligned (the host checks it), so a segment is whole vectors and
 // a scalar tail of fewer than 16 bytes; there is no head.
 #include <hip/hip_runtime.h>
@@ -38,7 +39,7 @@
 #include <string>
 
 #include "kf_sgd_elt.hpp"
-#include "kungfu_amd.h"
+#include "kf_update_batch.hpp"
 
 // Load / store policy of the streams, 1 = non-temporal. g is dead after this
 // kernel and is read non-temporally; p and m are read and then written in
@@ -62,8 +63,6 @@
 
 namespace kf
 {
-void set_last_error(const std::string &msg);  // kf_capi.hip: kf_last_error's text
-
 constexpr int kSgdSeg    = 32;
 constexpr int kSgdBlock  = 256;
 #ifndef KF_SGD_UNROLL
@@ -225,12 +224,9 @@ __global__ void __launch_bounds__(kSgdBlock)
     sgd_update_kernel(SgdBatchArgs<typename SgdElt<T>::C> a, Div np, int div)
 {
     using C = typename SgdElt<T>::C;
-    // Segments of about equal size (an exchange's shards of equal buckets)
-    // come as a 2-D grid, one row per segment: the segment is blockIdx.y,
-    // known before any kernarg load, and a row's blocks past the segment's
-    // last tile have nothing to do. Otherwise the segment of block b is the
-    // last s with blk0[s] <= b, searched in the kernarg table (wave-uniform
-    // scalar loads, one dependent load per step).
+    // kf_update_batch.hpp's batch_segment and, below, its dispatch_div, both
+    // written out: through the helpers this kernel's code does not stay the
+    // same (the Adam kernels' does).
     const bool rows = gridDim.y > 1;
     int s           = static_cast<int>(blockIdx.y);
     size_t blk = blockIdx.x, nblk = gridDim.x;
@@ -267,74 +263,35 @@ namespace
 {
 using namespace kf;
 
-int fail(int rc, const char *name, const std::string &what)
-{
-    set_last_error(std::string(name) + ": kf_sgd_update_batch: " + what);
-    return rc;
-}
+constexpr UpdateFail fail{"kf_sgd_update_batch"};
 
 template <typename T>
 int launch_sgd(void *const *params, const void *const *grads, void *const *moms,
                const size_t *counts, int nb, int np, const kf_sgd_hyper *hyper, hipStream_t s)
 {
-    using C         = typename SgdElt<T>::C;
-    constexpr int N = SgdVec<T>::N;
+    using C       = typename SgdElt<T>::C;
     const Div dv  = update_div(np);
-    const int div = np == 0 ? 0 : (dv.pow2 ? 1 : 2);
-    SgdBatchArgs<C> a;
-    a.nseg          = 0;
-    size_t blocks   = 0, widest = 0;
-    auto flush      = [&]() -> int {
-        if (a.nseg == 0) return KF_OK;
-        a.blk0[a.nseg] = static_cast<unsigned>(blocks);
-        // one row per segment when that at most doubles the grid
-        const bool rows = a.nseg > 1 && widest * a.nseg <= 2 * blocks;
-        const dim3 grid = rows ? dim3(static_cast<unsigned>(widest), a.nseg)
-                               : dim3(static_cast<unsigned>(blocks));
-        sgd_update_kernel<T><<<grid, kSgdBlock, 0, s>>>(a, dv, div);
-        a.nseg = 0;
-        blocks = widest = 0;
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            return fail(KF_ERR_HIP, "KF_ERR_HIP", std::string("launch: ") + hipGetErrorString(e));
-        }
-        return KF_OK;
-    };
-    const size_t tile = static_cast<size_t>(kSgdBlock) * kSgdUnroll;
-    for (int b = 0; b < nb; ++b) {
-        const size_t n = counts[b];
-        if (n == 0) continue;
-        size_t nblk = (n / N + tile - 1) / tile;  // one block per tile
-        if (nblk < 1) nblk = 1;                   // a tail alone
-        if (nblk > 0x400000u) nblk = 0x400000u;   // then blocks stride over the tiles
-        if (blocks + nblk > 0x7fffffu) {          // grid * block stays below 2^32 threads,
-            const int rc = flush();               // also as rows (at most twice the blocks)
-            if (rc != KF_OK) return rc;
-        }
-        const kf_sgd_hyper &h = hyper[b];
-        SgdSeg<C> &g          = a.seg[a.nseg];
-        g.p                   = params[b];
-        g.g                   = grads[b];
-        g.m                   = h.momentum != 0 ? moms[b] : nullptr;
-        g.n                   = n;
-        // computed in double, cast once to the compute type
-        g.nlr   = static_cast<C>(-h.lr);
-        g.mu    = static_cast<C>(h.momentum);
-        g.c     = static_cast<C>(1.0 - h.dampening);
-        g.wd    = static_cast<C>(h.weight_decay);
-        g.flags = (h.nesterov ? SGD_NESTEROV : 0) | (h.first ? SGD_FIRST : 0);
-        a.blk0[a.nseg] = static_cast<unsigned>(blocks);
-        blocks += nblk;
-        if (nblk > widest) widest = nblk;
-        if (++a.nseg == kSgdSeg) {
-            const int rc = flush();
-            if (rc != KF_OK) return rc;
-        }
-    }
-    return flush();
+    const int div = update_div_code(np, dv);
+    return plan_update_batch<SgdBatchArgs<C>>(
+        counts, nb, SgdVec<T>::N, static_cast<size_t>(kSgdBlock) * kSgdUnroll,
+        [&](SgdSeg<C> &g, int b) {
+            const kf_sgd_hyper &h = hyper[b];
+            g.p                   = params[b];
+            g.g                   = grads[b];
+            g.m                   = h.momentum != 0 ? moms[b] : nullptr;
+            g.n                   = counts[b];
+            // computed in double, cast once to the compute type
+            g.nlr   = static_cast<C>(-h.lr);
+            g.mu    = static_cast<C>(h.momentum);
+            g.c     = static_cast<C>(1.0 - h.dampening);
+            g.wd    = static_cast<C>(h.weight_decay);
+            g.flags = (h.nesterov ? SGD_NESTEROV : 0) | (h.first ? SGD_FIRST : 0);
+        },
+        [&](unsigned gx, unsigned gy, const SgdBatchArgs<C> &a) {
+            sgd_update_kernel<T><<<dim3(gx, gy), kSgdBlock, 0, s>>>(a, dv, div);
+            return launch_status(fail);
+        });
 }
-
-bool off16(const void *p) { return (reinterpret_cast<uintptr_t>(p) % 16) != 0; }
 
 }  // namespace
 

@@ -148,5 +148,7 @@ inline Div update_div(int np)
     dv.di   = np > 0 ? 1.0 / dv.d : 0.0;
     return dv;
 }
+// the kernels' `div` argument that goes with it: SgdDiv's DIV
+inline int update_div_code(int np, const Div &dv) { return np == 0 ? 0 : (dv.pow2 ? 1 : 2); }
 
 }  // namespace kf

@@ -257,27 +257,11 @@ class NativeExchange:
         the current stream. mom_shards[b] holds numel // world elements (None
         where hypers[b]'s momentum is 0). The gradient buckets are scratch:
         they hold nothing defined afterwards."""
-        params, grads = list(param_buckets), list(grad_buckets)
-        moms = [None] * len(params) if mom_shards is None else list(mom_shards)
-        hypers = list(hypers)
-        if not (len(params) == len(grads) == len(moms) == len(hypers)):
-            raise ValueError("sgd_step_: one grad bucket, momentum shard and hyper per bucket")
-        if not params:
-            return params
-        self._check(params + grads + [m for m in moms if m is not None])
-        for p, g, m in zip(params, grads, moms):
-            if g.numel() != p.numel() or \
-                    (m is not None and m.numel() * self.world != p.numel()):
-                raise ValueError("sgd_step_: bucket / shard sizes do not match")
-        rc = self.lib.kf_exchange_sgd_batch(
-            self._h, _lib.ptr_array([p.data_ptr() for p in params]),
-            _lib.ptr_array([g.data_ptr() for g in grads]),
-            _lib.ptr_array([0 if m is None else m.data_ptr() for m in moms]),
-            _arr(ctypes.c_size_t, [p.numel() for p in params]), len(params),
-            int(kungfu_dtype(params[0])), _lib.sgd_hyper_array(hypers), ALGOS[self.algo],
-            torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(rc, "kf_exchange_sgd_batch")
-        return params
+        params = list(param_buckets)
+        moms = [None] * len(params) if mom_shards is None else mom_shards
+        return self._shard_call("sgd_step_", self.lib.kf_exchange_sgd_batch,
+                                "kf_exchange_sgd_batch", _lib.sgd_hyper_array, params,
+                                grad_buckets, (moms,), hypers)
 
     def adam_step_(self, param_buckets, grad_buckets, exp_avg_shards, exp_avg_sq_shards, hypers):
         """sgd_step_ with the Adam / AdamW update on this rank's shards
@@ -288,9 +272,9 @@ class NativeExchange:
         numel // world elements of the parameters' dtype (f32, bf16 or f64).
         The gradient buckets are scratch: they hold nothing defined
         afterwards."""
-        return self._adam_call("adam_step_", self.lib.kf_exchange_adam_batch,
-                               "kf_exchange_adam_batch", param_buckets, grad_buckets,
-                               (exp_avg_shards, exp_avg_sq_shards), hypers)
+        return self._shard_call("adam_step_", self.lib.kf_exchange_adam_batch,
+                                "kf_exchange_adam_batch", _lib.adam_hyper_array, param_buckets,
+                                grad_buckets, (exp_avg_shards, exp_avg_sq_shards), hypers)
 
     def adam_master_step_(self, param_buckets, grad_buckets, master_shards, exp_avg_shards,
                           exp_avg_sq_shards, hypers):
@@ -300,11 +284,17 @@ class NativeExchange:
         on this rank's shard of every bucket with its fp32 master, exp_avg and
         exp_avg_sq shards of numel // world elements each. The gradient
         buckets are scratch."""
-        return self._adam_call("adam_master_step_", self.lib.kf_exchange_adam_master_batch,
-                               "kf_exchange_adam_master_batch", param_buckets, grad_buckets,
-                               (master_shards, exp_avg_shards, exp_avg_sq_shards), hypers)
+        return self._shard_call("adam_master_step_", self.lib.kf_exchange_adam_master_batch,
+                                "kf_exchange_adam_master_batch", _lib.adam_hyper_array,
+                                param_buckets, grad_buckets,
+                                (master_shards, exp_avg_shards, exp_avg_sq_shards), hypers)
 
-    def _adam_call(self, name, fn, cname, param_buckets, grad_buckets, state_shards, hypers):
+    def _shard_call(self, name, fn, cname, hyper_array, param_buckets, grad_buckets,
+                    state_shards, hypers):
+        """What sgd_step_, adam_step_ and adam_master_step_ share: the checks
+        and the call of fn (cname) with the buckets', the state shards' and
+        hyper_array(hypers)'s tables. A state shard may be None (SGD without
+        momentum): a null pointer."""
         params, grads, hypers = list(param_buckets), list(grad_buckets), list(hypers)
         states = [list(s) for s in state_shards]
         if not all(len(x) == len(params) for x in [grads, hypers] + states):
@@ -312,7 +302,7 @@ class NativeExchange:
                              % (name, len(states)))
         if not params:
             return params
-        flat = [t for s in states for t in s]
+        flat = [t for s in states for t in s if t is not None]
         if len(states) == 3:  # master weights: fp32 shards beside 16-bit buckets
             self._check(params + grads)
             self._check(flat)
@@ -323,13 +313,14 @@ class NativeExchange:
             self._check(params + grads + flat)
         for i, (p, g) in enumerate(zip(params, grads)):
             if g.numel() != p.numel() or \
-                    any(s[i].numel() * self.world != p.numel() for s in states):
+                    any(s[i] is not None and s[i].numel() * self.world != p.numel()
+                        for s in states):
                 raise ValueError("%s: bucket / shard sizes do not match" % name)
         rc = fn(self._h, _lib.ptr_array([p.data_ptr() for p in params]),
                 _lib.ptr_array([g.data_ptr() for g in grads]),
-                *[_lib.ptr_array([t.data_ptr() for t in s]) for s in states],
+                *[_lib.ptr_array([0 if t is None else t.data_ptr() for t in s]) for s in states],
                 _arr(ctypes.c_size_t, [p.numel() for p in params]), len(params),
-                int(kungfu_dtype(params[0])), _lib.adam_hyper_array(hypers), ALGOS[self.algo],
+                int(kungfu_dtype(params[0])), hyper_array(hypers), ALGOS[self.algo],
                 torch.cuda.current_stream(self.device).cuda_stream)
         _lib.check(rc, cname)
         return params

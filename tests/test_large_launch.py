@@ -76,7 +76,10 @@ def test_sgd_constants_pinned():
     assert _int(sgd, r"constexpr int kSgdSeg\s*=\s*(\d+);") == ll.SGD_SEG == 32
     assert _int(sgd, r"constexpr int kSgdBlock\s*=\s*(\d+);") == ll.BLOCK
     assert _int(sgd, r"#define KF_SGD_UNROLL (\d+)") == ll.SGD_UNROLL == 4
-    assert "const bool rows = a.nseg > 1 && widest * a.nseg <= 2 * blocks;" in sgd
+    # the grid rule is the shared planner's (tests/test_update_plan.py runs it)
+    assert '#include "kf_update_batch.hpp"' in sgd and "plan_update_batch<SgdBatchArgs<C>>(" in sgd
+    assert "const bool rows = a.nseg > 1 && widest * a.nseg <= 2 * blocks;" in \
+        _src("kf_update_batch.hpp")
 
 
 # ---- 2. the reduce family's shapes -------------------------------------------------

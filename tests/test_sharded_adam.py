@@ -169,7 +169,10 @@ def test_launch_constants_pinned():
     assert int(re.search(r"constexpr int kAdamSeg\s*=\s*(\d+);", src).group(1)) == ADAM_SEG
     assert int(re.search(r"constexpr int kAdamBlock\s*=\s*(\d+);", src).group(1)) == BLOCK
     assert int(re.search(r"#define KF_ADAM_UNROLL (\d+)", src).group(1)) == UNROLL
-    assert "const bool rows = a.nseg > 1 && widest * a.nseg <= 2 * blocks;" in src
+    # the grid rule is the shared planner's (tests/test_update_plan.py runs it)
+    assert '#include "kf_update_batch.hpp"' in src and "plan_update_batch<AdamBatchArgs<C>>(" in src
+    hdr = open(os.path.join(ROOT, "kungfu_amd", "csrc", "kf_update_batch.hpp")).read()
+    assert "const bool rows = a.nseg > 1 && widest * a.nseg <= 2 * blocks;" in hdr
 
 
 # ---- C ABI argument errors (no device) --------------------------------------

@@ -194,7 +194,10 @@ def test_launch_constants_pinned():
     assert int(re.search(r"constexpr int kAdamMasterBlock\s*=\s*(\d+);", src).group(1)) == BLOCK
     assert int(re.search(r"#define KF_ADAM_MASTER_ELTS (\d+)", src).group(1)) == ELTS
     assert "#define KF_ADAM_MASTER_UNROLL (16 / KF_ADAM_MASTER_ELTS)" in src and 16 // ELTS == UNROLL
-    assert "const bool rows = a.nseg > 1 && widest * a.nseg <= 2 * blocks;" in src
+    # the grid rule is the shared planner's (tests/test_update_plan.py runs it)
+    assert '#include "kf_update_batch.hpp"' in src and "plan_update_batch<AdamMasterArgs>(" in src
+    hdr = open(os.path.join(ROOT, "kungfu_amd", "csrc", "kf_update_batch.hpp")).read()
+    assert "const bool rows = a.nseg > 1 && widest * a.nseg <= 2 * blocks;" in hdr
     names = open(os.path.join(ROOT, "kungfu_amd", "csrc", "Makefile")).read()
     assert re.search(r"^NAMES\s*:=.*\bkf_adam_master\b", names, re.M)
 
