@@ -227,7 +227,8 @@ int kf_adam_update_batch(void *const *params, const void *const *grads, void *co
  * There is no other rounding to 16 bits anywhere, and the old value of
  * params16 is never read: the caller keeps params16 == narrow(masters). eps
  * stays fp32, so f16 parameters are taken; their gradients must be finite
- * (no loss scaling here). Segment b is counts[b] elements with its own
+ * (loss scaling and step skipping are kf_adam_master_update_batch_gated's,
+ * below). Segment b is counts[b] elements with its own
  * hyper[b]; every pointer is 16-byte aligned. g (2 bytes), master, m and v
  * are read once; master, m, v and params16 (2 bytes) written once: 28 bytes
  * per element. */
@@ -236,6 +237,102 @@ int kf_adam_master_update_batch(void *const *params16, const void *const *grads1
                                 void *const *exp_avg_sqs, const size_t *counts, int nb,
                                 KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
                                 void *stream);
+
+/* ---- the gated step: one device-side verdict per optimizer step ----------
+ *
+ * Gradient-norm clipping, loss scaling and the skipping of a step whose
+ * gradients are not finite need one global verdict between the reduce and the
+ * update. It is computed on the device (kungfu_amd/csrc/kf_step_gate.hip) and
+ * the gated update kernels read it from device memory, so the host never waits
+ * for it.
+ *
+ * The device state is two plain structs. A gate serves one optimizer; a step
+ * state serves one parameter group. Both start zero-filled, with loss_scale =
+ * the initial scale (1 without loss scaling) and beta1_pow = beta2_pow = 1. */
+typedef struct {
+    int32_t skip;       /* this step's verdict: 1 = the gradients are not finite   */
+    float grad_mul;     /* what the update multiplies g by: (float)(clip / scale)  */
+    float loss_scale;   /* fp32; after a call, the scale the NEXT loss is given    */
+    int32_t good_steps; /* applied steps since the scale last changed              */
+    double grad_norm;   /* this step's norm of the unscaled, averaged gradient     */
+    double total;       /* the sum of squares it came from (scaled gradients)      */
+    uint64_t applied;   /* steps applied so far                                    */
+    uint64_t skipped;   /* steps skipped so far                                    */
+} kf_step_gate;
+typedef struct {
+    double beta1_pow;   /* beta1^step and beta2^step as running products in double */
+    double beta2_pow;
+    int64_t step;       /* applied steps of this group                             */
+    double s2_f64;      /* sqrt(1 - beta2_pow), what the f64 kernel reads          */
+    double nss_f64;     /* -(lr / (1 - beta1_pow))                                 */
+    float s2;           /* the same two cast once to fp32: every other kernel      */
+    float nss;
+} kf_step_state;
+typedef struct { double lr, beta1, beta2; } kf_step_group;
+
+/* One verdict. sq is a device array of world * nplan doubles, sq[r * nplan +
+ * k] the sum of squares of rank r's shards of plan k (kf_segnorm_run's total);
+ * np[k] (host) is what plan k's gradients are still to be divided by: 0 when
+ * they already hold the average. groups[j] (host) and states[j] (device,
+ * contiguous) are parameter group j's. fp64 on one lane, one IEEE operation
+ * per parenthesis, correctly rounded sqrt and divisions, no atomics:
+ *   total = 0; for k in plan order:
+ *       s = 0; for r in rank order: s = s + sq[r][k]
+ *       if np[k] > 0: s = s / (np[k] * np[k])
+ *       total = total + s
+ *   skip      = !isfinite(total)
+ *   grad_norm = sqrt(total) / loss_scale
+ *   clip      = max_norm > 0 ? (x = max_norm / (grad_norm + 1e-6); x < 1 ? x : 1) : 1
+ *   grad_mul  = (float)(clip / loss_scale)
+ * with the loss_scale from before this call, the one the loss was multiplied
+ * by. A non-finite total means a non-finite gradient element somewhere (f64
+ * gradients whose squares overflow count as that). Then the loss scale, in
+ * fp32, by torch.amp.GradScaler's rule:
+ *   skip:  loss_scale = loss_scale * (float)backoff_factor; good_steps = 0
+ *   else:  ++good_steps == growth_interval: loss_scale = loss_scale *
+ *          (float)growth_factor unless that is not finite; good_steps = 0
+ *          (growth_interval 0: the scale never grows)
+ * and, only when !skip, every group:
+ *   beta1_pow = beta1_pow * beta1; beta2_pow = beta2_pow * beta2; ++step
+ *   s2_f64 = sqrt(1 - beta2_pow); nss_f64 = -(lr / (1 - beta1_pow))
+ *   s2 = (float)s2_f64; nss = (float)nss_f64
+ * A skipped step leaves every group's state as it was. The bias corrections
+ * are running products in double, not beta^step: the host does not know which
+ * steps were skipped. This is the gated path's own contract; after t applied
+ * steps the product may differ from pow(beta, t) in its last places.
+ * Any nplan >= 1, world >= 1 and ngroup >= 0: one launch for up to 64 plans
+ * and 16 groups, more launches on the same stream beyond. Only queues
+ * launches: no allocation, no host sync. max_norm <= 0 means no clipping. */
+int kf_step_gate_update(const double *sq, int world, int nplan, const int *np,
+                        const kf_step_group *groups, kf_step_state *states, int ngroup,
+                        double max_norm, double growth_factor, double backoff_factor,
+                        int growth_interval, kf_step_gate *gate, void *stream);
+
+/* kf_adam_update_batch / kf_adam_master_update_batch under a gate (kernels of
+ * their own beside the parents', kf_adam.hip / kf_adam_master.hip). They take
+ * what their parents take, except: ONE hyper for the whole call, whose
+ * bias_correction1 / bias_correction2 are ignored, and device pointers to the
+ * gate and to the segments' group's step state, both written by an earlier
+ * kf_step_gate_update on the same stream. Every block reads gate->skip; when
+ * it is set the kernel returns without touching params, params16, masters,
+ * exp_avgs or exp_avg_sqs. Otherwise s2 and nss come from *state (s2_f64 /
+ * nss_f64 for f64) in place of the parent's kernarg scalars, and exactly one
+ * operation joins the parent's sequence, directly after the /np:
+ *   g = rnd(g * grad_mul)
+ * rounded like every other operation there: to bf16 without master weights,
+ * to fp32 on the master path, to the type itself for f32 / f64. Everything
+ * else is the parent's arithmetic, operation for operation. */
+int kf_adam_update_batch_gated(void *const *params, const void *const *grads,
+                               void *const *exp_avgs, void *const *exp_avg_sqs,
+                               const size_t *counts, int nb, KungFu_Datatype dt, int np,
+                               const kf_adam_hyper *hyper, const kf_step_gate *gate,
+                               const kf_step_state *state, void *stream);
+int kf_adam_master_update_batch_gated(void *const *params16, const void *const *grads16,
+                                      void *const *masters, void *const *exp_avgs,
+                                      void *const *exp_avg_sqs, const size_t *counts, int nb,
+                                      KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
+                                      const kf_step_gate *gate, const kf_step_state *state,
+                                      void *stream);
 
 /* ---- gradient monitors: segmented squared norms ------------------------- */
 
@@ -789,6 +886,39 @@ int kf_exchange_adam_master_batch(kf_exchange_t *ex, void *const *params, void *
                                   void *const *exp_avg_sq_shards, const size_t *counts, int nb,
                                   KungFu_Datatype dt, const kf_adam_hyper *hyper, int algo,
                                   void *stream);
+/* The gated step (kf_step_gate_update above) is
+ * kf_exchange_adam_batch / kf_exchange_adam_master_batch split in two, with
+ * the verdict over ALL of an optimizer's bucket groups between the halves:
+ *   A  kf_exchange_reduce_shards_batch per group: phase 1 and the rank-order
+ *      folds. This rank's reduced shard of bucket b is left at grads[b] +
+ *      rank * q (q = counts[b] / world), and *np is what the update must
+ *      still divide by: the world after a plain reduce-scatter, 0 after the
+ *      fold or under rs_avg. World 1 on the built-in transport does nothing
+ *      and reports 1 (the whole buckets are the shards).
+ *   B  kf_segnorm_run over the shards, C  kf_exchange_all_gather_doubles,
+ *   D  kf_step_gate_update
+ *   E  kf_exchange_adam_gated_batch per group: kf_adam_update_batch_gated
+ *      (master_shards == NULL; f32, f64, bf16) or
+ *      kf_adam_master_update_batch_gated (bf16, f16) on the shards with np as
+ *      step A reported it, then phase 3, the parameters' in-place all-gather.
+ *      One hyper for the whole call, its bias corrections ignored; gate and
+ *      state are device pointers.
+ * Both halves make kf_exchange_adam_batch's up-front checks (multiples of the
+ * world, 16-byte alignment, every shard present) on every rank before any
+ * collective. Everything is queued on `stream`; un-pipelined; both follow
+ * kf_exchange_set_timing (A counts under phases 1 and 2, E under 2 and 3). */
+int kf_exchange_reduce_shards_batch(kf_exchange_t *ex, void *const *grads, const size_t *counts,
+                                    int nb, KungFu_Datatype dt, int algo, int *np, void *stream);
+int kf_exchange_adam_gated_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
+                                 void *const *master_shards, void *const *exp_avg_shards,
+                                 void *const *exp_avg_sq_shards, const size_t *counts, int nb,
+                                 KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
+                                 const kf_step_gate *gate, const kf_step_state *state, void *stream);
+/* recv[r * n + k] = rank r's send[k], k < n: the transport's byte all_gather
+ * of n doubles per rank (device pointers; send may be recv + rank * n). World
+ * 1 on the built-in transport is a copy. */
+int kf_exchange_all_gather_doubles(kf_exchange_t *ex, const double *send, double *recv, int n,
+                                   void *stream);
 /* Pipelined schedule for the batch calls (default 1 = off): the buckets of a
  * call are split into `groups` groups of consecutive buckets of about equal
  * bytes; the RCCL phases stay on the caller's stream in the same order on

@@ -123,6 +123,12 @@ EXPORTED = (
     "kf_exchange_adam_batch",
     "kf_adam_master_update_batch",
     "kf_exchange_adam_master_batch",
+    "kf_step_gate_update",
+    "kf_adam_update_batch_gated",
+    "kf_adam_master_update_batch_gated",
+    "kf_exchange_reduce_shards_batch",
+    "kf_exchange_adam_gated_batch",
+    "kf_exchange_all_gather_doubles",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -186,6 +192,48 @@ def adam_hyper_array(hypers):
         a.bias_correction1, a.bias_correction2 = 1.0 - b1 ** t, 1.0 - b2 ** t
         a.decoupled = int(bool(h.get("decoupled", False)))
     return arr
+
+
+class StepGate(ctypes.Structure):
+    """kf_step_gate (include/kungfu_amd.h): one optimizer's gate on the device."""
+    _fields_ = [("skip", ctypes.c_int32), ("grad_mul", ctypes.c_float),
+                ("loss_scale", ctypes.c_float), ("good_steps", ctypes.c_int32),
+                ("grad_norm", ctypes.c_double), ("total", ctypes.c_double),
+                ("applied", ctypes.c_uint64), ("skipped", ctypes.c_uint64)]
+
+
+class StepState(ctypes.Structure):
+    """kf_step_state (include/kungfu_amd.h): one parameter group's step state."""
+    _fields_ = [("beta1_pow", ctypes.c_double), ("beta2_pow", ctypes.c_double),
+                ("step", ctypes.c_int64), ("s2_f64", ctypes.c_double),
+                ("nss_f64", ctypes.c_double), ("s2", ctypes.c_float), ("nss", ctypes.c_float)]
+
+
+class StepGroup(ctypes.Structure):
+    """kf_step_group (include/kungfu_amd.h): what the gate needs of a group."""
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double)]
+
+
+def _np_dtype(struct):
+    import numpy as np
+    kinds = {ctypes.c_int32: "<i4", ctypes.c_float: "<f4", ctypes.c_double: "<f8",
+             ctypes.c_int64: "<i8", ctypes.c_uint64: "<u8"}
+    dt = np.dtype({"names": [n for n, _ in struct._fields_],
+                   "formats": [kinds[t] for _, t in struct._fields_],
+                   "offsets": [getattr(struct, n).offset for n, _ in struct._fields_],
+                   "itemsize": ctypes.sizeof(struct)})
+    return dt
+
+
+def step_gate_dtype():
+    """numpy's view of a kf_step_gate: the device state is bytes in a uint8
+    tensor; `tensor.cpu().numpy().view(step_gate_dtype())` reads it."""
+    return _np_dtype(StepGate)
+
+
+def step_state_dtype():
+    """numpy's view of a kf_step_state[]."""
+    return _np_dtype(StepState)
 
 
 # kf_done_fn: void (*)(int status, void *arg)
@@ -472,6 +520,29 @@ def load():
                                                   P(c_void_p), P(c_void_p), P(c_size_t), c_int,
                                                   c_int, P(AdamHyper), c_int, c_void_p]
     lib.kf_exchange_adam_master_batch.restype = c_int
+    lib.kf_step_gate_update.argtypes = [c_void_p, c_int, c_int, P(c_int), P(StepGroup), c_void_p,
+                                        c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                        c_int, c_void_p, c_void_p]
+    lib.kf_step_gate_update.restype = c_int
+    lib.kf_adam_update_batch_gated.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_void_p),
+                                               P(c_size_t), c_int, c_int, c_int, P(AdamHyper),
+                                               c_void_p, c_void_p, c_void_p]
+    lib.kf_adam_update_batch_gated.restype = c_int
+    lib.kf_adam_master_update_batch_gated.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p),
+                                                      P(c_void_p), P(c_void_p), P(c_size_t), c_int,
+                                                      c_int, c_int, P(AdamHyper), c_void_p,
+                                                      c_void_p, c_void_p]
+    lib.kf_adam_master_update_batch_gated.restype = c_int
+    lib.kf_exchange_reduce_shards_batch.argtypes = [c_void_p, P(c_void_p), P(c_size_t), c_int,
+                                                    c_int, c_int, P(c_int), c_void_p]
+    lib.kf_exchange_reduce_shards_batch.restype = c_int
+    lib.kf_exchange_adam_gated_batch.argtypes = [c_void_p, P(c_void_p), P(c_void_p), P(c_void_p),
+                                                 P(c_void_p), P(c_void_p), P(c_size_t), c_int,
+                                                 c_int, c_int, P(AdamHyper), c_void_p, c_void_p,
+                                                 c_void_p]
+    lib.kf_exchange_adam_gated_batch.restype = c_int
+    lib.kf_exchange_all_gather_doubles.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p]
+    lib.kf_exchange_all_gather_doubles.restype = c_int
     _lib = lib
     # HIP resources go back while the runtime is alive, before the C exit
     # handlers run (include/kungfu_amd.h kf_shutdown)

@@ -75,6 +75,26 @@ class HipEpilogue:
         return ops.adam_master_update_batch_(params16, grads16, masters, exp_avgs, exp_avg_sqs,
                                              hypers, np_)
 
+    # -- the gated step --
+    def sq_norm_plan(self, tensors):
+        """A plan whose run("sq", out=...) writes the tensors' fp64 sums of
+        squares and their total (ops.SegNorm), built once over fixed shards."""
+        return ops.SegNorm(tensors)
+
+    def step_gate_update_(self, sq, world, nps, groups, states, gate, **rule):
+        """The verdict of a gated step (ops.step_gate_update_), one launch."""
+        return ops.step_gate_update_(sq, world, nps, groups, states, gate, **rule)
+
+    def adam_update_gated_(self, params, grads, exp_avgs, exp_avg_sqs, hyper, gate, states, group,
+                           np_):
+        return ops.adam_update_batch_gated_(params, grads, exp_avgs, exp_avg_sqs, hyper, gate,
+                                            states, group, np_)
+
+    def adam_master_update_gated_(self, params16, grads16, masters, exp_avgs, exp_avg_sqs, hyper,
+                                  gate, states, group, np_):
+        return ops.adam_master_update_batch_gated_(params16, grads16, masters, exp_avgs,
+                                                   exp_avg_sqs, hyper, gate, states, group, np_)
+
 
 def coalesce_runs(buckets):
     """Maximal runs of buckets that are consecutive in one storage, each as
@@ -402,29 +422,45 @@ class Exchange:
             update(params, grads, *states, hypers, 1)
             return params
         marks = self._marks()
-        works = []
-        for i, g in enumerate(grads):
-            shard = self._workspace((key, "rs", i), g.numel() // self.world, g)
-            works.append((shard, self._scatter(g, shard, OP.SUM, (key, "a2a", i))))
+        shards, nps = self._reduce_shards(key, grads, marks)
         # one update launch over all shards: the / world is the fold's where
         # the shards were folded here, the update's own after a reduce-scatter
         width = 3 + len(states)
         sets = {0: tuple([] for _ in range(width)), self.world: tuple([] for _ in range(width))}
-        for _, (w, _) in works:
-            w.wait()
-        self._mark(marks, "reduce_scatter")
-        for i, (p, h, (shard, (w, recv))) in enumerate(zip(params, hypers, works)):
-            if recv is not None:
-                self.epilogue.fold_(list(recv.chunk(self.world)), shard, OP.SUM, self.world)
+        for i, (p, h, shard, np_) in enumerate(zip(params, hypers, shards, nps)):
             q = shard.numel()
-            dst = sets[0 if recv is not None else self.world]
             row = (p[self.rank * q:(self.rank + 1) * q], shard) + tuple(s[i] for s in states) + (h,)
-            for lst, x in zip(dst, row):
+            for lst, x in zip(sets[np_], row):
                 lst.append(x)
         for np_, lists in sets.items():
             if lists[0]:
                 update(*lists, np_)
         self._mark(marks, "epilogue")
+        self._gather_params(params, marks)
+        return params
+
+    def _reduce_shards(self, key, grads, marks):
+        """Phase 1 and the rank-order folds of a sharded step: (this rank's
+        reduced shards, what the update must still divide each by: the world
+        after a reduce-scatter, 0 after the fold). The shards are the cached
+        workspaces (key, "rs", i): the same addresses at every step."""
+        works = []
+        for i, g in enumerate(grads):
+            shard = self._workspace((key, "rs", i), g.numel() // self.world, g)
+            works.append((shard, self._scatter(g, shard, OP.SUM, (key, "a2a", i))))
+        for _, (w, _) in works:
+            w.wait()
+        self._mark(marks, "reduce_scatter")
+        shards, nps = [], []
+        for shard, (w, recv) in works:
+            if recv is not None:
+                self.epilogue.fold_(list(recv.chunk(self.world)), shard, OP.SUM, self.world)
+            shards.append(shard)
+            nps.append(0 if recv is not None else self.world)
+        return shards, nps
+
+    def _gather_params(self, params, marks):
+        """Phase 3 of a sharded step: every parameter bucket's in-place all-gather."""
         gathers = []
         for p in params:
             q = p.numel() // self.world
@@ -433,6 +469,82 @@ class Exchange:
         for w in gathers:
             w.wait()
         self._mark(marks, "all_gather")
+
+    # -- the gated step: adam_step_ / adam_master_step_ in two
+    # halves, with the optimizer's verdict over all its bucket groups between
+    def grad_shards_(self, grad_buckets, key):
+        """Where reduce_shards_(grad_buckets, key) leaves this rank's reduced
+        shards: fixed addresses, so a norm plan over them is built once."""
+        grads = list(grad_buckets)
+        for g in grads:
+            self._check(g)
+        if self.world == 1:
+            return grads
+        return [self._workspace((key, "rs", i), g.numel() // self.world, g)
+                for i, g in enumerate(grads)]
+
+    def reduce_shards_(self, grad_buckets, key):
+        """Half one (the native exchange's kf_exchange_reduce_shards_batch):
+        the gradients' reduce-scatter, or all-to-all and rank-order fold with
+        the / world. Returns what the update must still divide by: the world
+        after a reduce-scatter, 0 after the fold, 1 at world 1."""
+        grads = list(grad_buckets)
+        for g in grads:
+            self._check(g)
+        if self.world == 1:
+            return 1
+        if not grads:
+            return 0
+        _, nps = self._reduce_shards(key, grads, self._marks())
+        if len(set(nps)) != 1:
+            raise ValueError("reduce_shards_: one dtype per call")
+        return nps[0]
+
+    def gather_doubles_(self, send, recv):
+        """recv[r * n + k] = rank r's send[k] (kf_exchange_all_gather_doubles):
+        the plans' sums of squares of a gated step."""
+        if recv.numel() != send.numel() * self.world or send.dtype != torch.float64 or \
+                recv.dtype != torch.float64:
+            raise ValueError("gather_doubles_: recv holds world * send.numel() float64 values")
+        if self.world == 1:
+            if recv.data_ptr() != send.data_ptr():
+                recv.copy_(send)
+            return recv
+        dist.all_gather_into_tensor(recv, send.clone(), group=self.group)
+        return recv
+
+    def adam_gated_step_(self, param_buckets, grad_buckets, master_shards, exp_avg_shards,
+                         exp_avg_sq_shards, hyper, np_, gate, states, group, key):
+        """Half two (the native exchange's kf_exchange_adam_gated_batch):
+        epilogue.adam_update_gated_, or with master_shards
+        epilogue.adam_master_update_gated_, on the shards reduce_shards_ left
+        under the same `key`, with the one `hyper`, `np_` as reduce_shards_
+        returned it, the gate and step state `group` of `states`; then every
+        parameter bucket is all-gathered in place."""
+        params, grads = list(param_buckets), list(grad_buckets)
+        with_master = master_shards is not None
+        states_ = [list(s) for s in ((master_shards,) if with_master else ()) +
+                   (exp_avg_shards, exp_avg_sq_shards)]
+        if not all(len(x) == len(params) for x in [grads] + states_):
+            raise ValueError("adam_gated_step_: one grad bucket and %d state shards per bucket"
+                             % len(states_))
+        for i, (p, g) in enumerate(zip(params, grads)):
+            self._check(p)
+            if g.numel() != p.numel() or g.dtype != p.dtype or \
+                    any(s[i].numel() * self.world != p.numel() for s in states_):
+                raise ValueError("adam_gated_step_: bucket / shard sizes do not match")
+        if not params:
+            return params
+        shards = self.grad_shards_(grads, key)
+        q = [p.numel() // self.world for p in params]
+        mine = [p[self.rank * n:(self.rank + 1) * n] for p, n in zip(params, q)]
+        update = self.epilogue.adam_master_update_gated_ if with_master else \
+            self.epilogue.adam_update_gated_
+        marks = self._marks() if self.world > 1 else None
+        update(mine, shards, *states_, hyper, gate, states, group, np_)
+        if self.world > 1:
+            self._mark(marks, "epilogue")
+            self._gather_params(params, marks)
         return params
 
 

@@ -85,10 +85,11 @@ template <typename C> struct AdamBatchArgs {
 static_assert(sizeof(AdamBatchArgs<double>) + sizeof(Div) <= 3072, "kernarg budget");
 
 // one vector: p, m and v updated and stored
-template <typename T, int DIV, int DECAY>
+template <typename T, int DIV, int DECAY, typename GATE = AdamNoGate>
 __device__ __forceinline__ void adam_vec(void *pp, void *pm, void *pv, size_t vi, const u32x4 &rp,
                                          const u32x4 &rg, const u32x4 &rm, const u32x4 &rv,
-                                         const AdamSeg<typename SgdElt<T>::C> &h, const Div &d)
+                                         const AdamSeg<typename SgdElt<T>::C> &h, const Div &d,
+                                         const GATE &gate = GATE{})
 {
     using SV        = SgdVec<T>;
     using X         = typename SV::X;
@@ -98,16 +99,16 @@ __device__ __forceinline__ void adam_vec(void *pp, void *pm, void *pv, size_t vi
     SV::unpack(rg, g);
     SV::unpack(rm, m);
     SV::unpack(rv, v);
-    adam_math<T, DIV, DECAY, H, X>(p, g, m, v, h, d);
+    adam_math<T, DIV, DECAY, H, X>(p, g, m, v, h, d, gate);
     st_u4<KF_ADAM_ST_NT>(pp, vi, SV::pack(p));
     st_u4<KF_ADAM_ST_NT>(pm, vi, SV::pack(m));
     st_u4<KF_ADAM_ST_NT>(pv, vi, SV::pack(v));
 }
 
 // Block `blk` of `nblk` on one segment.
-template <typename T, int DIV, int DECAY>
+template <typename T, int DIV, int DECAY, typename GATE = AdamNoGate>
 __device__ __forceinline__ void adam_body(const AdamSeg<typename SgdElt<T>::C> &h, const Div &d,
-                                          size_t blk, size_t nblk)
+                                          size_t blk, size_t nblk, const GATE &gate = GATE{})
 {
     using E         = SgdElt<T>;
     using S         = typename E::S;
@@ -128,7 +129,7 @@ __device__ __forceinline__ void adam_body(const AdamSeg<typename SgdElt<T>::C> &
         S *sv       = reinterpret_cast<S *>(pv);
         C p[1] = {E::widen(sp[ti])}, g[1] = {E::widen(sq[ti])};
         C m[1] = {E::widen(sm[ti])}, v[1] = {E::widen(sv[ti])};
-        adam_math<T, DIV, DECAY, 1, C>(p, g, m, v, h, d);
+        adam_math<T, DIV, DECAY, 1, C>(p, g, m, v, h, d, gate);
         sp[ti] = E::narrow(p[0]);
         sm[ti] = E::narrow(m[0]);
         sv[ti] = E::narrow(v[0]);
@@ -152,7 +153,8 @@ __device__ __forceinline__ void adam_body(const AdamSeg<typename SgdElt<T>::C> &
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                adam_vec<T, DIV, DECAY>(pp, pm, pv, v0 + u * B, rp[u], rg[u], rm[u], rv[u], h, d);
+                adam_vec<T, DIV, DECAY>(pp, pm, pv, v0 + u * B, rp[u], rg[u], rm[u], rv[u], h, d,
+                                        gate);
             }
         } else {
             // ragged last tile
@@ -161,7 +163,7 @@ __device__ __forceinline__ void adam_body(const AdamSeg<typename SgdElt<T>::C> &
                 if (vi >= nvec) break;
                 const u32x4 rg = ld_u4<KF_ADAM_G_NT>(pg, vi), rp = ld_u4<KF_ADAM_PMV_NT>(pp, vi);
                 const u32x4 rm = ld_u4<KF_ADAM_PMV_NT>(pm, vi), rv = ld_u4<KF_ADAM_PMV_NT>(pv, vi);
-                adam_vec<T, DIV, DECAY>(pp, pm, pv, vi, rp, rg, rm, rv, h, d);
+                adam_vec<T, DIV, DECAY>(pp, pm, pv, vi, rp, rg, rm, rv, h, d, gate);
             }
         }
     }
@@ -181,6 +183,28 @@ __global__ void __launch_bounds__(kAdamBlock)
     });
 }
 
+// adam_update_kernel under a step gate (include/kungfu_amd.h
+// kf_adam_update_batch_gated): a skipped step returns before anything is
+// loaded; otherwise grad_mul, s2 and nss come from device memory, the segments'
+// own s2 and nss are not read.
+template <typename T>
+__global__ void __launch_bounds__(kAdamBlock)
+    adam_update_gated_kernel(AdamBatchArgs<typename SgdElt<T>::C> a, Div np, int div,
+                             const kf_step_gate *__restrict__ gate,
+                             const kf_step_state *__restrict__ st)
+{
+    using C = typename SgdElt<T>::C;
+    AdamGate<C> gt;
+    if (adam_gate_load(gate, st, gt)) return;
+    size_t blk, nblk;
+    const AdamSeg<C> &g = a.seg[batch_segment(a, blk, nblk)];
+    dispatch_div(div, [&](auto DIV) {
+        dispatch_decay(g.decay, [&](auto DECAY) {
+            adam_body<T, decltype(DIV)::value, decltype(DECAY)::value>(g, np, blk, nblk, gt);
+        });
+    });
+}
+
 }  // namespace kf
 
 namespace
@@ -188,10 +212,14 @@ namespace
 using namespace kf;
 
 constexpr UpdateFail fail{"kf_adam_update_batch"};
+constexpr UpdateFail fail_gated{"kf_adam_update_batch_gated"};
 
+// gate == nullptr: hyper[b] is segment b's and the parent kernel runs; else
+// the one hyper[0] is every segment's and the gated kernel runs.
 template <typename T>
 int launch_adam(void *const *params, const void *const *grads, void *const *ms, void *const *vs,
-                const size_t *counts, int nb, int np, const kf_adam_hyper *hyper, hipStream_t s)
+                const size_t *counts, int nb, int np, const kf_adam_hyper *hyper, hipStream_t s,
+                const kf_step_gate *gate = nullptr, const kf_step_state *st = nullptr)
 {
     using C       = typename SgdElt<T>::C;
     const Div dv  = update_div(np);
@@ -204,21 +232,23 @@ int launch_adam(void *const *params, const void *const *grads, void *const *ms, 
             g.m = ms[b];
             g.v = vs[b];
             g.n = counts[b];
-            adam_scalars<C>(g, hyper[b]);
+            adam_scalars<C>(g, hyper[gate ? 0 : b]);
         },
         [&](unsigned gx, unsigned gy, const AdamBatchArgs<C> &a) {
+            if (gate) {
+                adam_update_gated_kernel<T><<<dim3(gx, gy), kAdamBlock, 0, s>>>(a, dv, div, gate, st);
+                return launch_status(fail_gated);
+            }
             adam_update_kernel<T><<<dim3(gx, gy), kAdamBlock, 0, s>>>(a, dv, div);
             return launch_status(fail);
         });
 }
 
-}  // namespace
-
-extern "C" {
-
-int kf_adam_update_batch(void *const *params, const void *const *grads, void *const *exp_avgs,
-                         void *const *exp_avg_sqs, const size_t *counts, int nb,
-                         KungFu_Datatype dt, int np, const kf_adam_hyper *hyper, void *stream)
+// Both entries: every check comes before any HIP call.
+int adam_entry(const UpdateFail &fail, void *const *params, const void *const *grads,
+               void *const *exp_avgs, void *const *exp_avg_sqs, const size_t *counts, int nb,
+               KungFu_Datatype dt, int np, const kf_adam_hyper *hyper, const kf_step_gate *gate,
+               const kf_step_state *state, void *stream)
 {
     if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
     if (nb == 0) return KF_OK;
@@ -238,19 +268,54 @@ int kf_adam_update_batch(void *const *params, const void *const *grads, void *co
         if (off16(params[b]) || off16(grads[b]) || off16(exp_avgs[b]) || off16(exp_avg_sqs[b])) {
             return fail(KF_ERR_ARG, "KF_ERR_ARG", "pointers must be 16-byte aligned");
         }
-        if (!(hyper[b].bias_correction1 > 0) || !(hyper[b].bias_correction2 > 0)) {
+        const kf_adam_hyper &h = hyper[gate ? 0 : b];
+        if (!(h.bias_correction1 > 0) || !(h.bias_correction2 > 0)) {
             return fail(KF_ERR_ARG, "KF_ERR_ARG", "bias corrections must be > 0");
         }
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (dt) {
     case KungFu_FLOAT:
-        return launch_adam<float>(params, grads, exp_avgs, exp_avg_sqs, counts, nb, np, hyper, s);
+        return launch_adam<float>(params, grads, exp_avgs, exp_avg_sqs, counts, nb, np, hyper, s,
+                                  gate, state);
     case KungFu_DOUBLE:
-        return launch_adam<double>(params, grads, exp_avgs, exp_avg_sqs, counts, nb, np, hyper, s);
+        return launch_adam<double>(params, grads, exp_avgs, exp_avg_sqs, counts, nb, np, hyper, s,
+                                  gate, state);
     default:
-        return launch_adam<bf16_t>(params, grads, exp_avgs, exp_avg_sqs, counts, nb, np, hyper, s);
+        return launch_adam<bf16_t>(params, grads, exp_avgs, exp_avg_sqs, counts, nb, np, hyper, s,
+                                  gate, state);
     }
+}
+
+}  // namespace
+
+extern "C" {
+
+int kf_adam_update_batch(void *const *params, const void *const *grads, void *const *exp_avgs,
+                         void *const *exp_avg_sqs, const size_t *counts, int nb,
+                         KungFu_Datatype dt, int np, const kf_adam_hyper *hyper, void *stream)
+{
+    return adam_entry(fail, params, grads, exp_avgs, exp_avg_sqs, counts, nb, dt, np, hyper, nullptr,
+                      nullptr, stream);
+}
+
+int kf_adam_update_batch_gated(void *const *params, const void *const *grads,
+                               void *const *exp_avgs, void *const *exp_avg_sqs,
+                               const size_t *counts, int nb, KungFu_Datatype dt, int np,
+                               const kf_adam_hyper *hyper, const kf_step_gate *gate,
+                               const kf_step_state *state, void *stream)
+{
+    if (nb > 0 && (!gate || !state)) {
+        return fail_gated(KF_ERR_ARG, "KF_ERR_ARG", "null gate or step state");
+    }
+    if (nb <= 0 || !hyper) {
+        return adam_entry(fail_gated, params, grads, exp_avgs, exp_avg_sqs, counts, nb, dt, np,
+                          hyper, gate, state, stream);
+    }
+    kf_adam_hyper one    = *hyper;  // its bias corrections are the device's, not the caller's
+    one.bias_correction1 = one.bias_correction2 = 1.0;
+    return adam_entry(fail_gated, params, grads, exp_avgs, exp_avg_sqs, counts, nb, dt, np, &one,
+                      gate, state, stream);
 }
 
 }  // extern "C"

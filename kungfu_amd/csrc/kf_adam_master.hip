@@ -130,10 +130,11 @@ __device__ __forceinline__ void store_f32(void *base, size_t ui, const f32x2 (&x
 }
 
 // one unit: master, m, v and the narrowed parameters updated and stored
-template <typename T, int DIV, int DECAY>
+template <typename T, int DIV, int DECAY, typename GATE = AdamNoGate>
 __device__ __forceinline__ void master_unit(const AdamMasterSeg &h, const Div &d, size_t ui,
                                             const u32xh &rg, const u32x4 (&rp)[kMK],
-                                            const u32x4 (&rm)[kMK], const u32x4 (&rv)[kMK])
+                                            const u32x4 (&rm)[kMK], const u32x4 (&rv)[kMK],
+                                            const GATE &gate = GATE{})
 {
     f32x2 p[kMH], g[kMH], m[kMH], v[kMH];
 #pragma unroll
@@ -141,7 +142,7 @@ __device__ __forceinline__ void master_unit(const AdamMasterSeg &h, const Div &d
     unpack_f32(rp, p);
     unpack_f32(rm, m);
     unpack_f32(rv, v);
-    adam_math<float, DIV, DECAY, kMH, f32x2>(p, g, m, v, h, d);
+    adam_math<float, DIV, DECAY, kMH, f32x2>(p, g, m, v, h, d, gate);
     store_f32(h.p, ui, p);
     store_f32(h.m, ui, m);
     store_f32(h.v, ui, v);
@@ -161,9 +162,9 @@ __device__ __forceinline__ void ld_f32(const void *base, size_t ui, u32x4 (&raw)
 }
 
 // Block `blk` of `nblk` on one segment.
-template <typename T, int DIV, int DECAY>
+template <typename T, int DIV, int DECAY, typename GATE = AdamNoGate>
 __device__ __forceinline__ void master_body(const AdamMasterSeg &h, const Div &d, size_t blk,
-                                            size_t nblk)
+                                            size_t nblk, const GATE &gate = GATE{})
 {
     using E         = SgdElt<T>;
     constexpr int N = kAdamMasterElts;
@@ -180,7 +181,7 @@ __device__ __forceinline__ void master_body(const AdamMasterSeg &h, const Div &d
         float *sp = reinterpret_cast<float *>(h.p), *sm = reinterpret_cast<float *>(h.m);
         float *sv = reinterpret_cast<float *>(h.v);
         float p[1] = {sp[ti]}, g[1] = {E::widen(sg[ti])}, m[1] = {sm[ti]}, v[1] = {sv[ti]};
-        adam_math<float, DIV, DECAY, 1, float>(p, g, m, v, h, d);
+        adam_math<float, DIV, DECAY, 1, float>(p, g, m, v, h, d, gate);
         sp[ti]  = p[0];
         sm[ti]  = m[0];
         sv[ti]  = v[0];
@@ -206,7 +207,7 @@ __device__ __forceinline__ void master_body(const AdamMasterSeg &h, const Div &d
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                master_unit<T, DIV, DECAY>(h, d, u0 + u * B, rg[u], rp[u], rm[u], rv[u]);
+                master_unit<T, DIV, DECAY>(h, d, u0 + u * B, rg[u], rp[u], rm[u], rv[u], gate);
             }
         } else {
             // ragged last tile
@@ -218,7 +219,7 @@ __device__ __forceinline__ void master_body(const AdamMasterSeg &h, const Div &d
                 ld_f32<WNT>(h.p, ui, rp);
                 ld_f32<WNT>(h.m, ui, rm);
                 ld_f32<WNT>(h.v, ui, rv);
-                master_unit<T, DIV, DECAY>(h, d, ui, rg, rp, rm, rv);
+                master_unit<T, DIV, DECAY>(h, d, ui, rg, rp, rm, rv, gate);
             }
         }
     }
@@ -237,6 +238,26 @@ __global__ void __launch_bounds__(kAdamMasterBlock)
     });
 }
 
+// adam_master_kernel under a step gate (include/kungfu_amd.h
+// kf_adam_master_update_batch_gated): a skipped step returns before anything
+// is loaded; otherwise grad_mul, s2 and nss come from device memory.
+template <typename T>
+__global__ void __launch_bounds__(kAdamMasterBlock)
+    adam_master_gated_kernel(AdamMasterArgs a, Div np, int div,
+                             const kf_step_gate *__restrict__ gate,
+                             const kf_step_state *__restrict__ st)
+{
+    AdamGate<float> gt;
+    if (adam_gate_load(gate, st, gt)) return;
+    size_t blk, nblk;
+    const AdamMasterSeg &g = a.seg[batch_segment(a, blk, nblk)];
+    dispatch_div(div, [&](auto DIV) {
+        dispatch_decay(g.decay, [&](auto DECAY) {
+            master_body<T, decltype(DIV)::value, decltype(DECAY)::value>(g, np, blk, nblk, gt);
+        });
+    });
+}
+
 }  // namespace kf
 
 namespace
@@ -244,11 +265,15 @@ namespace
 using namespace kf;
 
 constexpr UpdateFail fail{"kf_adam_master_update_batch"};
+constexpr UpdateFail fail_gated{"kf_adam_master_update_batch_gated"};
 
+// gate == nullptr: hyper[b] is segment b's and the parent kernel runs; else
+// the one hyper[0] is every segment's and the gated kernel runs.
 template <typename T>
 int launch_master(void *const *params16, const void *const *grads16, void *const *masters,
                   void *const *ms, void *const *vs, const size_t *counts, int nb, int np,
-                  const kf_adam_hyper *hyper, hipStream_t s)
+                  const kf_adam_hyper *hyper, hipStream_t s, const kf_step_gate *gate = nullptr,
+                  const kf_step_state *st = nullptr)
 {
     const Div dv  = update_div(np);
     const int div = update_div_code(np, dv);
@@ -261,23 +286,25 @@ int launch_master(void *const *params16, const void *const *grads16, void *const
             g.m   = ms[b];
             g.v   = vs[b];
             g.n   = counts[b];
-            adam_scalars<float>(g, hyper[b]);
+            adam_scalars<float>(g, hyper[gate ? 0 : b]);
         },
         [&](unsigned gx, unsigned gy, const AdamMasterArgs &a) {
+            if (gate) {
+                adam_master_gated_kernel<T>
+                    <<<dim3(gx, gy), kAdamMasterBlock, 0, s>>>(a, dv, div, gate, st);
+                return launch_status(fail_gated);
+            }
             adam_master_kernel<T><<<dim3(gx, gy), kAdamMasterBlock, 0, s>>>(a, dv, div);
             return launch_status(fail);
         });
 }
 
-}  // namespace
-
-extern "C" {
-
-int kf_adam_master_update_batch(void *const *params16, const void *const *grads16,
-                                void *const *masters, void *const *exp_avgs,
-                                void *const *exp_avg_sqs, const size_t *counts, int nb,
-                                KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
-                                void *stream)
+// Both entries: every check comes before any HIP call.
+int master_entry(const UpdateFail &fail, void *const *params16, const void *const *grads16,
+                 void *const *masters, void *const *exp_avgs, void *const *exp_avg_sqs,
+                 const size_t *counts, int nb, KungFu_Datatype dt, int np,
+                 const kf_adam_hyper *hyper, const kf_step_gate *gate, const kf_step_state *state,
+                 void *stream)
 {
     if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
     if (nb == 0) return KF_OK;
@@ -298,17 +325,52 @@ int kf_adam_master_update_batch(void *const *params16, const void *const *grads1
             off16(exp_avg_sqs[b])) {
             return fail(KF_ERR_ARG, "KF_ERR_ARG", "pointers must be 16-byte aligned");
         }
-        if (!(hyper[b].bias_correction1 > 0) || !(hyper[b].bias_correction2 > 0)) {
+        const kf_adam_hyper &h = hyper[gate ? 0 : b];
+        if (!(h.bias_correction1 > 0) || !(h.bias_correction2 > 0)) {
             return fail(KF_ERR_ARG, "KF_ERR_ARG", "bias corrections must be > 0");
         }
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dt == KungFu_BFLOAT16) {
         return launch_master<bf16_t>(params16, grads16, masters, exp_avgs, exp_avg_sqs, counts, nb,
-                                     np, hyper, s);
+                                     np, hyper, s, gate, state);
     }
     return launch_master<f16_t>(params16, grads16, masters, exp_avgs, exp_avg_sqs, counts, nb, np,
-                                hyper, s);
+                                hyper, s, gate, state);
+}
+
+}  // namespace
+
+extern "C" {
+
+int kf_adam_master_update_batch(void *const *params16, const void *const *grads16,
+                                void *const *masters, void *const *exp_avgs,
+                                void *const *exp_avg_sqs, const size_t *counts, int nb,
+                                KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
+                                void *stream)
+{
+    return master_entry(fail, params16, grads16, masters, exp_avgs, exp_avg_sqs, counts, nb, dt, np,
+                        hyper, nullptr, nullptr, stream);
+}
+
+int kf_adam_master_update_batch_gated(void *const *params16, const void *const *grads16,
+                                      void *const *masters, void *const *exp_avgs,
+                                      void *const *exp_avg_sqs, const size_t *counts, int nb,
+                                      KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
+                                      const kf_step_gate *gate, const kf_step_state *state,
+                                      void *stream)
+{
+    if (nb > 0 && (!gate || !state)) {
+        return fail_gated(KF_ERR_ARG, "KF_ERR_ARG", "null gate or step state");
+    }
+    if (nb <= 0 || !hyper) {
+        return master_entry(fail_gated, params16, grads16, masters, exp_avgs, exp_avg_sqs, counts,
+                            nb, dt, np, hyper, gate, state, stream);
+    }
+    kf_adam_hyper one    = *hyper;  // its bias corrections are the device's, not the caller's
+    one.bias_correction1 = one.bias_correction2 = 1.0;
+    return master_entry(fail_gated, params16, grads16, masters, exp_avgs, exp_avg_sqs, counts, nb,
+                        dt, np, &one, gate, state, stream);
 }
 
 }  // extern "C"

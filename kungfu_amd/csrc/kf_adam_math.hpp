@@ -39,17 +39,76 @@ __device__ __forceinline__ f64x2 adam_div(f64x2 a, f64x2 b)
     return f64x2{__ddiv_rn(a.x, b.x), __ddiv_rn(a.y, b.y)};
 }
 
+// What a gated kernel (include/kungfu_amd.h kf_adam_update_batch_gated) read
+// from the step's gate and its group's step state, in the compute type C; the
+// ungated kernels pass no gate at all.
+struct AdamNoGate {
+    static constexpr bool on = false;
+};
+template <typename C> struct AdamGate {
+    static constexpr bool on = true;
+    C mul, s2, nss;
+};
+
+// The block's gate words, or nothing to do: true when the step is skipped.
+// Ordinary loads through kernel-argument pointers, wave-uniform. All of them
+// are issued before skip is looked at: one memory latency after the kernel
+// arguments', not one for skip and another for the scalars behind it.
+template <typename C>
+__device__ __forceinline__ bool adam_gate_load(const kf_step_gate *gate, const kf_step_state *st,
+                                               AdamGate<C> &out)
+{
+    const int skip = gate->skip;
+    out.mul        = static_cast<C>(gate->grad_mul);
+    if constexpr (std::is_same<C, double>::value) {
+        out.s2  = st->s2_f64;
+        out.nss = st->nss_f64;
+    } else {
+        out.s2  = st->s2;
+        out.nss = st->nss;
+    }
+    return skip != 0;
+}
+
+// s2 and nss of an update: the segment's own, or the gate's.
+template <typename SEG>
+__device__ __forceinline__ auto adam_s2(const SEG &h, const AdamNoGate &) -> decltype(h.s2)
+{
+    return h.s2;
+}
+template <typename SEG>
+__device__ __forceinline__ auto adam_nss(const SEG &h, const AdamNoGate &) -> decltype(h.nss)
+{
+    return h.nss;
+}
+template <typename SEG, typename C>
+__device__ __forceinline__ C adam_s2(const SEG &, const AdamGate<C> &gate)
+{
+    return gate.s2;
+}
+template <typename SEG, typename C>
+__device__ __forceinline__ C adam_nss(const SEG &, const AdamGate<C> &gate)
+{
+    return gate.nss;
+}
+
 // The update of H values (V = C) or of H lane pairs (V = X); g holds the
 // summed gradients on entry; h is the segment's kernarg entry (SEG: its
 // members w, b1, c1, b2, c2, s2, eps, nss in T's compute type), whose scalars
-// are wave-uniform. DECAY is the segment's choice, made once per block.
-template <typename T, int DIV, int DECAY, int H, typename V, typename SEG>
+// are wave-uniform. DECAY is the segment's choice, made once per block. A
+// gate adds g = rnd(g * mul) after the /np and replaces h.s2 and h.nss.
+template <typename T, int DIV, int DECAY, int H, typename V, typename SEG,
+          typename GATE = AdamNoGate>
 __device__ __forceinline__ void adam_math(V (&p)[H], V (&g)[H], V (&m)[H], V (&v)[H], const SEG &h,
-                                          const Div &d)
+                                          const Div &d, const GATE &gate = GATE{})
 {
     using E = SgdElt<T>;
 #pragma unroll
     for (int i = 0; i < H; ++i) g[i] = SgdDiv<T, DIV>::run(g[i], d);
+    if constexpr (GATE::on) {
+#pragma unroll
+        for (int i = 0; i < H; ++i) g[i] = E::rnd(g[i] * gate.mul);
+    }
     if constexpr (DECAY == ADAM_L2) {
 #pragma unroll
         for (int i = 0; i < H; ++i) g[i] = E::rnd(g[i] + h.w * p[i]);
@@ -71,10 +130,10 @@ __device__ __forceinline__ void adam_math(V (&p)[H], V (&g)[H], V (&m)[H], V (&v
 #pragma unroll
     for (int i = 0; i < H; ++i) {
         const V r = E::rnd(adam_sqrt(v[i]));
-        const V e = E::rnd(adam_div(r, h.s2));
+        const V e = E::rnd(adam_div(r, adam_s2(h, gate)));
         const V f = E::rnd(e + h.eps);
         const V u = adam_div(m[i], f);
-        p[i]      = E::rnd(p[i] + h.nss * u);
+        p[i]      = E::rnd(p[i] + adam_nss(h, gate) * u);
     }
 }
 

@@ -356,9 +356,22 @@ struct ShardUpdate {
     const kf_sgd_hyper *sgd;
     const kf_adam_hyper *adam;
     void *const *master = nullptr;  // Adam on 16-bit buckets: this rank's fp32 master shards
+    // The gated step (kf_exchange_reduce_shards_batch, kf_exchange_adam_gated_batch)
+    // runs the schedule in two calls with the verdict between them:
+    //   kReduceOnly  phase 1 and the rank-order folds, no update; *np_out = what
+    //                the update must still divide by
+    //   kUpdateOnly  the gated update with np = np_in, then phase 3; adam is ONE
+    //                hyper for every bucket
+    enum { kWhole = 0, kReduceOnly = 1, kUpdateOnly = 2 };
+    int part                   = kWhole;
+    int *np_out                = nullptr;
+    int np_in                  = 0;
+    const kf_step_gate *gate   = nullptr;
+    const kf_step_state *gstate = nullptr;
 
     const char *kernel() const
     {
+        if (gate) return master ? "kf_adam_master_update_batch_gated" : "kf_adam_update_batch_gated";
         return sgd ? "kf_sgd_update_batch"
                    : (master ? "kf_adam_master_update_batch" : "kf_adam_update_batch");
     }
@@ -366,6 +379,14 @@ struct ShardUpdate {
     int run(void *const *ps, const void *const *gs, const size_t *cnts, int b0, int n,
             KungFu_Datatype dt, int np, hipStream_t s) const
     {
+        if (gate && master) {
+            return kf_adam_master_update_batch_gated(ps, gs, master + b0, state + b0, state2 + b0,
+                                                     cnts, n, dt, np, adam, gate, gstate, s);
+        }
+        if (gate) {
+            return kf_adam_update_batch_gated(ps, gs, state + b0, state2 + b0, cnts, n, dt, np, adam,
+                                              gate, gstate, s);
+        }
         if (sgd) {
             return kf_sgd_update_batch(ps, gs, state ? state + b0 : nullptr, cnts, n, dt, np,
                                        sgd + b0, s);
@@ -566,8 +587,14 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
     const int sz = tsize(dt);
     const int W = world, r = rank;
     const bool sma = sma_alpha != nullptr;
+    const bool reduce_only = upd && upd->part == ShardUpdate::kReduceOnly;
+    const bool update_only = upd && upd->part == ShardUpdate::kUpdateOnly;
+    if (W == 1 && builtin && reduce_only) {  // a single peer: the buckets are the sums
+        *upd->np_out = 1;
+        return KF_OK;
+    }
     if (W == 1 && builtin && upd) {  // a single peer: the update over the whole buckets
-        const int rc = upd->run(upd->params, sends, counts, 0, nb, dt, 1, s);
+        const int rc = upd->run(upd->params, sends, counts, 0, nb, dt, update_only ? upd->np_in : 1, s);
         if (rc != KF_OK) return fail(rc, std::string(upd->kernel()) + ": " + kf_last_error());
         return KF_OK;
     }
@@ -593,11 +620,12 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
     // the /np inside the collective (ncclAvg): no shard epilogue
     const KungFu_Op rs_op =
         a == KF_ALGO_REDUCE_SCATTER_AVG ? static_cast<KungFu_Op>(KF_TRANSPORT_OP_AVG) : op;
+    if (reduce_only) *upd->np_out = a == KF_ALGO_REDUCE_SCATTER ? W : 0;
 
     // workspace: received shards (all-to-all) and gathered tails
     std::vector<size_t> wsoff(nb, 0), toff(nb, 0);
     size_t need = 0;
-    for (int b = 0; b < nb && (phases & 3); ++b) {
+    for (int b = 0; b < nb && (phases & 3) && !update_only; ++b) {
         const size_t q = counts[b] / W, t = counts[b] % W;
         if (a == KF_ALGO_ALL_TO_ALL && q) {
             wsoff[b] = need;
@@ -668,7 +696,7 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
             outs.clear();
             cnts.clear();
         }
-        for (int b = b0; b < b1; ++b) {  // rank-order folds: shards and tails
+        for (int b = b0; b < b1 && !update_only; ++b) {  // rank-order folds: shards and tails
             const size_t q = counts[b] / W, t = counts[b] % W;
             char *rcv      = static_cast<char *>(recvs[b]);
             if (q && a == KF_ALGO_ALL_TO_ALL) {
@@ -688,11 +716,11 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
                                                  average ? W : 0, cs);
             if (e != KF_OK) return fail(e, "rank-order fold of the received shards");
         }
-        if (upd) {
+        if (upd && !reduce_only) {
             // the update on this rank's shard of every bucket; after a plain
             // reduce-scatter the shard holds the sum and the kernel divides
             // (the shard is read once, no /np pass); the fold and ncclAvg
-            // have divided already
+            // have divided already (a gated update is told which)
             std::vector<void *> ps;
             std::vector<const void *> gs;
             cnts.clear();
@@ -702,8 +730,8 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
                 gs.push_back(static_cast<const char *>(recvs[b]) + r * q * sz);
                 cnts.push_back(q);
             }
-            const int e = upd->run(ps.data(), gs.data(), cnts.data(), b0, b1 - b0, dt,
-                                   a == KF_ALGO_REDUCE_SCATTER ? W : 0, cs);
+            const int np = update_only ? upd->np_in : (a == KF_ALGO_REDUCE_SCATTER ? W : 0);
+            const int e  = upd->run(ps.data(), gs.data(), cnts.data(), b0, b1 - b0, dt, np, cs);
             if (e != KF_OK) return fail(e, std::string(upd->kernel()) + ": " + kf_last_error());
         }
         return KF_OK;
@@ -1706,10 +1734,15 @@ static int exchange_adam(const char *name, kf_exchange_t *ex, void *const *param
                          void *const *grads, void *const *master_shards, bool with_master,
                          void *const *exp_avg_shards, void *const *exp_avg_sq_shards,
                          const size_t *counts, int nb, KungFu_Datatype dt,
-                         const kf_adam_hyper *hyper, int algo, void *stream)
+                         const kf_adam_hyper *hyper, int algo, void *stream,
+                         const kf_step_gate *gate = nullptr, const kf_step_state *gstate = nullptr,
+                         int np_in = 0)
 {
+    // gate != nullptr: kf_exchange_adam_gated_batch, the gated update (one
+    // hyper, its bias corrections ignored) and phase 3
     const std::string fn = std::string(name) + ": ";
     if (!ex || nb < 0) return fail(KF_ERR_ARG, fn + "bad arguments");
+    if (gate && (!gstate || np_in < 0)) return fail(KF_ERR_ARG, fn + "no step state, or np < 0");
     if (with_master) {
         if (dt != KungFu_BFLOAT16 && dt != KungFu_FLOAT16) {
             return fail(KF_ERR_DTYPE, fn + "bf16 and f16 only");
@@ -1744,16 +1777,95 @@ static int exchange_adam(const char *name, kf_exchange_t *ex, void *const *param
             (W > 1 && (counts[b] / W * sz) % 16)) {
             return fail(KF_ERR_ARG, fn + "buckets and their shards must start 16-byte aligned");
         }
-        if (!(hyper[b].bias_correction1 > 0) || !(hyper[b].bias_correction2 > 0)) {
+        if (!gate && (!(hyper[b].bias_correction1 > 0) || !(hyper[b].bias_correction2 > 0))) {
             return fail(KF_ERR_ARG, fn + "bias corrections must be > 0");
         }
     }
     DeviceGuard g(ex->device);
     std::lock_guard<std::mutex> lk(ex->mu);
-    const ShardUpdate step{params, exp_avg_shards, exp_avg_sq_shards, nullptr, hyper,
-                           with_master ? master_shards : nullptr};
+    ShardUpdate step{params, exp_avg_shards, exp_avg_sq_shards, nullptr, hyper,
+                     with_master ? master_shards : nullptr};
+    if (gate) {
+        step.part   = ShardUpdate::kUpdateOnly;
+        step.np_in  = np_in;
+        step.gate   = gate;
+        step.gstate = gstate;
+    }
     return ex->batch(grads, grads, counts, nb, dt, KungFu_SUM, 1, algo,
-                     static_cast<hipStream_t>(stream), nullptr, 7, &step);
+                     static_cast<hipStream_t>(stream), nullptr, gate ? 6 : 7, &step);
+}
+
+int kf_exchange_reduce_shards_batch(kf_exchange_t *ex, void *const *grads, const size_t *counts,
+                                    int nb, KungFu_Datatype dt, int algo, int *np, void *stream)
+{
+    const std::string fn = "kf_exchange_reduce_shards_batch: ";
+    if (!ex || nb < 0 || !np) return fail(KF_ERR_ARG, fn + "bad arguments");
+    if (!is_float(dt)) return fail(KF_ERR_DTYPE, fn + "f32, f16, bf16 and f64 only");
+    if (algo < KF_ALGO_AUTO || algo > KF_ALGO_REDUCE_SCATTER_AVG) return fail(KF_ERR_ARG, "unknown algo");
+    if (nb > 0 && (!grads || !counts)) return fail(KF_ERR_ARG, fn + "null table");
+    // every rank must reach the same verdict before any collective is queued
+    const size_t W = static_cast<size_t>(ex->world), sz = static_cast<size_t>(tsize(dt));
+    for (int b = 0; b < nb; ++b) {
+        if (counts[b] == 0) continue;
+        if (!grads[b]) return fail(KF_ERR_ARG, fn + "null bucket");
+        if (counts[b] % W) {
+            return fail(KF_ERR_ARG, fn + "counts must be multiples of the world "
+                                         "(padded buckets, no tails)");
+        }
+        if ((reinterpret_cast<uintptr_t>(grads[b]) % 16) || (W > 1 && (counts[b] / W * sz) % 16)) {
+            return fail(KF_ERR_ARG, fn + "buckets and their shards must start 16-byte aligned");
+        }
+    }
+    DeviceGuard g(ex->device);
+    std::lock_guard<std::mutex> lk(ex->mu);
+    if (nb == 0) {  // nothing to reduce: what a non-empty call would report
+        int a = 0;
+        const int rc = ex->world == 1 && ex->builtin ? KF_OK : resolve_algo(algo, dt, KungFu_SUM, ex->world, &a);
+        if (rc != KF_OK) return rc;
+        *np = ex->world == 1 && ex->builtin ? 1 : (a == KF_ALGO_REDUCE_SCATTER ? ex->world : 0);
+        return KF_OK;
+    }
+    ShardUpdate step{nullptr, nullptr, nullptr, nullptr, nullptr};
+    step.part   = ShardUpdate::kReduceOnly;
+    step.np_out = np;
+    return ex->batch(grads, grads, counts, nb, dt, KungFu_SUM, 1, algo,
+                     static_cast<hipStream_t>(stream), nullptr, 3, &step);
+}
+
+int kf_exchange_adam_gated_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
+                                 void *const *master_shards, void *const *exp_avg_shards,
+                                 void *const *exp_avg_sq_shards, const size_t *counts, int nb,
+                                 KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
+                                 const kf_step_gate *gate, const kf_step_state *state, void *stream)
+{
+    if (!gate) return fail(KF_ERR_ARG, "kf_exchange_adam_gated_batch: null gate");
+    return exchange_adam("kf_exchange_adam_gated_batch", ex, params, grads, master_shards,
+                         master_shards != nullptr, exp_avg_shards, exp_avg_sq_shards, counts, nb, dt,
+                         hyper, KF_ALGO_AUTO, stream, gate, state, np);
+}
+
+int kf_exchange_all_gather_doubles(kf_exchange_t *ex, const double *send, double *recv, int n,
+                                   void *stream)
+{
+    const std::string fn = "kf_exchange_all_gather_doubles: ";
+    if (!ex || n < 0) return fail(KF_ERR_ARG, fn + "bad arguments");
+    if (n == 0) return KF_OK;
+    if (!send || !recv) return fail(KF_ERR_ARG, fn + "null pointer");
+    DeviceGuard g(ex->device);
+    std::lock_guard<std::mutex> lk(ex->mu);
+    hipStream_t s        = static_cast<hipStream_t>(stream);
+    const size_t bytes   = static_cast<size_t>(n) * sizeof(double);
+    if (ex->world == 1 && ex->builtin) {
+        if (send != recv) KF_HIP(hipMemcpyAsync(recv, send, bytes, hipMemcpyDeviceToDevice, s));
+        return KF_OK;
+    }
+    const int e0 = ex->T->group_start(ex->comm);
+    if (e0 != 0) return ex->tfail(e0, "group_start");
+    const int e  = ex->T->all_gather(send, recv, bytes, ex->comm, s);
+    const int e1 = ex->T->group_end(ex->comm);
+    if (e != 0) return ex->tfail(e, "all_gather of the plans' sums of squares");
+    if (e1 != 0) return ex->tfail(e1, "group_end");
+    return KF_OK;
 }
 
 int kf_exchange_adam_batch(kf_exchange_t *ex, void *const *params, void *const *grads,

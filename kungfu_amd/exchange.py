@@ -302,6 +302,19 @@ class NativeExchange:
                              % (name, len(states)))
         if not params:
             return params
+        self._shard_tables(name, params, grads, states)
+        rc = fn(self._h, _lib.ptr_array([p.data_ptr() for p in params]),
+                _lib.ptr_array([g.data_ptr() for g in grads]),
+                *[_lib.ptr_array([0 if t is None else t.data_ptr() for t in s]) for s in states],
+                _arr(ctypes.c_size_t, [p.numel() for p in params]), len(params),
+                int(kungfu_dtype(params[0])), hyper_array(hypers), ALGOS[self.algo],
+                torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(rc, cname)
+        return params
+
+    def _shard_tables(self, name, params, grads, states):
+        """The checks of a sharded step's tables (_shard_call and the gated
+        step's second half)."""
         flat = [t for s in states for t in s if t is not None]
         if len(states) == 3:  # master weights: fp32 shards beside 16-bit buckets
             self._check(params + grads)
@@ -316,13 +329,75 @@ class NativeExchange:
                     any(s[i] is not None and s[i].numel() * self.world != p.numel()
                         for s in states):
                 raise ValueError("%s: bucket / shard sizes do not match" % name)
-        rc = fn(self._h, _lib.ptr_array([p.data_ptr() for p in params]),
-                _lib.ptr_array([g.data_ptr() for g in grads]),
-                *[_lib.ptr_array([0 if t is None else t.data_ptr() for t in s]) for s in states],
-                _arr(ctypes.c_size_t, [p.numel() for p in params]), len(params),
-                int(kungfu_dtype(params[0])), hyper_array(hypers), ALGOS[self.algo],
-                torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(rc, cname)
+
+    # -- the gated step: adam_step_ / adam_master_step_ in two
+    # halves, with the optimizer's verdict over all its bucket groups between
+    def grad_shards_(self, grad_buckets, key=None):
+        """Where reduce_shards_ leaves this rank's reduced shards: grads[b] +
+        rank * q, fixed addresses (`key` is collective.Exchange's, unused)."""
+        grads = list(grad_buckets)
+        self._check(grads)
+        q = [g.numel() // self.world for g in grads]
+        return [g[self.rank * n:(self.rank + 1) * n] for g, n in zip(grads, q)]
+
+    def reduce_shards_(self, grad_buckets, key=None):
+        """Half one (kf_exchange_reduce_shards_batch): phase 1 and the
+        rank-order folds, queued on the current stream. Returns what the
+        update must still divide by: the world after a reduce-scatter, 0 after
+        the fold or under rs_avg, 1 at world 1 on the built-in transport."""
+        grads = list(grad_buckets)
+        if grads:
+            self._check(grads)
+        np_ = ctypes.c_int(0)
+        dt = int(kungfu_dtype(grads[0])) if grads else 0x20408
+        rc = self.lib.kf_exchange_reduce_shards_batch(
+            self._h, _lib.ptr_array([g.data_ptr() for g in grads]),
+            _arr(ctypes.c_size_t, [g.numel() for g in grads]), len(grads), dt, ALGOS[self.algo],
+            ctypes.byref(np_), torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(rc, "kf_exchange_reduce_shards_batch")
+        return np_.value
+
+    def gather_doubles_(self, send, recv):
+        """recv[r * n + k] = rank r's send[k] (kf_exchange_all_gather_doubles),
+        queued on the current stream."""
+        if recv.numel() != send.numel() * self.world or send.dtype != torch.float64 or \
+                recv.dtype != torch.float64 or not (send.is_cuda and recv.is_cuda):
+            raise ValueError("gather_doubles_: recv holds world * send.numel() float64 values")
+        rc = self.lib.kf_exchange_all_gather_doubles(
+            self._h, send.data_ptr(), recv.data_ptr(), send.numel(),
+            torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(rc, "kf_exchange_all_gather_doubles")
+        return recv
+
+    def adam_gated_step_(self, param_buckets, grad_buckets, master_shards, exp_avg_shards,
+                         exp_avg_sq_shards, hyper, np_, gate, states, group, key=None):
+        """Half two (kf_exchange_adam_gated_batch): the gated update on this
+        rank's shards (ops.adam_update_batch_gated_'s kernel, or with
+        master_shards ops.adam_master_update_batch_gated_'s) with the one
+        `hyper`, `np_` as reduce_shards_ returned it, the gate and step state
+        `group` of `states`; then the parameter buckets' in-place all-gather.
+        Queued on the current stream."""
+        params, grads = list(param_buckets), list(grad_buckets)
+        with_master = master_shards is not None
+        shards = [list(s) for s in ((master_shards,) if with_master else ()) +
+                  (exp_avg_shards, exp_avg_sq_shards)]
+        if not all(len(x) == len(params) for x in [grads] + shards):
+            raise ValueError("adam_gated_step_: one grad bucket and %d state shards per bucket"
+                             % len(shards))
+        if not params:
+            return params
+        self._shard_tables("adam_gated_step_", params, grads, shards)
+        from . import ops
+        ops._check_gate(gate, states, int(group) + 1)
+        tables = [_lib.ptr_array([t.data_ptr() for t in s]) for s in shards]
+        rc = self.lib.kf_exchange_adam_gated_batch(
+            self._h, _lib.ptr_array([p.data_ptr() for p in params]),
+            _lib.ptr_array([g.data_ptr() for g in grads]), tables[0] if with_master else None,
+            tables[-2], tables[-1], _arr(ctypes.c_size_t, [p.numel() for p in params]),
+            len(params), int(kungfu_dtype(params[0])), int(np_),
+            _lib.adam_hyper_array([dict(hyper, step=1)]), gate.data_ptr(),
+            ops._state_ptr(states, group), torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(rc, "kf_exchange_adam_gated_batch")
         return params
 
     def all_reduce_named(self, name, buf, op="sum", average=False, stream=None, callback=None):

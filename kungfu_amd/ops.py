@@ -284,6 +284,141 @@ def adam_master_update_batch_(params16, grads16, masters, exp_avgs, exp_avg_sqs,
     return params
 
 
+def new_step_gate(device, loss_scale=1.0):
+    """A kf_step_gate on `device` as a uint8 tensor: zero-filled, with the
+    initial loss scale (1.0 without loss scaling)."""
+    import numpy as np
+    a = np.zeros(1, _lib.step_gate_dtype())
+    a["loss_scale"] = loss_scale
+    return torch.from_numpy(a.view(np.uint8).copy()).to(device)
+
+
+def new_step_states(device, ngroup, steps=None, betas=None):
+    """kf_step_state[ngroup] on `device` as a uint8 tensor: zero-filled with
+    both pows 1, or, resuming, step = steps[j] and the pows Python's
+    beta ** step for betas[j] = (beta1, beta2)."""
+    import numpy as np
+    a = np.zeros(max(1, ngroup), _lib.step_state_dtype())
+    a["beta1_pow"] = a["beta2_pow"] = 1.0
+    for j, t in enumerate(steps or []):
+        a["step"][j] = int(t)
+        a["beta1_pow"][j] = float(betas[j][0]) ** int(t)
+        a["beta2_pow"][j] = float(betas[j][1]) ** int(t)
+    return torch.from_numpy(a.view(np.uint8).copy()).to(device)
+
+
+def read_step_gate(gate):
+    """The gate as a numpy record (synchronises with the device)."""
+    return gate.cpu().numpy().view(_lib.step_gate_dtype())[0]
+
+
+def read_step_states(states):
+    """The step states as a numpy record array (synchronises)."""
+    return states.cpu().numpy().view(_lib.step_state_dtype())
+
+
+def _check_gate(gate, states=None, ngroup=1):
+    ts = [gate] if states is None else [gate, states]
+    _check_dev(ts)
+    for t, size, what in ((gate, ctypes.sizeof(_lib.StepGate), "gate"),
+                          (states, ngroup * ctypes.sizeof(_lib.StepState), "step states")):
+        if t is not None and (t.dtype != torch.uint8 or t.numel() < size or t.data_ptr() % 8):
+            raise ValueError("the %s must be at least %d uint8 bytes, 8-byte aligned" % (what, size))
+
+
+def step_gate_update_(sq, world, nps, groups, states, gate, max_norm=0.0, growth_factor=1.0,
+                      backoff_factor=1.0, growth_interval=0, stream=None):
+    """One verdict of a gated optimizer step on the device (kf_step_gate_update,
+    kungfu_amd/csrc/kf_step_gate.hip). sq: fp64 device tensor of world *
+    len(nps) sums of squares, sq[r * nplan + k]; nps[k]: what plan k's gradients
+    are still to be divided by (0: nothing); groups[j]: dict with lr and betas;
+    states: new_step_states' tensor for them; gate: new_step_gate's. Writes
+    skip, grad_mul, grad_norm, the loss scale's update and, unless the step is
+    skipped, every group's step, pows, s2 and nss. No host sync."""
+    nps, groups = [int(n) for n in nps], list(groups)
+    _check_dev([sq])
+    _check_gate(gate, states if groups else None, len(groups))
+    if sq.dtype != torch.float64 or sq.numel() != int(world) * len(nps) or not nps:
+        raise ValueError("step_gate_update_: sq is world * len(nps) float64 values")
+    garr = (_lib.StepGroup * max(1, len(groups)))()
+    for a, h in zip(garr, groups):
+        a.lr = float(h["lr"])
+        a.beta1, a.beta2 = (float(b) for b in h.get("betas", (0.9, 0.999)))
+    rc = _lib.load().kf_step_gate_update(
+        sq.data_ptr(), int(world), len(nps), (ctypes.c_int * len(nps))(*nps), garr,
+        states.data_ptr() if groups else None, len(groups), float(max_norm or 0.0),
+        float(growth_factor), float(backoff_factor), int(growth_interval), gate.data_ptr(),
+        _stream(stream, gate.device))
+    _lib.check(rc, "kf_step_gate_update", source="")
+    return gate
+
+
+def _state_ptr(states, group):
+    return states.data_ptr() + int(group) * ctypes.sizeof(_lib.StepState)
+
+
+def adam_update_batch_gated_(params, grads, exp_avgs, exp_avg_sqs, hyper, gate, states, group=0,
+                             np_=0, stream=None):
+    """adam_update_batch_ under a step gate (kf_adam_update_batch_gated): one
+    `hyper` dict for every segment (lr, betas, eps, weight_decay, decoupled; no
+    step: the bias corrections are the device's), the gate and group `group`
+    of `states` as step_gate_update_ left them. A skipped step leaves params
+    and both states untouched; otherwise g is multiplied by the gate's
+    grad_mul directly after the /np_."""
+    params, grads = list(params), list(grads)
+    ms, vs = list(exp_avgs), list(exp_avg_sqs)
+    if not (len(params) == len(grads) == len(ms) == len(vs)):
+        raise ValueError("adam_update_batch_gated_: one grad, exp_avg and exp_avg_sq per param "
+                         "segment")
+    if not params:
+        return params
+    _check_dev(params + grads + ms + vs)
+    _check_gate(gate, states, int(group) + 1)
+    for p, g, m, v in zip(params, grads, ms, vs):
+        if p.dtype != params[0].dtype or \
+                any(x.numel() != p.numel() or x.dtype != p.dtype for x in (g, m, v)):
+            raise ValueError("adam_update_batch_gated_: shape/dtype mismatch")
+    cnt = (ctypes.c_size_t * len(params))(*[p.numel() for p in params])
+    rc = _lib.load().kf_adam_update_batch_gated(
+        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (params, grads, ms, vs)],
+        cnt, len(params), int(kungfu_dtype(params[0])), int(np_),
+        _lib.adam_hyper_array([dict(hyper, step=1)]), gate.data_ptr(), _state_ptr(states, group),
+        _stream(stream, params[0].device))
+    _lib.check(rc, "kf_adam_update_batch_gated", source="")
+    return params
+
+
+def adam_master_update_batch_gated_(params16, grads16, masters, exp_avgs, exp_avg_sqs, hyper, gate,
+                                    states, group=0, np_=0, stream=None):
+    """adam_master_update_batch_ under a step gate
+    (kf_adam_master_update_batch_gated); hyper, gate, states and group as
+    adam_update_batch_gated_ takes them. A skipped step leaves params16,
+    masters and both states untouched."""
+    params, grads = list(params16), list(grads16)
+    ws, ms, vs = list(masters), list(exp_avgs), list(exp_avg_sqs)
+    if not (len(params) == len(grads) == len(ws) == len(ms) == len(vs)):
+        raise ValueError("adam_master_update_batch_gated_: one grad, master, exp_avg and "
+                         "exp_avg_sq per param segment")
+    if not params:
+        return params
+    _check_dev(params + grads + ws + ms + vs)
+    _check_gate(gate, states, int(group) + 1)
+    if params[0].dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("adam_master_update_batch_gated_: bf16 or f16 parameters")
+    for p, g, w, m, v in zip(params, grads, ws, ms, vs):
+        if p.dtype != params[0].dtype or g.dtype != p.dtype or g.numel() != p.numel() or \
+                any(x.numel() != p.numel() or x.dtype != torch.float32 for x in (w, m, v)):
+            raise ValueError("adam_master_update_batch_gated_: shape/dtype mismatch")
+    cnt = (ctypes.c_size_t * len(params))(*[p.numel() for p in params])
+    rc = _lib.load().kf_adam_master_update_batch_gated(
+        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (params, grads, ws, ms, vs)],
+        cnt, len(params), int(kungfu_dtype(params[0])), int(np_),
+        _lib.adam_hyper_array([dict(hyper, step=1)]), gate.data_ptr(), _state_ptr(states, group),
+        _stream(stream, params[0].device))
+    _lib.check(rc, "kf_adam_master_update_batch_gated", source="")
+    return params
+
+
 _NORM_DTYPES = (torch.float32, torch.float16, torch.bfloat16, torch.float64)
 
 

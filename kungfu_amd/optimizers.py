@@ -853,15 +853,15 @@ class _ShardedAdam(_Sharded):
     def _kf_build_sharded(self):
         import torch
         super()._kf_build_sharded()
-        if not self._kf_master:
-            return
         ex = self._kf_ex
-        for G in self._kf_groups:
+        for G in self._kf_groups if self._kf_master else []:
             if G["pb"].buckets and G["pb"].buckets[0].element_size() == 2:
                 G["w"] = self._kf_zero_shards(G, torch.float32)
                 for b, w in zip(G["pb"].buckets, G["w"]):  # the widening is exact
                     q = w.numel()
                     w.copy_(b[ex.rank * q:(ex.rank + 1) * q])
+        if self._kf_gated:
+            self._kf_build_gated()
 
     def _kf_states(self, G):
         """The group's zeroed exp_avg / exp_avg_sq shards, allocated on the
@@ -872,12 +872,156 @@ class _ShardedAdam(_Sharded):
             G["m"], G["v"] = self._kf_zero_shards(G, dtype), self._kf_zero_shards(G, dtype)
         return G["m"], G["v"]
 
+    # -- the gated step ---------------------------------------
+    _kf_gated = False
+    _kf_max_norm = 0.0
+    _kf_rule = None     # init_scale, growth_factor, backoff_factor, growth_interval
+    _kf_gate = None     # kf_step_gate on the device, a uint8 tensor
+    _kf_gstates = None  # kf_step_state per bucket group
+
+    def _kf_gate_ops(self):
+        """Where the norm pass, the verdict and the gated updates run: the
+        exchange's epilogue (collective.Exchange; injectable for CPU tests)
+        or the HIP one."""
+        from .collective import HipEpilogue
+        ep = getattr(self._kf_ex, "epilogue", None)
+        return ep if hasattr(ep, "step_gate_update_") else HipEpilogue()
+
+    def _kf_gate_tensor(self):
+        """The gate, created when first needed (scale_loss comes before the
+        first step) on the parameters' device."""
+        if self._kf_gate is None:
+            from . import ops
+            devices = {p.device for p in self._kf_params}
+            if len(devices) != 1:
+                raise ValueError("ShardedAdamOptimizer: a gated step needs all parameters on one "
+                                 "device")
+            self._kf_gate = ops.new_step_gate(devices.pop(), self._kf_rule["init_scale"])
+        return self._kf_gate
+
+    def _kf_build_gated(self):
+        """Once, with the buckets: the groups' step states, one norm plan per
+        dtype over this rank's gradient shards (fixed addresses), and the
+        buffers of the plans' sums of squares."""
+        import torch
+        from . import ops
+        gate, ex, ep = self._kf_gate_tensor(), self._kf_ex, self._kf_gate_ops()
+        self._kf_gstates = ops.new_step_states(gate.device, len(self._kf_groups))
+        by = {}
+        for j, G in enumerate(self._kf_groups):
+            by.setdefault(G["pb"].buckets[0].dtype, []).append(j)
+        self._kf_plans = []
+        for dtype, js in by.items():
+            shards = [t for j in js
+                      for t in ex.grad_shards_(self._kf_groups[j]["gb"].buckets, ("gated", j))]
+            plan = ep.sq_norm_plan(shards)
+            out = torch.zeros(len(shards) + 1, dtype=torch.float64, device=gate.device)
+            self._kf_plans.append((js, plan, out))
+        n = len(self._kf_plans)
+        self._kf_sq = torch.zeros(n, dtype=torch.float64, device=gate.device)
+        self._kf_sq_all = torch.zeros(n * ex.world, dtype=torch.float64, device=gate.device)
+
+    def _kf_step_gated(self):
+        """A (every group's reduce), B (the norm pass), C (the all-gather of
+        the plans' sums), D (the verdict), E (every group's gated update and
+        the parameters' all-gather): queued, nothing waits for the verdict."""
+        ex, ep, groups = self._kf_ex, self._kf_gate_ops(), self._kf_groups
+        for j, G in enumerate(groups):
+            self._kf_states(G)
+            G["np"] = ex.reduce_shards_(G["gb"].buckets, ("gated", j))
+        nps = []
+        for k, (js, plan, out) in enumerate(self._kf_plans):
+            if len({groups[j]["np"] for j in js}) != 1:
+                raise ValueError("ShardedAdamOptimizer: bucket groups of one dtype were reduced "
+                                 "differently")
+            nps.append(groups[js[0]]["np"])
+            plan.run("sq", out=out)
+            self._kf_sq[k:k + 1].copy_(out[-1:])
+        ex.gather_doubles_(self._kf_sq, self._kf_sq_all)
+        hs = []
+        for G in groups:
+            pg = self.param_groups[G["gi"]]  # read at every step: schedulers change them
+            hs.append({"lr": float(pg["lr"]), "betas": tuple(float(b) for b in pg["betas"]),
+                       "eps": float(pg["eps"]), "weight_decay": float(pg["weight_decay"]),
+                       "decoupled": self._kf_decoupled})
+        r = self._kf_rule
+        ep.step_gate_update_(self._kf_sq_all, ex.world, nps, hs, self._kf_gstates, self._kf_gate,
+                             max_norm=self._kf_max_norm, growth_factor=r["growth_factor"],
+                             backoff_factor=r["backoff_factor"],
+                             growth_interval=r["growth_interval"])
+        for j, (G, h) in enumerate(zip(groups, hs)):
+            ex.adam_gated_step_(G["pb"].buckets, G["gb"].buckets, G["w"], G["m"], G["v"], h,
+                                G["np"], self._kf_gate, self._kf_gstates, j, ("gated", j))
+
+    def _kf_need_gate(self, what):
+        if not self._kf_gated:
+            raise ValueError("ShardedAdamOptimizer.%s needs max_grad_norm or loss_scale" % what)
+
+    def scale_loss(self, loss):
+        """loss * loss_scale, a device multiply by the gate's current scale:
+        no host sync. Call backward() on the result."""
+        import torch
+        self._kf_need_gate("scale_loss")
+        # kf_step_gate.loss_scale: the fp32 word at byte 8
+        return loss * self._kf_gate_tensor()[8:12].view(torch.float32)[0]
+
+    def _kf_read_gate(self):
+        from . import ops
+        self._kf_need_gate("gate state")
+        return ops.read_step_gate(self._kf_gate_tensor())
+
+    def loss_scale_value(self):
+        """The loss scale the next loss is to be multiplied by (synchronises)."""
+        return float(self._kf_read_gate()["loss_scale"])
+
+    def last_grad_norm(self):
+        """The last step's norm of the unscaled, averaged gradient before
+        clipping; inf or NaN on a skipped step (synchronises)."""
+        return float(self._kf_read_gate()["grad_norm"])
+
+    def skipped_steps(self):
+        """Steps skipped so far for non-finite gradients (synchronises)."""
+        return int(self._kf_read_gate()["skipped"])
+
+    def applied_steps(self):
+        """Steps applied so far (synchronises)."""
+        return int(self._kf_read_gate()["applied"])
+
+    def scaler_state(self):
+        """{"loss_scale", "good_steps"}: the loss scale and its growth tracker,
+        for a checkpoint beside state_buffers() (synchronises)."""
+        g = self._kf_read_gate()
+        return {"loss_scale": float(g["loss_scale"]), "good_steps": int(g["good_steps"])}
+
+    def load_scaler_state(self, state):
+        """scaler_state()'s result back into the gate; the counters of
+        applied and skipped steps start again at zero."""
+        import numpy as np
+        import torch
+        from . import _lib
+        self._kf_need_gate("load_scaler_state")
+        gate = self._kf_gate_tensor()
+        a = np.zeros(1, _lib.step_gate_dtype())
+        a["loss_scale"], a["good_steps"] = float(state["loss_scale"]), int(state["good_steps"])
+        gate.copy_(torch.from_numpy(a.view(np.uint8).copy()))
+
+    def _kf_steps(self):
+        """Every bucket group's step count: the device's on the gated path."""
+        if not self._kf_gated or self._kf_gstates is None:
+            return [G["step"] for G in self._kf_groups or []]
+        from . import ops
+        return [int(t) for t in ops.read_step_states(self._kf_gstates)["step"]]
+
     def step(self, closure=None):
         loss = self._kf_closure(closure)
         if self._kf_groups is None:
             self._kf_build_sharded()
         for G in self._kf_groups:
             _SyncSGD._kf_place(G["ps"], G["gb"])
+        if self._kf_gated:
+            self._kf_step_gated()
+            _finish(self._kf_ex)
+            return loss
         for G in self._kf_groups:
             pg = self.param_groups[G["gi"]]  # read at every step: schedulers change them
             ms, vs = self._kf_states(G)
@@ -903,12 +1047,13 @@ class _ShardedAdam(_Sharded):
         weights gives fp32 exp_avg and exp_avg_sq and a third entry, "master",
         the fp32 master copy of the parameter."""
         out = {}
-        for G in self._kf_groups or []:
-            if G["m"] is None or G["step"] == 0:
+        # gated: the step counts are the device's (skipped steps do not count)
+        for G, step in zip(self._kf_groups or [], self._kf_steps()):
+            if G["m"] is None or step == 0:
                 continue
             m, v = self._kf_unshard(G, G["m"]), self._kf_unshard(G, G["v"])
             for p in m:
-                out[p] = {"step": G["step"], "exp_avg": m[p], "exp_avg_sq": v[p]}
+                out[p] = {"step": step, "exp_avg": m[p], "exp_avg_sq": v[p]}
             if G["w"] is not None:
                 for p, w in self._kf_unshard(G, G["w"]).items():
                     out[p]["master"] = w
@@ -930,7 +1075,7 @@ class _ShardedAdam(_Sharded):
         the master."""
         if self._kf_groups is None:
             self._kf_build_sharded()
-        for G in self._kf_groups:
+        for j, G in enumerate(self._kf_groups):
             steps = {int(mapping[p]["step"]) for p in G["ps"] if p in mapping}
             if not steps:
                 continue
@@ -943,6 +1088,20 @@ class _ShardedAdam(_Sharded):
             if G["w"] is not None:
                 self._kf_reshard(G, G["w"], lambda p: mapping.get(p, {}).get("master", p.data))
             G["step"] = steps.pop()
+            if self._kf_gated:
+                self._kf_seed_state(j, G["step"], self.param_groups[G["gi"]]["betas"])
+
+    def _kf_seed_state(self, j, step, betas):
+        """Bucket group j's device step state resumed at `step`: the running
+        products start from Python's beta ** step."""
+        import numpy as np
+        import torch
+        from . import _lib, ops
+        a = ops.read_step_states(self._kf_gstates).copy()
+        a[j] = np.zeros(1, _lib.step_state_dtype())[0]
+        a["step"][j] = step
+        a["beta1_pow"][j], a["beta2_pow"][j] = float(betas[0]) ** step, float(betas[1]) ** step
+        self._kf_gstates.copy_(torch.from_numpy(a.view(np.uint8).copy()))
 
 
 def ShardedSGDOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20):
@@ -993,7 +1152,7 @@ def ShardedSGDOptimizer(optimizer, named_parameters=None, exchange=None, bucket_
 
 
 def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20,
-                         master_weights=False):
+                         master_weights=False, max_grad_norm=None, loss_scale=None):
     """Synchronous Adam / AdamW with the optimizer update and its state
     sharded over the ranks, as ShardedSGDOptimizer does for SGD: every step is
 
@@ -1041,11 +1200,41 @@ def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket
     parameter equals the narrowing of its master on every rank, and no other
     rounding to 16 bits happens (kf_adam_master_update_batch). Updates below
     half a 16-bit ulp accumulate in the master instead of being rounded away.
-    f16 parameters are accepted; there is no loss scaling, no inf / NaN step
-    skipping and no gradient clipping here, so f16 users must keep their
-    gradients finite themselves. f32 and f64 groups take the path above and
-    give the same bits as without the flag. state_buffers() carries the
-    master as a third entry, "master".
+    f16 parameters are accepted. Without the two keywords below there is
+    no loss scaling, no inf / NaN step skipping and no gradient clipping: f16
+    users must then keep their gradients finite themselves. f32 and f64
+    groups take the path above and give the same bits as without the flag.
+    state_buffers() carries the master as a third entry, "master".
+
+    max_grad_norm / loss_scale: with either set, every step is
+    gated by one verdict computed on the device over all bucket groups; with
+    both None nothing changes. The step becomes: every group's reduce-scatter;
+    one norm pass over this rank's shards (ops.SegNorm, fp64); an all-gather
+    of 8 bytes per dtype and rank; the gate kernel (ops.step_gate_update_);
+    every group's gated update (ops.adam_update_batch_gated_ /
+    ops.adam_master_update_batch_gated_) and the parameters' all-gather. All
+    of it is queued; the host never waits for the verdict.
+      * max_grad_norm: a positive number. The gradients are multiplied by
+        min(1, max_grad_norm / (norm + 1e-6)), torch's clip_grad_norm_, with
+        the global norm of the unscaled, averaged gradient over all groups.
+      * loss_scale: a number (static), "dynamic" (torch.amp.GradScaler's
+        rule and defaults: 65536, x2 after 2000 good steps, x0.5 on a skip) or
+        a dict overriding init_scale, growth_factor, backoff_factor,
+        growth_interval. Train on scale_loss(loss).backward(): the update
+        divides the gradients by the scale the loss was multiplied by.
+      * A step whose gradients hold an inf or a NaN on any rank is skipped on
+        every rank: parameters, masters and state keep their bits, the step
+        count and the bias corrections do not advance, and a dynamic scale
+        backs off. Clipping without a loss scale skips such steps too.
+      * The bias corrections are running products in double kept on the
+        device (the host does not know which steps were skipped), not
+        1 - beta ** step; load_state_buffers seeds them with beta ** step.
+      * loss_scale_value(), last_grad_norm(), skipped_steps(),
+        applied_steps(), scaler_state() and state_buffers() read the device
+        state and are the only calls that synchronise; load_scaler_state()
+        restores the scale and its growth tracker.
+    Gating takes every dtype the optimizer takes; f16 still needs
+    master_weights=True (TypeError on the first step otherwise).
 
     state_buffers() (collective) and load_state_buffers(mapping) are the
     checkpoint path for the sharded state.
@@ -1077,4 +1266,60 @@ def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket
         opt._kf_master = True
         opt._kf_dtypes = ("float32", "float16", "bfloat16", "float64")
         opt._kf_dtype_words = "f32, f16, bf16 and f64"
+    if max_grad_norm is not None or loss_scale is not None:
+        opt._kf_max_norm, opt._kf_rule = _gate_rule(max_grad_norm, loss_scale)
+        for method in ("reduce_shards_", "gather_doubles_", "adam_gated_step_"):
+            if not hasattr(opt._kf_ex, method):
+                raise ValueError("ShardedAdamOptimizer(max_grad_norm / loss_scale) needs an "
+                                 "exchange with %s() (collective.Exchange or "
+                                 "exchange.NativeExchange)" % method)
+        opt._kf_gated = True
     return opt
+
+
+# torch.amp.GradScaler's defaults
+_DYNAMIC_SCALE = {"init_scale": 65536.0, "growth_factor": 2.0, "backoff_factor": 0.5,
+                  "growth_interval": 2000}
+
+
+def _gate_rule(max_grad_norm, loss_scale):
+    """(max_norm, rule) of a gated ShardedAdamOptimizer from its two keywords,
+    ValueError for anything else."""
+    import math
+    max_norm = 0.0
+    if max_grad_norm is not None:
+        if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or \
+                not (0 < max_grad_norm < math.inf):
+            raise ValueError("ShardedAdamOptimizer: max_grad_norm must be a positive finite "
+                             "number or None, not %r" % (max_grad_norm,))
+        max_norm = float(max_grad_norm)
+    static = {"init_scale": 1.0, "growth_factor": 1.0, "backoff_factor": 1.0, "growth_interval": 0}
+    if loss_scale is None:
+        return max_norm, static
+    if isinstance(loss_scale, str):
+        if loss_scale != "dynamic":
+            raise ValueError("ShardedAdamOptimizer: loss_scale must be None, a positive number, "
+                             "'dynamic' or a dict, not %r" % (loss_scale,))
+        return max_norm, dict(_DYNAMIC_SCALE)
+    if isinstance(loss_scale, dict):
+        unknown = set(loss_scale) - set(_DYNAMIC_SCALE)
+        if unknown:
+            raise ValueError("ShardedAdamOptimizer: loss_scale has unknown keys %s (known: %s)"
+                             % (sorted(unknown), sorted(_DYNAMIC_SCALE)))
+        rule = dict(_DYNAMIC_SCALE, **loss_scale)
+        for k in ("init_scale", "growth_factor", "backoff_factor"):
+            v = rule[k]
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0 < v < math.inf):
+                raise ValueError("ShardedAdamOptimizer: loss_scale[%r] must be a positive finite "
+                                 "number, not %r" % (k, v))
+            rule[k] = float(v)
+        n = rule["growth_interval"]
+        if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+            raise ValueError("ShardedAdamOptimizer: loss_scale['growth_interval'] must be an "
+                             "integer >= 0, not %r" % (n,))
+        return max_norm, rule
+    if isinstance(loss_scale, bool) or not isinstance(loss_scale, (int, float)) or \
+            not (0 < loss_scale < math.inf):
+        raise ValueError("ShardedAdamOptimizer: loss_scale must be None, a positive number, "
+                         "'dynamic' or a dict, not %r" % (loss_scale,))
+    return max_norm, dict(static, init_scale=float(loss_scale))

@@ -75,5 +75,6 @@ def ShardedAdamOptimizer(optimizer, named_parameters, **kwargs):
     """kungfu_amd.optimizers.ShardedAdamOptimizer with `named_parameters`
     positional. Keywords pass through: `exchange`, `bucket_bytes`, and
     `master_weights=True` for fp32 master weights and fp32 state on the shard
-    of bf16 / f16 parameters."""
+    of bf16 / f16 parameters, and `max_grad_norm` / `loss_scale` for the gated
+    step (gradient-norm clipping, loss scaling, inf / NaN step skipping)."""
     return _opt.ShardedAdamOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
