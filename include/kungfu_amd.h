@@ -334,6 +334,104 @@ int kf_adam_master_update_batch_gated(void *const *params16, const void *const *
                                       const kf_step_gate *gate, const kf_step_state *state,
                                       void *stream);
 
+/* ---- LAMB: layer-wise trust ratios on the sharded step --------------------
+ *
+ * LAMB (kungfu_amd/csrc/kf_lamb.hip) where the averaged
+ * gradient, exp_avg and exp_avg_sq only exist as one rank's shard and a tensor
+ * straddles shard boundaries at element offsets. A step is two element-wise
+ * passes with the norms between them. Every parenthesis is one IEEE operation
+ * in the compute type C, no FMA contraction; the sqrt and the divisions are
+ * correctly rounded; scalars are computed in double and cast once to C, as
+ * kf_adam_update_batch does. C is f32 for f32 parameters and f64 for f64; for
+ * bf16 / f16 parameters C is f32 on the fp32 master copy.
+ *
+ * Pass 1, moments, per element of this rank's shard:
+ *   g = np > 0 ? g / np : g                     (kf_bucket_div's rounding, as Adam)
+ *   m = (b1*m) + (c1*g)                         c1 = 1 - beta1
+ *   v = (b2*v) + (c2*(g*g))                     c2 = 1 - beta2
+ *   d = (sqrt(v) / s2) + eps                    s2 = sqrt(bias_correction2)
+ *   u = rb1 * (m / d)                           rb1 = (C)(1 / bias_correction1)
+ *   weight_decay != 0:  u = u + (wd*p)
+ * p is read and not written; m, v and u are written; u is a scratch shard of
+ * type C beside the state shards, never the gradient's own storage. 7 accesses
+ * per element: 28 bytes for f32, 26 on the master path (g is 2 bytes there).
+ *
+ * Norms: one kf_segnorm plan (below) of 2T segments on every rank, T the
+ * number of tensors: segment t is the piece of tensor t's parameters (of its
+ * master copy, on the master path) that lies in this rank's shard, with count
+ * 0 where the rank holds none of it; segment T + t is the same piece of u.
+ * out[0 .. 2T) is this rank's send vector of kf_exchange_all_gather_doubles,
+ * which gives sq[r][k].
+ *
+ * Trust, one lane per tensor, fp64:
+ *   P = 0; for r in rank order: P = P + sq[r][t]      U likewise from sq[r][T + t]
+ *   wn = sqrt(P); un = sqrt(U)
+ *   ratio = (adapt_t && wn > 0 && un > 0) ? wn / un : 1
+ *   trust_clip > 0:  ratio = ratio < trust_clip ? ratio : trust_clip
+ *   nlr[t] = -(lr_t * ratio); ratio[t] = ratio
+ * lr_t and adapt_t are those of tensor t's group, groups[group_of[t]].
+ *
+ * Pass 2, apply, per element of a piece:  p = p + ((C)nlr[t] * u); on the
+ * master path the same on the master, and params16 = narrow(master),
+ * round-to-nearest-even. Elements outside every piece (bucket padding) are not
+ * touched. 3 accesses per element.
+ *
+ * Non-finite gradients are NOT skipped: an inf or a NaN in a gradient reaches
+ * m, v, u, the tensor's norms and through them its parameters, as it does in
+ * torch.optim.Adam. There is no gate on this path. */
+
+/* The moments pass over nb segments of one dtype, one launch per 24 of them
+ * (f32, f64) or per 32 (master path). kf_adam_update_batch's conventions:
+ * every pointer 16-byte aligned, segment b has counts[b] elements and its own
+ * hyper[b], whose lr and decoupled are ignored; bias corrections must be > 0.
+ * kf_lamb_moments_batch takes f32 and f64 (anything else, bf16 and f16 among
+ * them: KF_ERR_DTYPE); params, grads, exp_avgs, exp_avg_sqs and updates all
+ * have that type. kf_lamb_master_moments_batch takes dt = bf16 or f16, the
+ * type of grads16 alone: masters, exp_avgs, exp_avg_sqs and updates are fp32.
+ * params / masters and the gradients are only read. */
+int kf_lamb_moments_batch(const void *const *params, const void *const *grads,
+                          void *const *exp_avgs, void *const *exp_avg_sqs, void *const *updates,
+                          const size_t *counts, int nb, KungFu_Datatype dt, int np,
+                          const kf_adam_hyper *hyper, void *stream);
+int kf_lamb_master_moments_batch(const void *const *grads16, const void *const *masters,
+                                 void *const *exp_avgs, void *const *exp_avg_sqs,
+                                 void *const *updates, const size_t *counts, int nb,
+                                 KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
+                                 void *stream);
+
+/* The trust ratios of ntensor tensors. sq is a device array of world * 2 *
+ * ntensor doubles, sq[r * 2 * ntensor + k]; group_of (device, ntensor ints,
+ * uploaded once by the caller) maps a tensor to its group; groups (host,
+ * ngroup entries, read before the call returns) come with every call because
+ * schedulers change lr. nlr and ratio are device arrays of ntensor doubles.
+ * A tensor whose group index is outside [0, ngroup) is not written. Any
+ * ntensor >= 1, world >= 1 and ngroup >= 1: one launch per 16 groups, on the
+ * same stream. trust_clip <= 0 means no clipping. No atomics, no host sync,
+ * no allocation. */
+typedef struct { double lr; int adapt; } kf_lamb_group;
+int kf_lamb_trust_update(const double *sq, int world, int ntensor, const int *group_of,
+                         const kf_lamb_group *groups, int ngroup, double trust_clip, double *nlr,
+                         double *ratio, void *stream);
+
+/* The apply pass as a plan (kf_segnorm's shape): kf_lamb_apply_create uploads
+ * the piece table to HBM once; kf_lamb_apply_run is one launch whatever the
+ * number of pieces, and only queues it (no allocation, no host sync). Piece i
+ * is counts[i] elements at params[i] and updates[i] of dt (f32 or f64,
+ * params16 == NULL), or, with dt = bf16 / f16, fp32 elements at params[i] (the
+ * master) and updates[i] and 16-bit ones at params16[i]; tensors[i] in
+ * [0, ntensor) indexes nlr. Pointers are aligned to the element only, but a
+ * piece's arrays must share their element offset from a 16-byte boundary
+ * (KF_ERR_ARG otherwise; pieces cut from shards that start 16-byte aligned
+ * do). A count may be 0 and npiece may be 0. Returns NULL on failure with
+ * kf_last_error() set. nlr is kf_lamb_trust_update's, ntensor doubles. */
+typedef struct kf_lamb_apply kf_lamb_apply_t; /* opaque plan */
+kf_lamb_apply_t *kf_lamb_apply_create(void *const *params, const void *const *updates,
+                                      void *const *params16 /* NULL: f32, f64 */,
+                                      const size_t *counts, const int *tensors, int npiece,
+                                      int ntensor, KungFu_Datatype dt);
+int kf_lamb_apply_run(kf_lamb_apply_t *p, const double *nlr, void *stream);
+void kf_lamb_apply_destroy(kf_lamb_apply_t *p);
+
 /* ---- gradient monitors: segmented squared norms ------------------------- */
 
 /* What MonitorGradientNoiseScaleOptimizer and MonitorGradientVarianceOptimizer
@@ -919,6 +1017,16 @@ int kf_exchange_adam_gated_batch(kf_exchange_t *ex, void *const *params, void *c
  * 1 on the built-in transport is a copy. */
 int kf_exchange_all_gather_doubles(kf_exchange_t *ex, const double *send, double *recv, int n,
                                    void *stream);
+/* Phase 3 alone: the in-place all-gather of the parameter buckets, params[b] +
+ * rank * q (q = counts[b] / world elements) to every rank, for a step whose
+ * update ran outside the exchange (LAMB). It makes
+ * kf_exchange_adam_batch's up-front checks on every rank before any
+ * collective: a float dtype, every counts[b] a multiple of the world, buckets
+ * and shards 16-byte aligned. World 1 on the built-in transport does nothing.
+ * Queued on `stream`; un-pipelined; follows kf_exchange_set_timing under
+ * phase 3. */
+int kf_exchange_gather_params_batch(kf_exchange_t *ex, void *const *params, const size_t *counts,
+                                    int nb, KungFu_Datatype dt, void *stream);
 /* Pipelined schedule for the batch calls (default 1 = off): the buckets of a
  * call are split into `groups` groups of consecutive buckets of about equal
  * bytes; the RCCL phases stay on the caller's stream in the same order on

@@ -129,6 +129,13 @@ EXPORTED = (
     "kf_exchange_reduce_shards_batch",
     "kf_exchange_adam_gated_batch",
     "kf_exchange_all_gather_doubles",
+    "kf_lamb_moments_batch",
+    "kf_lamb_master_moments_batch",
+    "kf_lamb_trust_update",
+    "kf_lamb_apply_create",
+    "kf_lamb_apply_run",
+    "kf_lamb_apply_destroy",
+    "kf_exchange_gather_params_batch",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -192,6 +199,11 @@ def adam_hyper_array(hypers):
         a.bias_correction1, a.bias_correction2 = 1.0 - b1 ** t, 1.0 - b2 ** t
         a.decoupled = int(bool(h.get("decoupled", False)))
     return arr
+
+
+class LambGroup(ctypes.Structure):
+    """kf_lamb_group (include/kungfu_amd.h): what the trust ratios need of a group."""
+    _fields_ = [("lr", ctypes.c_double), ("adapt", ctypes.c_int)]
 
 
 class StepGate(ctypes.Structure):
@@ -543,6 +555,25 @@ def load():
     lib.kf_exchange_adam_gated_batch.restype = c_int
     lib.kf_exchange_all_gather_doubles.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p]
     lib.kf_exchange_all_gather_doubles.restype = c_int
+    lib.kf_lamb_moments_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_void_p),
+                                          P(c_void_p), P(c_size_t), c_int, c_int, c_int,
+                                          P(AdamHyper), c_void_p]
+    lib.kf_lamb_moments_batch.restype = c_int
+    lib.kf_lamb_master_moments_batch.argtypes = lib.kf_lamb_moments_batch.argtypes
+    lib.kf_lamb_master_moments_batch.restype = c_int
+    lib.kf_lamb_trust_update.argtypes = [c_void_p, c_int, c_int, c_void_p, P(LambGroup), c_int,
+                                         ctypes.c_double, c_void_p, c_void_p, c_void_p]
+    lib.kf_lamb_trust_update.restype = c_int
+    lib.kf_lamb_apply_create.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_size_t),
+                                         P(c_int), c_int, c_int, c_int]
+    lib.kf_lamb_apply_create.restype = c_void_p
+    lib.kf_lamb_apply_run.argtypes = [c_void_p, c_void_p, c_void_p]
+    lib.kf_lamb_apply_run.restype = c_int
+    lib.kf_lamb_apply_destroy.argtypes = [c_void_p]
+    lib.kf_lamb_apply_destroy.restype = None
+    lib.kf_exchange_gather_params_batch.argtypes = [c_void_p, P(c_void_p), P(c_size_t), c_int,
+                                                    c_int, c_void_p]
+    lib.kf_exchange_gather_params_batch.restype = c_int
     _lib = lib
     # HIP resources go back while the runtime is alive, before the C exit
     # handlers run (include/kungfu_amd.h kf_shutdown)

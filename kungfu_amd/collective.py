@@ -95,6 +95,26 @@ class HipEpilogue:
         return ops.adam_master_update_batch_gated_(params16, grads16, masters, exp_avgs,
                                                    exp_avg_sqs, hyper, gate, states, group, np_)
 
+    # -- LAMB --
+    def lamb_moments_(self, params, grads, exp_avgs, exp_avg_sqs, updates, hypers, np_):
+        """LAMB's moments pass over the shards (ops.lamb_moments_batch_)."""
+        return ops.lamb_moments_batch_(params, grads, exp_avgs, exp_avg_sqs, updates, hypers, np_)
+
+    def lamb_master_moments_(self, grads16, masters, exp_avgs, exp_avg_sqs, updates, hypers, np_):
+        """The same through fp32 master and state shards
+        (ops.lamb_master_moments_batch_)."""
+        return ops.lamb_master_moments_batch_(grads16, masters, exp_avgs, exp_avg_sqs, updates,
+                                              hypers, np_)
+
+    def lamb_trust_update_(self, sq, world, group_of, groups, nlr, ratio, trust_clip=0.0):
+        """The tensors' trust ratios (ops.lamb_trust_update_), one launch per 16 groups."""
+        return ops.lamb_trust_update_(sq, world, group_of, groups, nlr, ratio, trust_clip)
+
+    def lamb_apply_plan(self, params, updates, tensors, ntensor, params16=None):
+        """A plan whose run(nlr) applies the updates to the pieces
+        (ops.LambApplyPlan), built once over fixed views."""
+        return ops.LambApplyPlan(params, updates, tensors, ntensor, params16)
+
 
 def coalesce_runs(buckets):
     """Maximal runs of buckets that are consecutive in one storage, each as
@@ -512,6 +532,20 @@ class Exchange:
             return recv
         dist.all_gather_into_tensor(recv, send.clone(), group=self.group)
         return recv
+
+    def gather_params_(self, param_buckets):
+        """Phase 3 alone (the native exchange's kf_exchange_gather_params_batch):
+        every parameter bucket's in-place all-gather of the ranks' shards, for
+        a step whose update ran outside the exchange (LAMB). Nothing at world 1."""
+        params = list(param_buckets)
+        for p in params:
+            self._check(p)
+            if p.numel() % self.world:
+                raise ValueError("gather_params_: bucket sizes must be multiples of the world")
+        if self.world == 1 or not params:
+            return params
+        self._gather_params(params, self._marks())
+        return params
 
     def adam_gated_step_(self, param_buckets, grad_buckets, master_shards, exp_avg_shards,
                          exp_avg_sq_shards, hyper, np_, gate, states, group, key):

@@ -1868,6 +1868,36 @@ int kf_exchange_all_gather_doubles(kf_exchange_t *ex, const double *send, double
     return KF_OK;
 }
 
+int kf_exchange_gather_params_batch(kf_exchange_t *ex, void *const *params, const size_t *counts,
+                                    int nb, KungFu_Datatype dt, void *stream)
+{
+    const std::string fn = "kf_exchange_gather_params_batch: ";
+    if (!ex || nb < 0) return fail(KF_ERR_ARG, fn + "bad arguments");
+    if (!is_float(dt)) return fail(KF_ERR_DTYPE, fn + "f32, f16, bf16 and f64 only");
+    if (nb == 0) return KF_OK;
+    if (!params || !counts) return fail(KF_ERR_ARG, fn + "null table");
+    // every rank must reach the same verdict before any collective is queued
+    const size_t W = static_cast<size_t>(ex->world), sz = static_cast<size_t>(tsize(dt));
+    for (int b = 0; b < nb; ++b) {
+        if (counts[b] == 0) continue;
+        if (!params[b]) return fail(KF_ERR_ARG, fn + "null bucket");
+        if (counts[b] % W) {
+            return fail(KF_ERR_ARG, fn + "counts must be multiples of the world "
+                                         "(padded buckets, no tails)");
+        }
+        if ((reinterpret_cast<uintptr_t>(params[b]) % 16) || (W > 1 && (counts[b] / W * sz) % 16)) {
+            return fail(KF_ERR_ARG, fn + "buckets and their shards must start 16-byte aligned");
+        }
+    }
+    DeviceGuard g(ex->device);
+    std::lock_guard<std::mutex> lk(ex->mu);
+    if (ex->world == 1 && ex->builtin) return KF_OK;
+    // phase 3 of a plain batch call whose buckets are the parameters
+    std::vector<const void *> snd(params, params + nb);
+    return ex->batch(snd.data(), params, counts, nb, dt, KungFu_SUM, 0, KF_ALGO_AUTO,
+                     static_cast<hipStream_t>(stream), nullptr, 4);
+}
+
 int kf_exchange_adam_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
                            void *const *exp_avg_shards, void *const *exp_avg_sq_shards,
                            const size_t *counts, int nb, KungFu_Datatype dt,

@@ -369,6 +369,22 @@ class NativeExchange:
         _lib.check(rc, "kf_exchange_all_gather_doubles")
         return recv
 
+    def gather_params_(self, param_buckets):
+        """Phase 3 alone (kf_exchange_gather_params_batch): the parameter
+        buckets' in-place all-gather of the ranks' shards, queued on the
+        current stream, for a step whose update ran outside the exchange
+        (LAMB). Nothing at world 1 on the built-in transport."""
+        params = list(param_buckets)
+        if not params:
+            return params
+        self._check(params)
+        rc = self.lib.kf_exchange_gather_params_batch(
+            self._h, _lib.ptr_array([p.data_ptr() for p in params]),
+            _arr(ctypes.c_size_t, [p.numel() for p in params]), len(params),
+            int(kungfu_dtype(params[0])), torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(rc, "kf_exchange_gather_params_batch")
+        return params
+
     def adam_gated_step_(self, param_buckets, grad_buckets, master_shards, exp_avg_shards,
                          exp_avg_sq_shards, hyper, np_, gate, states, group, key=None):
         """Half two (kf_exchange_adam_gated_batch): the gated update on this

@@ -419,6 +419,177 @@ def adam_master_update_batch_gated_(params16, grads16, masters, exp_avgs, exp_av
     return params
 
 
+# -- LAMB (include/kungfu_amd.h "LAMB") -------------------------
+
+def lamb_moments_batch_(params, grads, exp_avgs, exp_avg_sqs, updates, hypers, np_=0, stream=None):
+    """LAMB's moments pass over many flat f32 or f64 segments, one launch per
+    24 of them (kf_lamb_moments_batch, kungfu_amd/csrc/kf_lamb.hip):
+
+      g = grads[b] / np_ (np_ > 0)
+      m = b1 * m + (1 - b1) * g ; v = b2 * v + (1 - b2) * g * g
+      u = (m / (1 - b1**step)) / (sqrt(v) / sqrt(1 - b2**step) + eps) + wd * p
+
+    rounded as include/kungfu_amd.h states. exp_avgs and exp_avg_sqs are
+    updated in place, updates[b] is written, params and grads are only read.
+    hypers[b] as adam_update_batch_ takes them (lr and decoupled are ignored).
+    Every tensor starts 16-byte aligned."""
+    params, grads, hypers = list(params), list(grads), list(hypers)
+    ms, vs, us = list(exp_avgs), list(exp_avg_sqs), list(updates)
+    if not (len(params) == len(grads) == len(ms) == len(vs) == len(us) == len(hypers)):
+        raise ValueError("lamb_moments_batch_: one grad, exp_avg, exp_avg_sq, update and hyper "
+                         "per param segment")
+    if not params:
+        return us
+    _check_dev(params + grads + ms + vs + us)
+    for p, g, m, v, u in zip(params, grads, ms, vs, us):
+        if p.dtype != params[0].dtype or \
+                any(x.numel() != p.numel() or x.dtype != p.dtype for x in (g, m, v, u)):
+            raise ValueError("lamb_moments_batch_: shape/dtype mismatch")
+    cnt = (ctypes.c_size_t * len(params))(*[p.numel() for p in params])
+    rc = _lib.load().kf_lamb_moments_batch(
+        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (params, grads, ms, vs, us)],
+        cnt, len(params), int(kungfu_dtype(params[0])), int(np_),
+        _lib.adam_hyper_array(hypers), _stream(stream, params[0].device))
+    _lib.check(rc, "kf_lamb_moments_batch", source="")
+    return us
+
+
+def lamb_master_moments_batch_(grads16, masters, exp_avgs, exp_avg_sqs, updates, hypers, np_=0,
+                               stream=None):
+    """lamb_moments_batch_ for bf16 or f16 gradients with fp32 master weights
+    and state, one launch per 32 segments (kf_lamb_master_moments_batch): the
+    gradient is widened, the f32 arithmetic runs on (masters, g, exp_avgs,
+    exp_avg_sqs) and writes the fp32 updates. masters and grads16 are only
+    read; the 16-bit parameters are not touched (LambApplyPlan writes them)."""
+    grads, ws, hypers = list(grads16), list(masters), list(hypers)
+    ms, vs, us = list(exp_avgs), list(exp_avg_sqs), list(updates)
+    if not (len(grads) == len(ws) == len(ms) == len(vs) == len(us) == len(hypers)):
+        raise ValueError("lamb_master_moments_batch_: one master, exp_avg, exp_avg_sq, update and "
+                         "hyper per gradient segment")
+    if not grads:
+        return us
+    _check_dev(grads + ws + ms + vs + us)
+    if grads[0].dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("lamb_master_moments_batch_: bf16 or f16 gradients")
+    for g, w, m, v, u in zip(grads, ws, ms, vs, us):
+        if g.dtype != grads[0].dtype or \
+                any(x.numel() != g.numel() or x.dtype != torch.float32 for x in (w, m, v, u)):
+            raise ValueError("lamb_master_moments_batch_: shape/dtype mismatch")
+    cnt = (ctypes.c_size_t * len(grads))(*[g.numel() for g in grads])
+    rc = _lib.load().kf_lamb_master_moments_batch(
+        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (grads, ws, ms, vs, us)],
+        cnt, len(grads), int(kungfu_dtype(grads[0])), int(np_),
+        _lib.adam_hyper_array(hypers), _stream(stream, grads[0].device))
+    _lib.check(rc, "kf_lamb_master_moments_batch", source="")
+    return us
+
+
+def lamb_trust_update_(sq, world, group_of, groups, nlr, ratio, trust_clip=0.0, stream=None):
+    """The trust ratios of T = group_of.numel() tensors on the device
+    (kf_lamb_trust_update): sq is world * 2 * T float64 sums of squares,
+    sq[r * 2T + t] of rank r's piece of tensor t's parameters and
+    sq[r * 2T + T + t] of its update; group_of an int32 device tensor (tensor
+    -> group); groups[j] a dict with lr and adapt. Writes ratio[t] =
+    ||p|| / ||u|| (1 where adapt is off or a norm is not > 0), clipped from
+    above by trust_clip > 0, and nlr[t] = -(lr * ratio[t]). No host sync."""
+    groups = list(groups)
+    _check_dev([sq, group_of, nlr, ratio])
+    T = group_of.numel()
+    if group_of.dtype != torch.int32 or T < 1 or not groups:
+        raise ValueError("lamb_trust_update_: group_of is a non-empty int32 tensor, and at least "
+                         "one group")
+    if sq.dtype != torch.float64 or sq.numel() != int(world) * 2 * T or int(world) < 1:
+        raise ValueError("lamb_trust_update_: sq is world * 2 * T float64 values")
+    for t in (nlr, ratio):
+        if t.dtype != torch.float64 or t.numel() != T:
+            raise ValueError("lamb_trust_update_: nlr and ratio are T float64 values")
+    garr = (_lib.LambGroup * len(groups))()
+    for a, h in zip(garr, groups):
+        a.lr, a.adapt = float(h["lr"]), int(bool(h["adapt"]))
+    rc = _lib.load().kf_lamb_trust_update(
+        sq.data_ptr(), int(world), T, group_of.data_ptr(), garr, len(groups),
+        float(trust_clip or 0.0), nlr.data_ptr(), ratio.data_ptr(), _stream(stream, sq.device))
+    _lib.check(rc, "kf_lamb_trust_update", source="")
+    return nlr
+
+
+class LambApplyPlan:
+    """LAMB's apply pass over "tensor ∩ own shard" pieces (kf_lamb_apply_*):
+    built once over views that never move, run(nlr) is one launch whatever
+    the number of pieces:
+
+      params[i] += nlr[tensors[i]] * updates[i]       (in the pieces' f32 / f64)
+
+    With params16 (bf16 or f16 views of the same lengths) params are the fp32
+    master pieces and params16[i] = params[i] narrowed, round-to-nearest-even.
+    Pieces are aligned to the element only; a piece's tensors must share their
+    element offset from a 16-byte boundary. A piece may be empty. The plan
+    keeps the tensors alive. nlr: ntensor float64 values on the device."""
+
+    def __init__(self, params, updates, tensors, ntensor, params16=None):
+        ps, us, ts = list(params), list(updates), [int(t) for t in tensors]
+        p16 = None if params16 is None else list(params16)
+        if not (len(ps) == len(us) == len(ts)) or (p16 is not None and len(p16) != len(ps)):
+            raise ValueError("LambApplyPlan: one update and tensor index per piece")
+        _check_dev(ps + us + (p16 or []))
+        for i, (p, u) in enumerate(zip(ps, us)):
+            if p.dtype != ps[0].dtype or u.dtype != p.dtype or u.numel() != p.numel():
+                raise ValueError("LambApplyPlan: shape/dtype mismatch")
+            if p16 is not None and (p16[i].numel() != p.numel() or p16[i].dtype != p16[0].dtype):
+                raise ValueError("LambApplyPlan: shape/dtype mismatch")
+        if ps:
+            if p16 is not None:
+                if ps[0].dtype != torch.float32 or \
+                        p16[0].dtype not in (torch.bfloat16, torch.float16):
+                    raise ValueError("LambApplyPlan: fp32 masters and bf16 or f16 parameters")
+            elif ps[0].dtype not in (torch.float32, torch.float64):
+                raise ValueError("LambApplyPlan: f32 or f64 parameters (bf16 and f16 through "
+                                 "their masters)")
+        self._keep = (ps, us, p16)
+        self.npiece, self.ntensor = len(ps), int(ntensor)
+        self.device = ps[0].device if ps else None
+        self._plan = None
+        if not ps:
+            return
+        lib = _lib.load()
+        dt = int(kungfu_dtype(p16[0] if p16 is not None else ps[0]))
+        with torch.cuda.device(self.device):
+            self._plan = lib.kf_lamb_apply_create(
+                _lib.ptr_array([t.data_ptr() for t in ps]),
+                _lib.ptr_array([t.data_ptr() for t in us]),
+                None if p16 is None else _lib.ptr_array([t.data_ptr() for t in p16]),
+                (ctypes.c_size_t * len(ps))(*[t.numel() for t in ps]),
+                (ctypes.c_int * len(ps))(*ts), len(ps), self.ntensor, dt)
+        if not self._plan:
+            raise _lib.KungFuAMDError("kf_lamb_apply_create failed: %s"
+                                      % lib.kf_last_error().decode())
+
+    def run(self, nlr, stream=None):
+        if not self.npiece:
+            return
+        if self._plan is None:
+            raise ValueError("LambApplyPlan: closed")
+        _check_dev([nlr])
+        if nlr.dtype != torch.float64 or nlr.numel() != self.ntensor or nlr.device != self.device:
+            raise ValueError("LambApplyPlan.run: nlr must be %d float64 values on %s"
+                             % (self.ntensor, self.device))
+        rc = _lib.load().kf_lamb_apply_run(self._plan, nlr.data_ptr(),
+                                           _stream(stream, self.device))
+        _lib.check(rc, "kf_lamb_apply_run", source="")
+
+    def close(self):
+        if self._plan is not None:
+            _lib.load().kf_lamb_apply_destroy(self._plan)
+            self._plan = None
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 _NORM_DTYPES = (torch.float32, torch.float16, torch.bfloat16, torch.float64)
 
 

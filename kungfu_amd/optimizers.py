@@ -28,6 +28,8 @@ Operator surface kept from the reference:
   sharded over the ranks. The package's own (the reference has none).
 * ``ShardedAdamOptimizer(optimizer, named_parameters=None, ...)`` — the same
   for torch.optim.Adam / AdamW: exp_avg and exp_avg_sq sharded over the ranks.
+* ``ShardedLAMBOptimizer(optimizer, named_parameters=None, ...)`` — LAMB on
+  the same shards: per-tensor trust ratios from norms taken across the ranks.
 
 Buckets: parameters are grouped (in registration order, per dtype/device) into
 flat padded device buckets (``collective.GradBuckets``); ``p.grad`` (S-SGD) or
@@ -1104,6 +1106,147 @@ class _ShardedAdam(_Sharded):
         self._kf_gstates.copy_(torch.from_numpy(a.view(np.uint8).copy()))
 
 
+def lamb_pieces(gb, world, rank):
+    """The "tensor ∩ shard" pieces of one GradBuckets layout on `rank`:
+    [(tensor, bucket, offset, count)] with `offset` counted from the start of
+    the rank's shard of that bucket, one entry per tensor that has elements
+    there (a tensor is contiguous in one bucket, so it has at most one piece
+    per rank). Bucket padding lies in no piece; a tensor of zero elements has
+    none."""
+    out = []
+    for t, v in enumerate(gb.views):
+        n = v.numel()
+        if n == 0:
+            continue
+        for j, b in enumerate(gb.buckets):
+            lo = b.data_ptr()
+            if lo <= v.data_ptr() < lo + b.numel() * b.element_size():
+                break
+        else:
+            raise ValueError("lamb_pieces: a view outside every bucket")
+        s = (v.data_ptr() - lo) // b.element_size()
+        q = b.numel() // world
+        a, e = max(s, rank * q), min(s + n, (rank + 1) * q)
+        if a < e:
+            out.append((t, j, a - rank * q, e - a))
+    return out
+
+
+class _ShardedLAMB(_ShardedAdam):
+    """reduce-scatter(grads) -> moments on the own shard -> segmented norms of
+    the (parameter, update) pieces -> all-gather of the sums -> trust ratios
+    -> apply on the own pieces -> all-gather(params). The
+    state is _ShardedAdam's; "u", the update direction, is one scratch shard
+    per bucket in the compute type and is not checkpointed."""
+
+    _kf_name = "ShardedLAMBOptimizer"
+    _kf_dtypes = ("float32", "float64")
+    _kf_dtype_words = "f32 and f64 (bf16 and f16 with master_weights=True)"
+    _kf_trust_clip = 0.0
+    _kf_always_adapt = False
+    _kf_lamb = None  # the plans, one per (dtype, device)
+
+    def _kf_new_group(self):
+        return dict(super()._kf_new_group(), u=None)
+
+    def _kf_lamb_ops(self):
+        """Where the moments, the norms, the trust ratios and the apply pass
+        run: the exchange's epilogue (collective.Exchange; injectable for CPU
+        tests) or the HIP one."""
+        from .collective import HipEpilogue
+        ep = getattr(self._kf_ex, "epilogue", None)
+        return ep if hasattr(ep, "lamb_moments_") else HipEpilogue()
+
+    def _kf_build_sharded(self):
+        """Once, with the buckets: the state and update shards (fixed
+        addresses), the piece list of every bucket group, and per (dtype,
+        device) the norm plan over 2T segments, the tensor -> group table,
+        the ratios' buffers and the apply plan."""
+        import torch
+        super()._kf_build_sharded()
+        ex, ep = self._kf_ex, self._kf_lamb_ops()
+        by = {}
+        for j, G in enumerate(self._kf_groups):
+            self._kf_states(G)
+            G["u"] = self._kf_zero_shards(G, G["m"][0].dtype if G["m"] else None)
+            b = G["pb"].buckets[0]
+            by.setdefault((b.dtype, b.device), []).append(j)
+        self._kf_lamb = []
+        for (dtype, device), js in by.items():
+            pp, uu, p16, tensors, group_of, owners = [], [], [], [], [], []
+            for k, j in enumerate(js):
+                G = self._kf_groups[j]
+                pieces = {t: (b, off, n) for t, b, off, n in
+                          lamb_pieces(G["pb"], ex.world, ex.rank)}
+                for t, p in enumerate(G["ps"]):
+                    b, off, n = pieces.get(t, (0, 0, 0))
+                    bucket = G["pb"].buckets[b]
+                    q = bucket.numel() // ex.world
+                    mine = bucket[ex.rank * q:(ex.rank + 1) * q]
+                    pp.append((G["w"][b] if G["w"] is not None else mine)[off:off + n])
+                    uu.append(G["u"][b][off:off + n])
+                    if G["w"] is not None:
+                        p16.append(mine[off:off + n])
+                    tensors.append(len(owners))
+                    group_of.append(k)
+                    owners.append(p)
+            T = len(owners)
+            f64 = dict(dtype=torch.float64, device=device)
+            self._kf_lamb.append({
+                "js": js, "owners": owners, "T": T,
+                "norm": ep.sq_norm_plan(pp + uu),
+                "out": torch.zeros(2 * T + 1, **f64),
+                "sq": torch.zeros(2 * T * ex.world, **f64),
+                "group_of": torch.tensor(group_of, dtype=torch.int32, device=device),
+                "nlr": torch.zeros(T, **f64), "ratio": torch.ones(T, **f64),
+                "apply": ep.lamb_apply_plan(pp, uu, tensors, T, p16 if p16 else None)})
+
+    def step(self, closure=None):
+        loss = self._kf_closure(closure)
+        if self._kf_groups is None:
+            self._kf_build_sharded()
+        ex, ep, groups = self._kf_ex, self._kf_lamb_ops(), self._kf_groups
+        for G in groups:
+            _SyncSGD._kf_place(G["ps"], G["gb"])
+        for j, G in enumerate(groups):
+            G["np"] = ex.reduce_shards_(G["gb"].buckets, ("lamb", j))
+        for j, G in enumerate(groups):
+            pg = self.param_groups[G["gi"]]  # read at every step: schedulers change them
+            G["step"] += 1
+            wd = float(pg["weight_decay"])
+            G["h"] = {"lr": float(pg["lr"]), "betas": tuple(float(b) for b in pg["betas"]),
+                      "eps": float(pg["eps"]), "weight_decay": wd, "decoupled": False,
+                      "step": G["step"], "adapt": wd != 0 or self._kf_always_adapt}
+            shards = ex.grad_shards_(G["gb"].buckets, ("lamb", j))
+            hs = [G["h"]] * len(shards)
+            if G["w"] is not None:
+                ep.lamb_master_moments_(shards, G["w"], G["m"], G["v"], G["u"], hs, G["np"])
+            else:
+                q = [b.numel() // ex.world for b in G["pb"].buckets]
+                mine = [b[ex.rank * n:(ex.rank + 1) * n] for b, n in zip(G["pb"].buckets, q)]
+                ep.lamb_moments_(mine, shards, G["m"], G["v"], G["u"], hs, G["np"])
+        for L in self._kf_lamb:
+            L["norm"].run("sq", out=L["out"])
+            ex.gather_doubles_(L["out"][:2 * L["T"]], L["sq"])
+            ep.lamb_trust_update_(L["sq"], ex.world, L["group_of"],
+                                  [groups[j]["h"] for j in L["js"]], L["nlr"], L["ratio"],
+                                  self._kf_trust_clip)
+            L["apply"].run(L["nlr"])
+        for G in groups:
+            ex.gather_params_(G["pb"].buckets)
+        _finish(ex)
+        return loss
+
+    def last_trust_ratios(self):
+        """{parameter: the trust ratio its last step used} (1.0 before the
+        first step); synchronises with the device."""
+        out = {}
+        for L in self._kf_lamb or []:
+            for p, r in zip(L["owners"], L["ratio"].cpu().tolist()):
+                out[p] = float(r)
+        return out
+
+
 def ShardedSGDOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20):
     """Synchronous SGD with the optimizer update sharded over the ranks
     (sharded optimizer state): every step is
@@ -1323,3 +1466,85 @@ def _gate_rule(max_grad_norm, loss_scale):
         raise ValueError("ShardedAdamOptimizer: loss_scale must be None, a positive number, "
                          "'dynamic' or a dict, not %r" % (loss_scale,))
     return max_norm, dict(static, init_scale=float(loss_scale))
+
+
+def ShardedLAMBOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20,
+                         master_weights=False, trust_clip=None, always_adapt=False, **unsupported):
+    """LAMB (layer-wise adaptive moments for large batches) with the update
+    and its state sharded over the ranks as ShardedAdamOptimizer's are
+    (DESIGN.md §17). Every step is
+
+      reduce-scatter(grads) -> [own shard: g / np, exp_avg, exp_avg_sq,
+                                u = m^ / (sqrt(v^) + eps) + weight_decay * p]
+        -> norms of every tensor's piece of p and of u on this rank (one
+           ops.SegNorm pass, fp64) -> all-gather of 16 bytes per tensor and rank
+        -> trust ratio per tensor, ||p|| / ||u|| (ops.lamb_trust_update_)
+        -> [own pieces: p -= lr * ratio * u] -> all-gather(params)
+
+    all queued on the current stream: the host never waits for a norm. A
+    tensor's norms are taken over the whole tensor although its elements are
+    spread over the ranks' shards at element offsets; the sums are added in
+    rank order, so every rank computes the same ratios bit for bit. The
+    arithmetic is include/kungfu_amd.h's ("LAMB"): apex FusedLAMB's
+    formulation with bias correction, without its global gradient clipping.
+
+    `optimizer` must be a torch.optim.Adam or torch.optim.AdamW (TypeError
+    otherwise); it only lends its class and its param_groups (lr, betas, eps,
+    weight_decay, read at every step, so LR schedulers work). weight_decay is
+    LAMB's lambda for both classes: wd * p joins the update before the norm.
+    A parameter group adapts (uses the trust ratio) when its weight_decay != 0
+    or always_adapt=True, apex's rule; otherwise its ratio is 1. A tensor
+    whose parameter norm or update norm is not > 0 (a zero-element tensor
+    among them) has ratio 1.
+
+      * trust_clip: None, or a positive number the ratio is clipped to from
+        above (1.0 gives "LAMBC"-style clipping).
+      * master_weights=True: bf16 and f16 groups keep fp32 master weights
+        and fp32 state, as ShardedAdamOptimizer(master_weights=True) does;
+        both passes run in fp32 on the master and the 16-bit parameters are
+        the master narrowed. Without it bf16 and f16 parameters are refused
+        (TypeError on the first step): f32 and f64 only.
+      * Non-finite gradients are not skipped: they reach the parameters as
+        they do in torch.optim.Adam.
+      * A parameter without a gradient is updated as with a zero gradient,
+        and p.grad does not hold the averaged gradient after step().
+
+    state_buffers() / load_state_buffers() are ShardedAdamOptimizer's
+    checkpoint path (step, exp_avg, exp_avg_sq, master); the update direction
+    is scratch and is not part of it. last_trust_ratios() returns {parameter:
+    float} of the last step and synchronises.
+
+    Not offered: max_grad_norm / loss_scale gating, overlap=True, the
+    hierarchical (multi-host) path, amsgrad, maximize, capturable,
+    differentiable, and any optimizer other than Adam / AdamW."""
+    import math
+    import torch
+    for k in unsupported:
+        if k in ("max_grad_norm", "loss_scale"):
+            raise ValueError("ShardedLAMBOptimizer: %s (the gated step) is not offered" % k)
+        raise TypeError("ShardedLAMBOptimizer got an unexpected keyword argument %r" % k)
+    if not isinstance(optimizer, (torch.optim.Adam, torch.optim.AdamW)):
+        raise TypeError("ShardedLAMBOptimizer wraps a torch.optim.Adam or AdamW, not %s"
+                        % type(optimizer).__name__)
+    for g in optimizer.param_groups:
+        for option in ("amsgrad", "maximize", "capturable", "differentiable"):
+            if g.get(option, False):
+                raise ValueError("ShardedLAMBOptimizer: %s=True is not supported" % option)
+    if trust_clip is not None and (isinstance(trust_clip, bool) or
+                                   not isinstance(trust_clip, (int, float)) or
+                                   not (0 < trust_clip < math.inf)):
+        raise ValueError("ShardedLAMBOptimizer: trust_clip must be a positive finite number or "
+                         "None, not %r" % (trust_clip,))
+    opt = _wrap(optimizer, _ShardedLAMB)
+    opt._kf_setup(named_parameters, exchange, bucket_bytes)
+    for method in ("reduce_shards_", "grad_shards_", "gather_doubles_", "gather_params_"):
+        if not hasattr(opt._kf_ex, method):
+            raise ValueError("ShardedLAMBOptimizer needs an exchange with %s() "
+                             "(collective.Exchange or exchange.NativeExchange)" % method)
+    opt._kf_trust_clip = float(trust_clip) if trust_clip is not None else 0.0
+    opt._kf_always_adapt = bool(always_adapt)
+    if master_weights:
+        opt._kf_master = True
+        opt._kf_dtypes = ("float32", "float16", "bfloat16", "float64")
+        opt._kf_dtype_words = "f32, f16, bf16 and f64"
+    return opt

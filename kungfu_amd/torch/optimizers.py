@@ -24,14 +24,16 @@ takes ``named_parameters`` positionally.
 ``ShardedSGDOptimizer`` (the package's own: S-SGD with the SGD update and its
 momentum sharded over the ranks) likewise takes ``named_parameters``
 positionally, and so does ``ShardedAdamOptimizer`` (the same for
-torch.optim.Adam / AdamW and their two state tensors).
+torch.optim.Adam / AdamW and their two state tensors) and
+``ShardedLAMBOptimizer`` (LAMB's layer-wise trust ratios on the same shards).
 """
 from .. import optimizers as _opt
 from ..optimizers import SynchronousAveragingOptimizer
 
 __all__ = ["SynchronousSGDOptimizer", "SynchronousAveragingOptimizer",
            "MonitorGradientNoiseScaleOptimizer", "MonitorGradientVarianceOptimizer",
-           "PairAveragingOptimizer", "ShardedSGDOptimizer", "ShardedAdamOptimizer"]
+           "PairAveragingOptimizer", "ShardedSGDOptimizer", "ShardedAdamOptimizer",
+           "ShardedLAMBOptimizer"]
 
 
 def SynchronousSGDOptimizer(optimizer, named_parameters, op=None, **kwargs):
@@ -78,3 +80,10 @@ def ShardedAdamOptimizer(optimizer, named_parameters, **kwargs):
     of bf16 / f16 parameters, and `max_grad_norm` / `loss_scale` for the gated
     step (gradient-norm clipping, loss scaling, inf / NaN step skipping)."""
     return _opt.ShardedAdamOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
+
+
+def ShardedLAMBOptimizer(optimizer, named_parameters, **kwargs):
+    """kungfu_amd.optimizers.ShardedLAMBOptimizer with `named_parameters`
+    positional. Keywords pass through: `exchange`, `bucket_bytes`,
+    `master_weights`, `trust_clip` and `always_adapt`."""
+    return _opt.ShardedLAMBOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
