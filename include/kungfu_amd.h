@@ -334,6 +334,74 @@ int kf_adam_master_update_batch_gated(void *const *params16, const void *const *
                                       const kf_step_gate *gate, const kf_step_state *state,
                                       void *stream);
 
+/* ---- Adam, stochastic rounding: bf16 parameters and state, fp32 registers --
+ *
+ * The third choice for a bf16 model beside kf_adam_update_batch (bf16 state,
+ * every operation rounded to nearest even: an update below half an ulp of p is
+ * rounded away, and rnd(b2*v) == v for every normal v at beta2 = 0.999, so
+ * exp_avg_sq never decays) and kf_adam_master_update_batch (28 bytes per
+ * element, 12 bytes of state): kungfu_amd/csrc/kf_adam_sr.hip, DESIGN.md §18.
+ * 14 bytes per element and 4 bytes of state, as the first; both stalls go
+ * away in expectation.
+ *
+ * Arithmetic. kf_adam_update_batch's f32 arithmetic, operation for operation,
+ * on the widened bf16 p, g, m and v: exactly what kf_adam_master_update_batch
+ * runs on its master. The widening is exact, the /np is the fp32 one, and no
+ * intermediate value is rounded to 16 bits; p', m', v' are the f32 results.
+ *
+ * Stores.  p = sr(p', r_p);  m = f32_to_bf16(m') (round-to-nearest-even: m
+ * decays by 10 % a step and cannot stall);  v = sr(v', r_v).
+ *
+ * sr(x, r), for a finite x and 16 random bits r, is
+ *   (bits(x) + r) >> 16                  as unsigned 32-bit arithmetic,
+ * that is, x goes to the next bf16 away from zero with probability
+ * low16(bits(x)) / 2^16 and is truncated otherwise: E[sr(x)] = x. A carry into
+ * the exponent is kept, so a finite f32 above bf16's largest finite value may
+ * become inf. A value that is exactly a bf16 is returned unchanged for every
+ * r. inf and NaN narrow as the round-to-nearest-even narrowing does (inf
+ * stays; a NaN keeps its sign and upper payload and is made quiet).
+ *
+ * Random bits: a pure function of (key, stream word, element index). They do
+ * not depend on the launch geometry, on how the elements are split into
+ * segments, on the rank or on the world. For element i of segment b, with
+ * e = bases[b] + i:
+ *   (a, b) = philox2x32_10(c0 = (uint32_t)(e >> 1), c1 = streams[b], key)
+ *   w = (e & 1) ? b : a;   r_p = w >> 16;   r_v = w & 0xffff
+ * Philox2x32-10 (Salmon, Moraes, Dror, Shaw 2011): ten rounds of
+ *   (hi, lo) = 0xD256D193 * c0 (64-bit product);  c0 = hi ^ key ^ c1;  c1 = lo
+ * with key = key + 0x9E3779B9 between rounds. Known answers (c0, c1, key ->
+ * a, b): (0, 0, 0 -> ff1dae59, 6cd10df2), (ffffffff, ffffffff, ffffffff ->
+ * 2c3f628b, ab4fd7ad), (243f6a88, 85a308d3, 13198a2e -> dd7ce038, f62a4c12).
+ * One evaluation serves an element pair.
+ *
+ * kf_adam_sr_update_batch takes what kf_adam_update_batch takes, plus per
+ * segment bases[b] (the element index of its first element) and streams[b],
+ * and one key for the call. kf_adam_sr_update_batch_gated follows
+ * kf_adam_update_batch_gated's rules: one hyper, a skipped step returns before
+ * any load and leaves every byte as it was, grad_mul, s2 and nss come from the
+ * device. Checks, all before any HIP call: everything kf_adam_update_batch
+ * checks (bases and streams are tables like the others); dt must be
+ * KungFu_BFLOAT16 (KF_ERR_DTYPE otherwise); in a non-empty segment bases[b]
+ * must be a multiple of 8 and bases[b] + counts[b] at most 2^33 (KF_ERR_ARG).
+ * One launch per 32 segments.
+ *
+ * kf_adam_sr_narrow is sr() alone: out[i] = sr(x[i], r[i]) for n fp32 bit
+ * patterns x, n 16-bit words r and n bf16 results, all on the device. It runs
+ * the update kernels' own narrowing and exists so that the narrowing can be
+ * swept over its whole domain. */
+int kf_adam_sr_update_batch(void *const *params, const void *const *grads, void *const *exp_avgs,
+                            void *const *exp_avg_sqs, const size_t *counts, const uint64_t *bases,
+                            const uint32_t *streams, int nb, KungFu_Datatype dt, int np,
+                            const kf_adam_hyper *hyper, uint32_t key, void *stream);
+int kf_adam_sr_update_batch_gated(void *const *params, const void *const *grads,
+                                  void *const *exp_avgs, void *const *exp_avg_sqs,
+                                  const size_t *counts, const uint64_t *bases,
+                                  const uint32_t *streams, int nb, KungFu_Datatype dt, int np,
+                                  const kf_adam_hyper *hyper, uint32_t key,
+                                  const kf_step_gate *gate, const kf_step_state *state,
+                                  void *stream);
+int kf_adam_sr_narrow(const void *x, const void *r, void *out, size_t n, void *stream);
+
 /* ---- LAMB: layer-wise trust ratios on the sharded step --------------------
  *
  * LAMB (kungfu_amd/csrc/kf_lamb.hip) where the averaged

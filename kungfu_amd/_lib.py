@@ -136,6 +136,9 @@ EXPORTED = (
     "kf_lamb_apply_run",
     "kf_lamb_apply_destroy",
     "kf_exchange_gather_params_batch",
+    "kf_adam_sr_update_batch",
+    "kf_adam_sr_update_batch_gated",
+    "kf_adam_sr_narrow",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -574,6 +577,17 @@ def load():
     lib.kf_exchange_gather_params_batch.argtypes = [c_void_p, P(c_void_p), P(c_size_t), c_int,
                                                     c_int, c_void_p]
     lib.kf_exchange_gather_params_batch.restype = c_int
+    lib.kf_adam_sr_update_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_void_p),
+                                            P(c_size_t), P(ctypes.c_uint64), P(u32), c_int, c_int,
+                                            c_int, P(AdamHyper), u32, c_void_p]
+    lib.kf_adam_sr_update_batch.restype = c_int
+    lib.kf_adam_sr_update_batch_gated.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p),
+                                                  P(c_void_p), P(c_size_t), P(ctypes.c_uint64),
+                                                  P(u32), c_int, c_int, c_int, P(AdamHyper), u32,
+                                                  c_void_p, c_void_p, c_void_p]
+    lib.kf_adam_sr_update_batch_gated.restype = c_int
+    lib.kf_adam_sr_narrow.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.kf_adam_sr_narrow.restype = c_int
     _lib = lib
     # HIP resources go back while the runtime is alive, before the C exit
     # handlers run (include/kungfu_amd.h kf_shutdown)

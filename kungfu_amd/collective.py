@@ -95,6 +95,19 @@ class HipEpilogue:
         return ops.adam_master_update_batch_gated_(params16, grads16, masters, exp_avgs,
                                                    exp_avg_sqs, hyper, gate, states, group, np_)
 
+    # -- Adam with stochastic rounding --
+    def adam_sr_update_(self, params, grads, exp_avgs, exp_avg_sqs, hypers, np_, bases, streams,
+                        key):
+        """The stochastic-rounding Adam / AdamW update of bf16 shards
+        (ops.adam_sr_update_batch_), one launch."""
+        return ops.adam_sr_update_batch_(params, grads, exp_avgs, exp_avg_sqs, hypers, bases,
+                                         streams, key, np_)
+
+    def adam_sr_update_gated_(self, params, grads, exp_avgs, exp_avg_sqs, hyper, gate, states,
+                              group, np_, bases, streams, key):
+        return ops.adam_sr_update_batch_gated_(params, grads, exp_avgs, exp_avg_sqs, hyper, gate,
+                                               states, bases, streams, key, group, np_)
+
     # -- LAMB (DESIGN.md §17) --
     def lamb_moments_(self, params, grads, exp_avgs, exp_avg_sqs, updates, hypers, np_):
         """LAMB's moments pass over the shards (ops.lamb_moments_batch_)."""

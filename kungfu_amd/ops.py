@@ -419,6 +419,90 @@ def adam_master_update_batch_gated_(params16, grads16, masters, exp_avgs, exp_av
     return params
 
 
+# -- Adam, stochastic rounding (include/kungfu_amd.h) -----------
+
+def _sr_tables(name, params, grads, ms, vs, bases, streams, key):
+    """The checked segment tables of the two stochastic-rounding entries."""
+    bases, streams = [int(b) for b in bases], [int(s) for s in streams]
+    if not (len(params) == len(grads) == len(ms) == len(vs) == len(bases) == len(streams)):
+        raise ValueError("%s: one grad, exp_avg, exp_avg_sq, base and stream word per param "
+                         "segment" % name)
+    if not 0 <= int(key) < 1 << 32 or any(not 0 <= s < 1 << 32 for s in streams) or \
+            any(not 0 <= b < 1 << 64 for b in bases):
+        raise ValueError("%s: key and stream words are 32-bit, bases 64-bit unsigned" % name)
+    if not params:
+        return None
+    _check_dev(params + grads + ms + vs)
+    for p, g, m, v in zip(params, grads, ms, vs):
+        if p.dtype != torch.bfloat16 or \
+                any(x.numel() != p.numel() or x.dtype != p.dtype for x in (g, m, v)):
+            raise ValueError("%s: bf16 tensors of one shape per segment" % name)
+    nb = len(params)
+    return [_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (params, grads, ms, vs)] + \
+        [(ctypes.c_size_t * nb)(*[p.numel() for p in params]), (ctypes.c_uint64 * nb)(*bases),
+         (ctypes.c_uint32 * nb)(*streams)]
+
+
+def adam_sr_update_batch_(params, grads, exp_avgs, exp_avg_sqs, hypers, bases, streams, key,
+                          np_=0, stream=None):
+    """The Adam / AdamW update of many flat bf16 segments with bf16 state,
+    fp32 arithmetic in registers and stochastic rounding of p and exp_avg_sq,
+    one launch per 32 segments (kf_adam_sr_update_batch,
+    kungfu_amd/csrc/kf_adam_sr.hip), in place on params and both states. The
+    arithmetic is adam_master_update_batch_'s on the widened values; exp_avg is
+    narrowed round-to-nearest-even. bases[b] is the element index of segment
+    b's first element (a multiple of 8), streams[b] its 32-bit stream word and
+    `key` the call's 32-bit key: the random bits are Philox2x32-10 of (key,
+    stream word, element index) and of nothing else. hypers[b] as
+    adam_update_batch_ takes them. grads are only read."""
+    params, grads, hypers = list(params), list(grads), list(hypers)
+    ms, vs = list(exp_avgs), list(exp_avg_sqs)
+    if len(hypers) != len(params):
+        raise ValueError("adam_sr_update_batch_: one hyper per param segment")
+    t = _sr_tables("adam_sr_update_batch_", params, grads, ms, vs, bases, streams, key)
+    if t is None:
+        return params
+    rc = _lib.load().kf_adam_sr_update_batch(
+        *t, len(params), int(kungfu_dtype(params[0])), int(np_), _lib.adam_hyper_array(hypers),
+        int(key), _stream(stream, params[0].device))
+    _lib.check(rc, "kf_adam_sr_update_batch", source="")
+    return params
+
+
+def adam_sr_update_batch_gated_(params, grads, exp_avgs, exp_avg_sqs, hyper, gate, states, bases,
+                                streams, key, group=0, np_=0, stream=None):
+    """adam_sr_update_batch_ under a step gate (kf_adam_sr_update_batch_gated);
+    hyper, gate, states and group as adam_update_batch_gated_ takes them. A
+    skipped step leaves params and both states untouched."""
+    params, grads = list(params), list(grads)
+    ms, vs = list(exp_avgs), list(exp_avg_sqs)
+    t = _sr_tables("adam_sr_update_batch_gated_", params, grads, ms, vs, bases, streams, key)
+    if t is None:
+        return params
+    _check_gate(gate, states, int(group) + 1)
+    rc = _lib.load().kf_adam_sr_update_batch_gated(
+        *t, len(params), int(kungfu_dtype(params[0])), int(np_),
+        _lib.adam_hyper_array([dict(hyper, step=1)]), int(key), gate.data_ptr(),
+        _state_ptr(states, group), _stream(stream, params[0].device))
+    _lib.check(rc, "kf_adam_sr_update_batch_gated", source="")
+    return params
+
+
+def adam_sr_narrow(x, r):
+    """sr(x, r) element-wise on the device (kf_adam_sr_narrow): x holds fp32
+    bit patterns as int32, r 16-bit random words as int16; returns the bf16
+    results as an int16 tensor. The update kernels' own narrowing, for sweeps."""
+    _check_dev([x, r])
+    if x.dtype != torch.int32 or r.dtype != torch.int16 or x.numel() != r.numel() or \
+            not (x.is_contiguous() and r.is_contiguous()):
+        raise ValueError("adam_sr_narrow: int32 bit patterns and as many int16 random words")
+    out = torch.empty_like(r)
+    rc = _lib.load().kf_adam_sr_narrow(x.data_ptr(), r.data_ptr(), out.data_ptr(), x.numel(),
+                                       _stream(None, x.device))
+    _lib.check(rc, "kf_adam_sr_narrow", source="")
+    return out
+
+
 # -- LAMB (include/kungfu_amd.h "LAMB", DESIGN.md §17) -------------------------
 
 def lamb_moments_batch_(params, grads, exp_avgs, exp_avg_sqs, updates, hypers, np_=0, stream=None):

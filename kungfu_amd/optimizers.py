@@ -848,9 +848,11 @@ class _ShardedAdam(_Sharded):
     _kf_dtype_words = "f32, bf16 and f64"
     _kf_decoupled = False
     _kf_master = False
+    _kf_sr = False      # stochastic rounding of the bf16 groups
+    _kf_sr_seed = 0
 
     def _kf_new_group(self):
-        return {"m": None, "v": None, "w": None, "step": 0}
+        return {"m": None, "v": None, "w": None, "step": 0, "sr": False, "draw": 0}
 
     def _kf_build_sharded(self):
         import torch
@@ -862,8 +864,29 @@ class _ShardedAdam(_Sharded):
                 for b, w in zip(G["pb"].buckets, G["w"]):  # the widening is exact
                     q = w.numel()
                     w.copy_(b[ex.rank * q:(ex.rank + 1) * q])
+        for j, G in enumerate(self._kf_groups if self._kf_sr else []):
+            if G["pb"].buckets and G["pb"].buckets[0].dtype == torch.bfloat16:
+                G["sr"] = True
+                G["streams"] = [sr_stream_word(self._kf_sr_seed, j, i)
+                                for i in range(len(G["pb"].buckets))]
         if self._kf_gated:
             self._kf_build_gated()
+
+    # -- stochastic rounding -----------------------------------
+    def _kf_sr_ops(self):
+        """Where the stochastic-rounding updates run: the exchange's epilogue
+        (collective.Exchange; injectable for CPU tests) or the HIP one."""
+        from .collective import HipEpilogue
+        ep = getattr(self._kf_ex, "epilogue", None)
+        return ep if hasattr(ep, "adam_sr_update_") else HipEpilogue()
+
+    def _kf_sr_tables(self, G):
+        """(this rank's slices of the group's parameter buckets, their element
+        offsets in the buckets, the call's key) of a stochastic-rounding group."""
+        ex = self._kf_ex
+        q = [b.numel() // ex.world for b in G["pb"].buckets]
+        mine = [b[ex.rank * n:(ex.rank + 1) * n] for b, n in zip(G["pb"].buckets, q)]
+        return mine, [ex.rank * n for n in q], G["draw"] & 0xffffffff
 
     def _kf_states(self, G):
         """The group's zeroed exp_avg / exp_avg_sq shards, allocated on the
@@ -952,6 +975,14 @@ class _ShardedAdam(_Sharded):
                              backoff_factor=r["backoff_factor"],
                              growth_interval=r["growth_interval"])
         for j, (G, h) in enumerate(zip(groups, hs)):
+            if G["sr"]:
+                G["draw"] += 1  # the host's count: a step the device skips draws too
+                mine, bases, key = self._kf_sr_tables(G)
+                self._kf_sr_ops().adam_sr_update_gated_(
+                    mine, ex.grad_shards_(G["gb"].buckets, ("gated", j)), G["m"], G["v"], h,
+                    self._kf_gate, self._kf_gstates, j, G["np"], bases, G["streams"], key)
+                ex.gather_params_(G["pb"].buckets)
+                continue
             ex.adam_gated_step_(G["pb"].buckets, G["gb"].buckets, G["w"], G["m"], G["v"], h,
                                 G["np"], self._kf_gate, self._kf_gstates, j, ("gated", j))
 
@@ -1024,7 +1055,7 @@ class _ShardedAdam(_Sharded):
             self._kf_step_gated()
             _finish(self._kf_ex)
             return loss
-        for G in self._kf_groups:
+        for j, G in enumerate(self._kf_groups):
             pg = self.param_groups[G["gi"]]  # read at every step: schedulers change them
             ms, vs = self._kf_states(G)
             G["step"] += 1
@@ -1032,7 +1063,16 @@ class _ShardedAdam(_Sharded):
                  "eps": float(pg["eps"]), "weight_decay": float(pg["weight_decay"]),
                  "decoupled": self._kf_decoupled, "step": G["step"]}
             nb = len(G["pb"].buckets)
-            if G["w"] is not None:
+            if G["sr"]:
+                ex = self._kf_ex
+                G["draw"] += 1
+                np_ = ex.reduce_shards_(G["gb"].buckets, ("sr", j))
+                mine, bases, key = self._kf_sr_tables(G)
+                self._kf_sr_ops().adam_sr_update_(
+                    mine, ex.grad_shards_(G["gb"].buckets, ("sr", j)), ms, vs, [h] * nb, np_,
+                    bases, G["streams"], key)
+                ex.gather_params_(G["pb"].buckets)
+            elif G["w"] is not None:
                 self._kf_ex.adam_master_step_(G["pb"].buckets, G["gb"].buckets, G["w"], ms, vs,
                                               [h] * nb)
             else:
@@ -1059,6 +1099,9 @@ class _ShardedAdam(_Sharded):
             if G["w"] is not None:
                 for p, w in self._kf_unshard(G, G["w"]).items():
                     out[p]["master"] = w
+            if G["sr"]:
+                for p in m:
+                    out[p]["sr_draw"] = G["draw"]
         _finish(self._kf_ex)
         return out
 
@@ -1090,6 +1133,13 @@ class _ShardedAdam(_Sharded):
             if G["w"] is not None:
                 self._kf_reshard(G, G["w"], lambda p: mapping.get(p, {}).get("master", p.data))
             G["step"] = steps.pop()
+            if G["sr"]:
+                draws = {int(mapping[p]["sr_draw"]) for p in G["ps"]
+                         if p in mapping and "sr_draw" in mapping[p]}
+                if len(draws) > 1:
+                    raise ValueError("load_state_buffers: the parameters of one group differ in "
+                                     "sr_draw: %s" % sorted(draws))
+                G["draw"] = draws.pop() if draws else G["step"]
             if self._kf_gated:
                 self._kf_seed_state(j, G["step"], self.param_groups[G["gi"]]["betas"])
 
@@ -1104,6 +1154,23 @@ class _ShardedAdam(_Sharded):
         a["step"][j] = step
         a["beta1_pow"][j], a["beta2_pow"][j] = float(betas[0]) ** step, float(betas[1]) ** step
         self._kf_gstates.copy_(torch.from_numpy(a.view(np.uint8).copy()))
+
+
+def splitmix64(x):
+    """One step of SplitMix64 (Steele, Lea, Flood 2014) on a 64-bit word:
+    z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+    z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31, all modulo 2^64."""
+    mask = (1 << 64) - 1
+    z = (x + 0x9E3779B97F4A7C15) & mask
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
+    return z ^ (z >> 31)
+
+
+def sr_stream_word(sr_seed, group_index, bucket_index):
+    """The Philox stream word of one bucket of a stochastic-rounding group:
+    low32(splitmix64(splitmix64(sr_seed) ^ (group_index << 32 | bucket_index)))."""
+    return splitmix64(splitmix64(sr_seed) ^ (group_index << 32 | bucket_index)) & 0xffffffff
 
 
 def lamb_pieces(gb, world, rank):
@@ -1295,7 +1362,8 @@ def ShardedSGDOptimizer(optimizer, named_parameters=None, exchange=None, bucket_
 
 
 def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20,
-                         master_weights=False, max_grad_norm=None, loss_scale=None):
+                         master_weights=False, max_grad_norm=None, loss_scale=None,
+                         stochastic_rounding=False, sr_seed=0):
     """Synchronous Adam / AdamW with the optimizer update and its state
     sharded over the ranks, as ShardedSGDOptimizer does for SGD: every step is
 
@@ -1379,6 +1447,49 @@ def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket
     Gating takes every dtype the optimizer takes; f16 still needs
     master_weights=True (TypeError on the first step otherwise).
 
+    stochastic_rounding=True, the alternative to
+    master_weights for a bf16 model (both together: ValueError): every bf16
+    bucket group keeps bf16 parameters and bf16 exp_avg / exp_avg_sq, 4 / world
+    bytes of state per element and rank and 14 bytes of kernel traffic per
+    element, as without the flag, but the update (ops.adam_sr_update_batch_)
+    runs master_weights' f32 arithmetic in registers on the widened values and
+    narrows the results itself. Round-to-nearest-even loses every update below
+    half a bf16 ulp of the parameter, and at beta2 = 0.999 it leaves every
+    normal exp_avg_sq where it is (b2 * v rounds back to v), so the second
+    moment never decays; stochastic rounding removes both stalls in
+    expectation.
+      * What is stochastic: the narrowing of the new parameter and of the new
+        exp_avg_sq, sr(x, r) = (bits(x) + r) >> 16 with 16 random bits each:
+        up (away from zero) with probability low16(x) / 2^16, truncated
+        otherwise, so the expectation is x; a value that is a bf16 already is
+        kept for every r. What is not: the f32 arithmetic, exp_avg (narrowed
+        round-to-nearest-even; it decays by 10 % a step and cannot stall), the
+        gradient's reduce, and every f32 / f64 group, which takes the path
+        above with the same bits as without the flag. f16 parameters remain a
+        TypeError on the first step.
+      * A finite value in bf16's top binade may round up to inf.
+      * The random bits are Philox2x32-10 of (key, stream word, element
+        index) and of nothing else: key = draw mod 2^32, where draw is the
+        group's host-side count of step() calls from 1 (equal to `step`
+        without a gate; under max_grad_norm / loss_scale it also advances on
+        a step the device skips); the element index is the element's offset
+        in its bucket; stream word = low32(splitmix64(splitmix64(sr_seed) ^
+        (group_index << 32 | bucket_index))), group_index counting the
+        (param group, dtype) bucket groups and bucket_index the group's
+        buckets, splitmix64(x) being z = x + 0x9E3779B97F4A7C15; z = (z ^
+        z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) *
+        0x94D049BB133111EB; z ^ z >> 31 modulo 2^64. sr_seed is an int in
+        [0, 2^64) (ValueError otherwise). Rank, world, shard boundaries and
+        launch geometry play no part: given identical averaged gradients and
+        the same sr_seed, the results are identical bit for bit for any world.
+      * The step follows ShardedLAMBOptimizer's pattern: reduce_shards_,
+        grad_shards_, the update on this rank's slice of the parameter
+        buckets, gather_params_. Under a gate the group's last phase is
+        ops.adam_sr_update_batch_gated_ and gather_params_.
+      * state_buffers() adds "sr_draw" to every parameter's entry of such a
+        group and load_state_buffers() restores it (absent: draw = step), so
+        a resumed run draws the bits the uninterrupted run would have drawn.
+
     state_buffers() (collective) and load_state_buffers(mapping) are the
     checkpoint path for the sharded state.
 
@@ -1417,6 +1528,19 @@ def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket
                                  "exchange with %s() (collective.Exchange or "
                                  "exchange.NativeExchange)" % method)
         opt._kf_gated = True
+    if isinstance(sr_seed, bool) or not isinstance(sr_seed, int) or not 0 <= sr_seed < 1 << 64:
+        raise ValueError("ShardedAdamOptimizer: sr_seed must be an int in [0, 2**64), not %r"
+                         % (sr_seed,))
+    if stochastic_rounding:
+        if master_weights:
+            raise ValueError("ShardedAdamOptimizer: stochastic_rounding and master_weights are "
+                             "alternatives, not both")
+        for method in ("reduce_shards_", "grad_shards_", "gather_params_"):
+            if not hasattr(opt._kf_ex, method):
+                raise ValueError("ShardedAdamOptimizer(stochastic_rounding=True) needs an "
+                                 "exchange with %s() (collective.Exchange or "
+                                 "exchange.NativeExchange)" % method)
+        opt._kf_sr, opt._kf_sr_seed = True, sr_seed
     return opt
 
 
