@@ -12,6 +12,11 @@ below. They restate the host code's launch arithmetic (kf_capi.hip grid_for /
 make_plan / launch_batch_kc, kf_segnorm.hip kf_segnorm_create, kf_sgd.hip
 launch_sgd); tests/test_large_launch.py reads the same constants out of the
 sources, so a retune fails there and does not silently empty the GPU tests.
+
+The Adam, master-weight, gated, stochastic-rounding and LAMB moments kernels
+share the SGD update's planner (kf_update_batch.hpp plan_update_batch), which
+update_plan restates for one table; their rows shapes are ROWS_TILES and
+ROWS_WITH_TAIL_ONLY (update_shape).
 """
 import numpy as np
 
@@ -344,3 +349,75 @@ def sgd_grid(counts, dt):
     widest, total = max(blocks), sum(blocks)
     rows = len(blocks) > 1 and widest * len(blocks) <= 2 * total
     return rows, widest, blocks
+
+
+# ---- the Adam-family updates: kf_update_batch.hpp plan_update_batch ----------------------
+
+PLAN_BLOCK_CAP = 0x400000    # blocks of one segment; beyond, they stride over the tiles
+PLAN_GRID_CAP = 0x7FFFFF     # blocks of one launch
+
+ROWS_TILES = SGD_ROWS_TILES
+
+
+def update_plan(counts, unit, tile_units, nseg):
+    """The launches plan_update_batch makes of one table of `counts`:
+    [(rows, widest, [blocks per segment])]. A unit is `unit` elements, a tile
+    `tile_units` units; one block per tile, at least one (a tail alone), at
+    most PLAN_BLOCK_CAP; rows when nseg > 1 and widest * nseg <= 2 * blocks; a
+    launch is flushed at `nseg` segments and before PLAN_GRID_CAP blocks.
+    Empty segments take no entry."""
+    out, cur = [], []
+
+    def flush():
+        if cur:
+            widest, total = max(cur), sum(cur)
+            out.append((len(cur) > 1 and widest * len(cur) <= 2 * total, widest, list(cur)))
+            del cur[:]
+    for n in counts:
+        if n == 0:
+            continue
+        nblk = min(max(ceil_div(n // unit, tile_units), 1), PLAN_BLOCK_CAP)
+        if sum(cur) + nblk > PLAN_GRID_CAP:
+            flush()
+        cur.append(nblk)
+        if len(cur) == nseg:
+            flush()
+    flush()
+    return out
+
+
+def multi_tile_rows(counts, unit, tile_units, nseg):
+    """Does a launch of these counts run a rows grid with a segment of more
+    than one tile? (and, if so, does a row have blocks past its last tile)"""
+    hit = [p for p in update_plan(counts, unit, tile_units, nseg) if p[0] and p[1] > 1]
+    return bool(hit), any(min(p[2]) < p[1] for p in hit)
+
+
+def update_counts(unit, tile_units, tiles):
+    """Segments of `tiles` tiles, each short by 100 units, with a scalar tail
+    of 3 elements (unit - 1 where a unit holds fewer)."""
+    return [(t * tile_units - 100) * unit + min(3, unit - 1) for t in tiles]
+
+
+def tail_only_counts(unit, tile_units):
+    """ROWS_WITH_TAIL_ONLY: three segments of 2 tiles and one of unit - 1
+    elements, a row whose only work is block 0's scalar tail."""
+    return update_counts(unit, tile_units, (2, 2, 2)) + [unit - 1]
+
+
+# kernel -> (source file, elements per unit, units per tile, segments per
+# launch); the numbers are pinned to the sources by tests/test_large_launch.py
+UPDATE_KERNELS = {
+    "adam-f32": ("kf_adam.hip", 4, 1024, 24), "adam-bf16": ("kf_adam.hip", 8, 1024, 24),
+    "adam-f64": ("kf_adam.hip", 2, 1024, 24),
+    "master-bf16": ("kf_adam_master.hip", 4, 1024, 32), "master-f16": ("kf_adam_master.hip", 4, 1024, 32),
+    "sr-bf16": ("kf_adam_sr.hip", 8, 1024, 32),
+    "lamb-f32": ("kf_lamb.hip", 4, 1024, 24), "lamb-f64": ("kf_lamb.hip", 2, 1024, 24),
+    "lamb_master-bf16": ("kf_lamb.hip", 4, 1024, 32), "lamb_master-f16": ("kf_lamb.hip", 4, 1024, 32),
+}
+UPDATE_SHAPES = ("rows", "tail_only")
+
+
+def update_shape(kernel, shape):
+    _, unit, tile, _ = UPDATE_KERNELS[kernel]
+    return update_counts(unit, tile, ROWS_TILES) if shape == "rows" else tail_only_counts(unit, tile)

@@ -13,6 +13,13 @@ tail; its tile constants are read out of the kernel sources.
 Everything here travels as uint16 bit patterns; store() gives the numpy form
 the references take (float16 for f16, the bits themselves for bf16). No torch
 and no GPU is needed to import this module.
+
+The update kernels: SGD, Adam (bf16) and master-weight Adam; their gated
+twins at an unscale of 2^-16 and a clip of 0.37, one call per decay mode (the
+gated entries take one hyper); the stochastic-rounding update and its gated
+twin, every segment with an element base and a stream word of its own; LAMB's
+master moments pass; and the narrowing of LAMB's master apply pass on the
+grid of fp32 values around every 16-bit rounding boundary.
 """
 import functools
 import os
@@ -185,7 +192,36 @@ def kernels():
     nblock = _int(seg, r"constexpr int kNormBlock\s*=\s*(\d+);")
     elts = _int(master, r"#define KF_ADAM_MASTER_ELTS (\d+)")
     assert "#define KF_ADAM_MASTER_UNROLL (16 / KF_ADAM_MASTER_ELTS)" in master
+    sr, lamb = _src("kf_adam_sr.hip"), _src("kf_lamb.hip")
+    # the gated kernels are launched by their parents' planner call, on its
+    # grid and with its block: the "adam" and "master" geometry is theirs
+    assert adam.count("plan_update_batch<") == 1 and master.count("plan_update_batch<") == 1
+    assert "adam_update_gated_kernel<T><<<dim3(gx, gy), kAdamBlock, 0, s>>>" in adam
+    assert "adam_update_kernel<T><<<dim3(gx, gy), kAdamBlock, 0, s>>>" in adam
+    assert re.search(r"adam_master_gated_kernel<T>\s*<<<dim3\(gx, gy\), kAdamMasterBlock, 0, s>>>",
+                     master)
+    assert "adam_master_kernel<T><<<dim3(gx, gy), kAdamMasterBlock, 0, s>>>" in master
+    assert adam.count("adam_body<T, decltype(DIV)::value, decltype(DECAY)::value>") == 2
+    assert "plan_update_batch<" not in _src("kf_step_gate.hip")
+    # so is the stochastic-rounding kernel's gated twin
+    assert sr.count("plan_update_batch<") == 1 and \
+        sr.count("<<<dim3(gx, gy), kAdamSrBlock, 0, s>>>") == 2
+    assert "constexpr int kAdamSrUnroll = KF_ADAM_SR_UNROLL;" in sr
+    # the LAMB master moments pass: 16-byte units of the fp32 compute type
+    assert "counts, nb, SgdVec<C>::N, static_cast<size_t>(kLambBlock) * kLambUnroll," in lamb
+    assert "return launch_moments<float, kLambMasterSeg>(masters, grads16," in lamb
     return {
+        "adam_sr": (_int(sr, r"constexpr int kAdamSrElts\s*=\s*(\d+);"),
+                    _int(sr, r"constexpr int kAdamSrBlock\s*=\s*(\d+);")
+                    * _int(sr, r"#define KF_ADAM_SR_UNROLL (\d+)"),
+                    _int(sr, r"constexpr int kAdamSrSeg\s*=\s*(\d+);")),
+        "lamb_master": (16 // 4, _int(lamb, r"constexpr int kLambBlock\s*=\s*(\d+);")
+                        * _int(lamb, r"constexpr int kLambUnroll\s*=\s*(\d+);"),
+                        _int(lamb, r"constexpr int kLambMasterSeg\s*=\s*(\d+);")),
+        # the apply pass's pieces: 16-byte units of fp32, one piece per table row
+        "lamb_apply": (16 // 4, _int(lamb, r"constexpr int kLambBlock\s*=\s*(\d+);")
+                       * _int(lamb, r"#define KF_LAMB_APPLY_UNROLL (\d+)")
+                       * _int(lamb, r"#define KF_LAMB_APPLY_TILES (\d+)"), None),
         "reduce": (EPV, block * _int(capi, r"int unroll\s*=\s*(\d+);"), None),
         "batch_k1": (EPV, bblock * _int(capi, r"#define KF_BATCH_UNROLL_K1 (\d+)"),
                      _int(hpp, r"constexpr int kBatchSeg1\s*=\s*(\d+);")),
@@ -639,14 +675,14 @@ def adam_sweep(np_, step):
 MASTER_TRIPLES = ((1.0, 0.0, 0.0), (1.0 / 3.0, -1.0, 1.0 + 2.0 ** -23), (-30000.25, 1e-8, 1e30))
 
 
-@functools.lru_cache(maxsize=2)
-def master_sweep(dt, np_, step):
-    """g swept against three fp32 (master, m, v) triples. The long segments
-    are one per triple; tail segment j has triple j % 3."""
-    import adam_master_ref
-    hypers = adam_hypers(step)
-    block_segs, nedge = _update_layout("master", 3, 1)
-    block = Layout("master", block_segs)
+
+
+def _master_block(kernel):
+    """One hyper row's block of a gradient sweep against the fp32 triples:
+    (segments, their Layout, g, (w, m, v)). The long segments are one per
+    triple; tail segment j has triple j % 3."""
+    block_segs, nedge = _update_layout(kernel, 3, 1)
+    block = Layout(kernel, block_segs)
     g = np.empty(block.total, np.uint16)
     trip = np.empty(block.total, np.int64)
     for c in range(3):
@@ -657,19 +693,301 @@ def master_sweep(dt, np_, step):
     g[a:] = patterns()[np.arange(block.total - a) % NPAT]
     trip[a:] = np.repeat(np.arange(nedge), block.n[3:]) % 3
     t32 = np.array(MASTER_TRIPLES, np.float32)
-    w, m, v = (t32[trip, j] for j in range(3))
-    lay = Layout("master", block_segs * len(hypers))
-    want = {"p16": [], "w": [], "m": [], "v": []}
+    return block_segs, block, g, tuple(t32[trip, j] for j in range(3))
+
+
+def _master_sweep(name, kernel, dt, hypers, ref, **params):
+    """g swept against the triples, one block per hyper row.
+    ref(w, g, m, v, hyper) -> {role: array} over one block."""
+    block_segs, block, g, (w, m, v) = _master_block(kernel)
+    lay = Layout(kernel, block_segs * len(hypers))
+    want = {}
     for h in hypers:
-        p16, w2, m2, v2 = adam_master_ref.step(w, store(dt, g), m, v, dt, h, np_)
-        for k, x in zip(("p16", "w", "m", "v"), (bits_of(p16), w2, m2, v2)):
-            want[k].append(x)
+        for k, x in ref(w, g, m, v, h).items():
+            want.setdefault(k, []).append(x)
     want = {k: np.concatenate(x) for k, x in want.items()}
     want["g"] = np.tile(g, len(hypers))
     inputs = {"g": np.tile(g, len(hypers)), "w": np.tile(w, len(hypers)),
               "m": np.tile(m, len(hypers)), "v": np.tile(v, len(hypers))}
-    sw = UpdateSweep("master", dt, lay, inputs, want, [("g", np.ones(lay.total, bool))],
-                     np=np_, step=step)
+    sw = UpdateSweep(name, dt, lay, inputs, want, [("g", np.ones(lay.total, bool))], **params)
     sw.hypers = hypers
     sw.hyper_of_seg = np.repeat(np.arange(len(hypers)), len(block_segs))
     return sw
+
+
+@functools.lru_cache(maxsize=2)
+def master_sweep(dt, np_, step):
+    """g swept against three fp32 (master, m, v) triples. The long segments
+    are one per triple; tail segment j has triple j % 3."""
+    import adam_master_ref
+
+    def ref(w, g, m, v, h):
+        p16, w2, m2, v2 = adam_master_ref.step(w, store(dt, g), m, v, dt, h, np_)
+        return {"p16": bits_of(p16), "w": w2, "m": m2, "v": v2}
+    return _master_sweep("master", "master", dt, adam_hypers(step), ref, np=np_, step=step)
+
+
+# ---- i, j. the gated updates ----------------------------------------------------------
+
+# an unscale (every bf16 subnormal gradient times 2^-16 is an fp32 subnormal
+# on the master and stochastic-rounding paths, and below half the smallest
+# bf16 subnormal on the plain bf16 path), and a clip
+GATED_MULS = (2.0 ** -16, 0.37)
+NROWS = 3  # tests/test_sharded_adam.py's ROWS: the three decay modes
+
+
+def gate_of(mul, skip=0):
+    """A gate as a verdict leaves it, with grad_mul = mul."""
+    import step_gate_ref
+    g = step_gate_ref.new_gate()
+    g["skip"], g["grad_mul"] = skip, np.float32(mul)
+    return g
+
+
+def _gated(s, h, mul):
+    """The gate and the step state of a gated sweep: the state adam_ref's own
+    scalars for h["step"] correspond to."""
+    import step_gate_ref
+    s.gate, s.state = gate_of(mul), step_gate_ref.scalars_of(h)
+    return s
+
+
+@functools.lru_cache(maxsize=NROWS)
+def gated_adam_sweep(np_, step, mul, row):
+    """adam_sweep's layout and settings for one row of ROWS (the gated entry
+    takes one hyper for all segments), bf16."""
+    import step_gate_ref
+    dt = "bf16"
+    h = adam_hypers(step)[row]
+    gate, state = gate_of(mul), step_gate_ref.scalars_of(h)
+
+    def ref(x, h):
+        p, m, v = step_gate_ref.update(x["p"], x["g"], x["m"], x["v"], dt, h, gate, state, np_)
+        return {"p": p, "m": m, "v": v, "g": x["g"]}
+    s = _update_sweep("adam_gated", "adam", dt, [h], ("p", "g", "m", "v"), ("p", "g", "m", "v"),
+                      _env16(dt, {"v": {"m": special(dt, "one")}}), ref,
+                      np=np_, step=step, mul=mul, row=row)
+    return _gated(s, h, mul)
+
+
+@functools.lru_cache(maxsize=NROWS)
+def gated_master_sweep(dt, np_, step, mul, row):
+    """master_sweep's layout for one row of ROWS."""
+    import step_gate_ref
+    h = adam_hypers(step)[row]
+    gate, state = gate_of(mul), step_gate_ref.scalars_of(h)
+
+    def ref(w, g, m, v, h):
+        p16, w2, m2, v2 = step_gate_ref.update_master(w, store(dt, g), m, v, dt, h, gate, state, np_)
+        return {"p16": bits_of(p16), "w": w2, "m": m2, "v": v2}
+    s = _master_sweep("master_gated", "master", dt, [h], ref, np=np_, step=step, mul=mul, row=row)
+    return _gated(s, h, mul)
+
+
+def subnormal_products(dt, g, mul, np_=0):
+    """Which gradients (bit patterns) give a non-zero fp32-subnormal
+    g / np * mul on the paths that compute in fp32 without narrowing."""
+    with np.errstate(under="ignore", invalid="ignore", over="ignore"):
+        x = widen(dt, g)
+        if np_:
+            x = x * np.float32(1.0 / np_) if np_ & (np_ - 1) == 0 else x / np.float32(np_)
+        x = np.abs(x * np.float32(mul))
+    return (x > 0) & (x < np.finfo(np.float32).tiny)
+
+
+# ---- k. the stochastic-rounding update ----------------------------------------------------
+
+SR_KEY = 0x9ABCDEF1
+SR_STRADDLES = 1  # the segment (a long one) that holds element 2^32
+
+
+def sr_tables(lay):
+    """(bases, stream words) of a layout's segments: a base (a multiple of 8)
+    and a stream word of its own for every segment; segment SR_STRADDLES
+    crosses element 2^32 and the last segment (a tail alone) holds the last
+    elements below 2^33."""
+    nseg = len(lay.n)
+    bases = 8 * (1000 * np.arange(nseg, dtype=np.int64) + 3)
+    assert bases[-1] + lay.n.max() < 1 << 32
+    bases[SR_STRADDLES] = (1 << 32) - 8 * 1001
+    bases[-1] = (1 << 33) - 8
+    streams = (0x01234567 * (np.arange(nseg, dtype=np.int64) + 1)) & 0xFFFFFFFF
+    return bases, streams
+
+
+def sr_narrow(lay, pw, mw, vw, bases, streams, key):
+    """adam_sr_ref's narrowing of fp32 (p', m', v') over a whole layout at
+    once: element i of segment s has index bases[s] + i and stream word
+    streams[s]. tests/test_sweep16.py pins it to adam_sr_ref.step segment by
+    segment."""
+    import adam_sr_ref
+    e = (np.repeat(bases - lay.start, lay.n) + np.arange(lay.total)).astype(np.uint64)
+    a, b = adam_sr_ref.philox2x32_10(e >> np.uint64(1), np.repeat(streams, lay.n), key)
+    w = np.where((e & np.uint64(1)) != 0, b, a).astype(np.uint32)
+    return (adam_sr_ref.sr(pw, w >> np.uint32(16)), f32_to_bf16_bits(mw),
+            adam_sr_ref.sr(vw, w & np.uint32(0xFFFF)))
+
+
+def _sr_sweep(name, hypers, wide, **params):
+    """adam_sweep's layout; wide(x, h) -> fp32 (p', m', v') of one row's
+    block. s.wide keeps them beside the narrowed s.want."""
+    dt = "bf16"
+
+    def ref(x, h):
+        pw, mw, vw = wide({r: bf16_bits_to_f32(x[r]) for r in ("p", "g", "m", "v")}, h)
+        return {"p": pw, "m": mw, "v": vw}
+    s = _update_sweep(name, "adam_sr", dt, hypers, ("p", "g", "m", "v"), ("p", "g", "m", "v"),
+                      _env16(dt, {"v": {"m": special(dt, "one")}}), ref, **params)
+    s.bases, s.streams = sr_tables(s.layout)
+    s.wide = s.want
+    p, m, v = sr_narrow(s.layout, s.wide["p"], s.wide["m"], s.wide["v"], s.bases, s.streams, SR_KEY)
+    s.want = {"p": p, "m": m, "v": v, "g": s.inputs["g"]}
+    for a in s.want.values():
+        a.setflags(write=False)
+    return s
+
+
+@functools.lru_cache(maxsize=2)
+def sr_sweep(np_, step):
+    """p, g, m and v swept in turn through widen, the fp32 update, sr(p'),
+    rne(m'), sr(v'); the three rows of ROWS in one call."""
+    import adam_ref
+    return _sr_sweep("adam_sr", adam_hypers(step),
+                     lambda x, h: adam_ref.step(x["p"], x["g"], x["m"], x["v"], "f32", h, np_),
+                     np=np_, step=step)
+
+
+@functools.lru_cache(maxsize=NROWS)
+def sr_gated_sweep(np_, step, mul, row):
+    import step_gate_ref
+    h = adam_hypers(step)[row]
+    gate, state = gate_of(mul), step_gate_ref.scalars_of(h)
+    s = _sr_sweep("adam_sr_gated", [h],
+                  lambda x, h: step_gate_ref.update(x["p"], x["g"], x["m"], x["v"], "f32", h, gate,
+                                                    state, np_),
+                  np=np_, step=step, mul=mul, row=row)
+    return _gated(s, h, mul)
+
+
+# ---- l. LAMB's master moments pass --------------------------------------------------------
+
+LAMB_NPS = (0, 3)
+LAMB_WDS = (0.0, 1e-2)
+
+
+def lamb_hypers(wd):
+    """A first and a later step."""
+    import lamb_ref
+    return [lamb_ref.hyper(ADAM_LR, eps=1e-6, weight_decay=wd, step=t) for t in ADAM_STEPS]
+
+
+@functools.lru_cache(maxsize=2)
+def lamb_master_sweep(dt, np_, wd):
+    """g swept against MASTER_TRIPLES as (master, m, v): m, v and u are
+    written, the master and g only read."""
+    import lamb_ref
+
+    def ref(w, g, m, v, h):
+        m2, v2, u = lamb_ref.moments(w, lamb_ref.widen16(g, dt), m, v, "f32", h, np_)
+        return {"m": m2, "v": v2, "u": u}
+    return _master_sweep("lamb_master", "lamb_master", dt, lamb_hypers(wd), ref, np=np_, wd=wd)
+
+
+# ---- m. LAMB's master apply pass: the narrowing ---------------------------------------------
+
+def narrowing_grid(dt):
+    """fp32 masters around every rounding boundary of dt: for every positive
+    finite 16-bit value, the exact tie between it and the next one (both
+    parities of the last kept bit; above the largest finite value the tie
+    narrows to inf: 65520 for f16), and one fp32 ulp either side of the tie;
+    all of that negated; fp32 subnormals, values that narrow to 16-bit
+    subnormals (in the ties already), +-0, +-inf, NaN, the fp32 extremes."""
+    elts = kernels()["master"][0]
+    top = special(dt, "max")
+    lo = widen(dt, np.arange(0, top + 1, dtype=np.uint16)).astype(np.float64)
+    hi = np.empty_like(lo)
+    hi[:-1] = lo[1:]
+    hi[-1] = 2.0 ** 128 if dt == "bf16" else 65536.0
+    tie = ((lo + hi) / 2).astype(np.float32)
+    assert np.array_equal(tie.astype(np.float64), (lo + hi) / 2)  # exact in fp32
+    below = np.nextafter(tie, np.float32(0))
+    above = np.nextafter(tie, np.float32(np.inf))
+    extra = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, np.finfo(np.float32).max,
+                      np.finfo(np.float32).smallest_subnormal, 2.0 ** -127, 2.0 ** -140,
+                      65504.0, 65519.996, 65520.0, 65520.004, 2.0 ** -24, 2.0 ** -25,
+                      2.0 ** -25 + 2.0 ** -48, 6.0e-8, 1.0, 1.0 + 2.0 ** -8, 1.0 + 2.0 ** -11],
+                     np.float32)
+    pos = np.concatenate([tie, below, above, lo.astype(np.float32), extra])
+    grid = np.concatenate([pos, -pos])
+    return grid[:grid.size - (grid.size % elts) + 3 - elts]  # a 3-element scalar tail
+
+
+APPLY_HEAD, APPLY_UNIT, APPLY_TAIL = 0, 1, 2
+APPLY_NLR = -0.01  # with u = 0: p + (nlr * 0) = p + (-0) = p, -0 included
+
+
+def apply_regions(offset, n):
+    """(head, unit, tail) element counts of a master-path piece of n elements
+    that starts `offset` elements past a 16-byte boundary in all three of its
+    arrays (kf_lamb_apply_create, apply_body): the head runs to the first
+    index at which the fp32 arrays and the 16-bit one are all 16-byte aligned."""
+    unit = kernels()["lamb_apply"][0]
+    head = min(n, (-offset) % EPV)
+    assert (offset + head) % unit == 0 or head == n
+    units = (n - head) // unit
+    return head, units * unit, n - head - units * unit
+
+
+class ApplyCase:
+    """The narrowing grid through the three paths of the master apply pass,
+    in one flat buffer per array (element i of all three arrays is the same
+    element; every buffer starts 16-byte aligned):
+
+      long   one piece at offset 0: the grid's last three values, then the
+             grid: every value in a 16-byte unit, a scalar tail after them
+      heads  pieces of 7 at element 1 of rows of 16 elements: head = 7
+      tails  pieces of 3 at element 0 of rows of 8: no unit, a tail of 3
+
+    p: the fp32 image (bit patterns; GUARD_F32 outside the pieces), used: the
+    pieces' elements, label: their region, pieces: [(start, n)]."""
+
+    def __init__(self, dt):
+        self.dt = dt
+        grid = np.ascontiguousarray(narrowing_grid(dt)).view(np.uint32)
+        self.grid = grid
+        wrap = lambda k: np.concatenate([grid, grid[:(-grid.size) % k]]).reshape(-1, k)  # noqa: E731
+        long = np.concatenate([grid[-3:], grid])
+        heads, tails = wrap(7), wrap(3)
+        self.long = (2 * EPV, long.size)
+        b0 = -(-(self.long[0] + long.size + EPV) // 16) * 16
+        self.heads = (b0, heads.shape[0])              # rows of 16 from b0, the piece at [1, 8)
+        c0 = b0 + 16 * heads.shape[0]
+        self.tails = (c0, tails.shape[0])              # rows of 8 from c0, the piece at [0, 3)
+        self.size = c0 + 8 * tails.shape[0] + EPV
+        self.p = np.full(self.size, GUARD_F32, np.uint32)
+        self.label = np.full(self.size, -1, np.int8)
+        self.pieces = [self.long]
+        self.p[self.long[0]:self.long[0] + long.size] = long
+        h, u, t = apply_regions(0, long.size)
+        self.label[self.long[0]:self.long[0] + long.size] = np.repeat(
+            [APPLY_HEAD, APPLY_UNIT, APPLY_TAIL], [h, u, t])
+        for (start, rows), data, off in ((self.heads, heads, 1), (self.tails, tails, 0)):
+            k = data.shape[1]
+            stride = 16 if off else 8
+            idx = start + off + stride * np.arange(rows)[:, None] + np.arange(k)[None, :]
+            self.p[idx] = data
+            h, u, t = apply_regions(off, k)
+            self.label[idx] = np.repeat([APPLY_HEAD, APPLY_UNIT, APPLY_TAIL], [h, u, t])[None, :]
+            self.pieces += [(int(s), k) for s in idx[:, 0]]
+        self.used = self.label >= 0
+        import lamb_ref
+        self.u = np.where(self.used, np.uint32(0), np.uint32(GUARD_F32))
+        self.want16 = np.where(self.used, lamb_ref.narrow16(self.p.view(np.float32), dt),
+                               np.uint16(GUARD))
+        for a in (self.p, self.u, self.want16, self.label, self.used):
+            a.setflags(write=False)
+
+
+@functools.lru_cache(maxsize=None)
+def apply_case(dt):
+    return ApplyCase(dt)

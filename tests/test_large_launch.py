@@ -287,3 +287,147 @@ def test_sgd_shapes(dt):
         assert ll.ceil_div(n // e, ll.TILE) == t
     rows, widest, blocks = ll.sgd_grid(ll.sgd_counts(dt, ll.SGD_FLAT_TILES), dt)
     assert not rows and blocks == [5, 1, 1, 1]  # the control: the 1-D table
+
+
+# ---- 6. the Adam-family updates' rows grids ------------------------------------------------
+
+def test_update_planner_pinned():
+    hpp = _src("kf_update_batch.hpp")
+    assert "size_t nblk = (n / elts + tile - 1) / tile;  // one block per tile" in hpp
+    assert "if (nblk < 1) nblk = 1;" in hpp
+    assert "if (nblk > 0x400000u) nblk = 0x400000u;" in hpp and ll.PLAN_BLOCK_CAP == 0x400000
+    assert "if (blocks + nblk > 0x7fffffu) {" in hpp and ll.PLAN_GRID_CAP == 0x7FFFFF
+    assert "const bool rows = a.nseg > 1 && widest * a.nseg <= 2 * blocks;" in hpp
+    assert "if (++a.nseg == NSEG) {" in hpp and "if (n == 0) continue;" in hpp
+    # the restatement on the planner's edges
+    assert ll.update_plan([0, 5, 0], 4, 1024, 24) == [(False, 1, [1])]
+    assert ll.update_plan([4096 * 3] * 25, 4, 1024, 24) == [(True, 3, [3] * 24), (False, 3, [3])]
+    assert ll.update_plan([4 * 1024 * (ll.PLAN_BLOCK_CAP + 7)], 4, 1024, 24)[0][2] == [ll.PLAN_BLOCK_CAP]
+    big = 4 * 1024 * ll.PLAN_BLOCK_CAP
+    assert [p[2] for p in ll.update_plan([big, big, 4096], 4, 1024, 24)] == \
+        [[ll.PLAN_BLOCK_CAP], [ll.PLAN_BLOCK_CAP, 1]]
+    assert ll.update_plan([4096 * 5, 4096, 4096, 4096], 4, 1024, 24) == [(False, 5, [5, 1, 1, 1])]
+    # and it is the SGD restatement's rule
+    for dt in ("f32", "f16", "bf16", "f64"):
+        for tiles in (ll.SGD_ROWS_TILES, ll.SGD_FLAT_TILES):
+            counts = ll.sgd_counts(dt, tiles)
+            assert ll.update_counts(ll.epv(dt), ll.TILE, tiles) == counts
+            (plan,) = ll.update_plan(counts, ll.epv(dt), ll.TILE, ll.SGD_SEG)
+            assert plan == ll.sgd_grid(counts, dt)
+
+
+def test_update_kernel_constants_pinned():
+    """UPDATE_KERNELS' numbers against every source file."""
+    adam, master = _src("kf_adam.hip"), _src("kf_adam_master.hip")
+    sr, lamb = _src("kf_adam_sr.hip"), _src("kf_lamb.hip")
+    k = ll.UPDATE_KERNELS
+    for dt in ("f32", "bf16", "f64"):
+        assert k["adam-" + dt] == ("kf_adam.hip", ll.epv(dt), ll.BLOCK * 4, 24)
+    assert _int(adam, r"constexpr int kAdamSeg\s*=\s*(\d+);") == 24
+    assert _int(adam, r"constexpr int kAdamBlock\s*=\s*(\d+);") == ll.BLOCK
+    assert _int(adam, r"#define KF_ADAM_UNROLL (\d+)") == 4
+    assert "counts, nb, SgdVec<T>::N, static_cast<size_t>(kAdamBlock) * kAdamUnroll," in adam
+    for dt in ("bf16", "f16"):
+        assert k["master-" + dt] == ("kf_adam_master.hip", 4, ll.BLOCK * 4, 32)
+        assert k["lamb_master-" + dt] == ("kf_lamb.hip", 4, ll.BLOCK * 4, 32)
+    assert _int(master, r"constexpr int kAdamMasterSeg\s*=\s*(\d+);") == 32
+    assert _int(master, r"constexpr int kAdamMasterBlock\s*=\s*(\d+);") == ll.BLOCK
+    assert _int(master, r"#define KF_ADAM_MASTER_ELTS (\d+)") == 4
+    assert "#define KF_ADAM_MASTER_UNROLL (16 / KF_ADAM_MASTER_ELTS)" in master
+    assert "counts, nb, kAdamMasterElts, static_cast<size_t>(kAdamMasterBlock) * kAdamMasterUnroll," \
+        in master
+    assert k["sr-bf16"] == ("kf_adam_sr.hip", 8, ll.BLOCK * 4, 32)
+    assert _int(sr, r"constexpr int kAdamSrSeg\s*=\s*(\d+);") == 32
+    assert _int(sr, r"constexpr int kAdamSrBlock\s*=\s*(\d+);") == ll.BLOCK
+    assert _int(sr, r"#define KF_ADAM_SR_UNROLL (\d+)") == 4
+    assert _int(sr, r"constexpr int kAdamSrElts\s*=\s*(\d+);") == 8
+    assert "counts, nb, kAdamSrElts, static_cast<size_t>(kAdamSrBlock) * kAdamSrUnroll," in sr
+    for dt in ("f32", "f64"):
+        assert k["lamb-" + dt] == ("kf_lamb.hip", ll.epv(dt), ll.BLOCK * 4, 24)
+    assert _int(lamb, r"constexpr int kLambSeg\s*=\s*(\d+);") == 24
+    assert _int(lamb, r"constexpr int kLambMasterSeg\s*=\s*(\d+);") == 32
+    assert _int(lamb, r"constexpr int kLambBlock\s*=\s*(\d+);") == ll.BLOCK
+    assert _int(lamb, r"constexpr int kLambUnroll\s*=\s*(\d+);") == 4
+    assert "counts, nb, SgdVec<C>::N, static_cast<size_t>(kLambBlock) * kLambUnroll," in lamb
+    # every kernel's own tile loop, tail and idle blocks, over the shared lookup
+    for src, n in ((adam, 2), (master, 2), (sr, 2), (lamb, 1)):
+        assert src.count("batch_segment(a, blk, nblk)") == n
+        assert "for (size_t t = blk; t < ntiles; t += nblk) {" in src and "if (blk == 0 && ti < n) {" in src
+
+
+@pytest.mark.parametrize("kernel", sorted(ll.UPDATE_KERNELS))
+def test_update_rows_shapes(kernel):
+    _, unit, tile, nseg = ll.UPDATE_KERNELS[kernel]
+    counts = ll.update_shape(kernel, "rows")
+    (plan,) = ll.update_plan(counts, unit, tile, nseg)
+    assert plan == (True, 5, [5, 4, 5, 3])
+    for n, t in zip(counts, ll.ROWS_TILES):
+        assert (n // unit) % tile == tile - 100 and 0 < n % unit < unit  # ragged last tile, a tail
+        assert ll.ceil_div(n // unit, tile) == t
+    assert ll.multi_tile_rows(counts, unit, tile, nseg) == (True, True)
+    counts = ll.update_shape(kernel, "tail_only")
+    (plan,) = ll.update_plan(counts, unit, tile, nseg)
+    assert plan == (True, 2, [2, 2, 2, 1])
+    # the short segment's row: `widest` blocks and no tile, block 0's tail alone
+    assert counts[3] == unit - 1 and counts[3] // unit == 0 and plan[1] == 2
+    assert ll.ceil_div(counts[3] // unit, tile) == 0 and (unit - 1 == 1) == kernel.endswith("f64")
+    assert [ll.ceil_div(n // unit, tile) for n in counts[:3]] == [2, 2, 2]
+
+
+def test_what_the_existing_kernel_tests_launch():
+    """The record: which shapes of the kernel-level tests of the Adam family
+    select a rows grid with a segment of more than one tile (first flag), and
+    whether a row then has blocks past its last tile (second flag).
+
+    The Adam, master-weight and gated tests reach rows with two-tile segments
+    through _rows_segments (three equal segments: every block has a tile).
+    Two launches do have rows with idle blocks: the first table of the bf16
+    Adam sweep (tests/sweep16.py adam_sweep, ungated, np and step as swept)
+    and the three cuts of test_sharded_adam_sr_gpu.test_split_invariance
+    (ungated, np = 0). Neither LAMB moments test, no gated or master-weight
+    launch and no launch of the stochastic-rounding kernel with np > 0 or a
+    gate does."""
+    import sweep16 as sw
+    import test_sharded_adam_gpu as ag
+    import test_sharded_adam_master_gpu as mg
+    import test_sharded_adam_sr_gpu as srg
+    import test_sharded_lamb_gpu as lg
+    k = ll.UPDATE_KERNELS
+    record = {}
+    for dt in ("f32", "bf16", "f64"):
+        _, unit, tile, nseg = k["adam-" + dt]
+        rows_n = 2 * ag.BLOCK * ag.UNROLL * unit + 3
+        record["adam-" + dt] = [ll.multi_tile_rows(c, unit, tile, nseg)
+                                for c in (ag.SIZES + (1,) * ag.N_ONES, (rows_n,) * 3)]
+    for dt in ("bf16", "f16"):
+        _, unit, tile, nseg = k["master-" + dt]
+        rows_n = 2 * mg.BLOCK * mg.UNROLL * mg.ELTS + 3
+        record["master-" + dt] = [ll.multi_tile_rows(c, unit, tile, nseg)
+                                  for c in (mg.SIZES + (1,) * mg.N_ONES, (rows_n,) * 3)]
+    _, unit, tile, nseg = k["sr-bf16"]
+    record["sr-bf16"] = [ll.multi_tile_rows(c, unit, tile, nseg) for c in
+                         (srg.SIZES + (1,) * srg.N_ONES, (8 * 129, srg.TILE + 56, srg.SIZES[-1] - 8 * 129 - srg.TILE - 56),
+                          (4096, 1011))]
+    for name, ones in (("lamb-f32", lg.LAMB_SEG), ("lamb-f64", lg.LAMB_SEG),
+                       ("lamb_master-bf16", lg.LAMB_MASTER_SEG)):
+        _, unit, tile, nseg = k[name]
+        record[name] = [ll.multi_tile_rows(lg.SIZES + (1,) * (ones + 8), unit, tile, nseg)]
+    for name, kernel, s in (("adam-bf16", "adam", sw.adam_sweep(0, 1)),
+                            ("master-bf16", "master", sw.master_sweep("bf16", 0, 1)),
+                            ("sr-bf16", "adam_sr", sw.sr_sweep(0, 1)),
+                            ("lamb_master-bf16", "lamb_master", sw.lamb_master_sweep("bf16", 0, 0.0))):
+        unit, tile, nseg = sw.kernels()[kernel]
+        assert (unit, tile, nseg) == k[name][1:]
+        record[name].append(ll.multi_tile_rows(s.layout.n.tolist(), unit, tile, nseg))
+    print(record)
+    none, equal, idle = (False, False), (True, False), (True, True)
+    assert record == {
+        # (SIZES and one-element segments, _rows_segments[, the 16-bit sweep's layout])
+        "adam-f32": [none, equal], "adam-f64": [none, equal],
+        # the sweep's first table: 12 long segments and 12 tails, 10 x 24 <= 2 * 132
+        "adam-bf16": [none, equal, idle],
+        "master-bf16": [none, equal, none], "master-f16": [none, equal],
+        # (SIZES, test_split_invariance's three cuts in one launch: 1, 2 and 2
+        # blocks, test_high_bases, the sweep)
+        "sr-bf16": [none, idle, none, none],
+        "lamb-f32": [none], "lamb-f64": [none], "lamb_master-bf16": [none, none]}

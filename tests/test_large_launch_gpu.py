@@ -2,8 +2,20 @@
 the oracle: the runtime-k fold's one-vector-in-flight loads (single and
 batched launches of 2048 blocks and more), grid-stride under a lowered block
 cap, the segmented norm's strided SQ body, its fold's eight-loads-at-a-time
-loop and its total's later LDS rounds, and the SGD update as a rows grid of
-multi-tile segments.
+loop and its total's later LDS rounds, and the SGD, Adam, master-weight,
+gated, stochastic-rounding and LAMB moments updates as rows grids of
+multi-tile segments (42 cases of the Adam family, under a second together on
+an MI355X, none above 0.1 s). What those 42 catch, measured on libraries with
+one line changed: without the g * grad_mul multiply every applied gated case
+fails, with p narrowed by r_v's bits every stochastic-rounding case. A change
+that makes two blocks of a row do the same in-place work (the scalar tail on
+the blocks after the first, `blk` for `blk == 0`; a row's blocks striding by
+one less than the row's width) rewrites what the other block has read a
+moment before, so it shows only where the blocks' timing lets it: 3 and 13
+of the 42 failed, the stochastic-rounding cases among them every time (their
+one-launch-per-segment half has a single block), while the sweeps of
+tests/test_sweep16_gpu.py, whose tails-alone tables are rows grids one block
+wide, fail on the first of the two throughout.
 
 The shapes come from tests/large_launch.py; tests/test_large_launch.py shows
 on the CPU that each reaches its path. Every reduce and blend output is
@@ -473,6 +485,279 @@ def test_sgd_rows_grid_multi_tile(dev, dt, tiles):
         assert _sgd_same(_sgd_host(ps[i], dt), wp, dt), ("param", dt, i)
         assert _sgd_same(_sgd_host(ms[i], dt), wm, dt), ("momentum", dt, i)
         assert _sgd_host(gs[i], dt).tobytes() == g.tobytes(), ("grad was written", dt, i)
+
+
+# ---- D. the Adam-family updates as rows ---------------------------------------------------
+# ROWS_TILES: segments of 5, 4, 5 and 3 tiles, a rows grid 5 wide whose rows
+# have up to two blocks without a tile. ROWS_WITH_TAIL_ONLY: three segments of
+# two tiles and one shorter than a unit, whose row does block 0's scalar tail
+# and nothing else. Every role's segments sit in one poisoned allocation.
+
+_BITS16 = ("bf16", "f16")
+_TORCH = {"f32": torch.float32, "f64": torch.float64, "bf16": torch.bfloat16, "f16": torch.float16}
+UPDATE_NP = 3
+SR_KEY = 0x9ABCDEF1
+
+
+def _as_dt(x, dt):
+    """fp64 values in dt's travelling form: numpy's own type, or uint16 bits."""
+    import sweep16 as sw
+    if dt in _BITS16:
+        return sw.narrow(dt, x.astype(np.float32))
+    return x.astype({"f32": np.float32, "f64": np.float64}[dt])
+
+
+def _f16(a, dt):
+    """uint16 bits in the form adam_master_ref takes."""
+    return a.view(np.float16) if dt == "f16" else a
+
+
+class Seated:
+    """One role's segments in one poisoned allocation: every segment starts on
+    a 16-byte boundary with at least two vectors of poison after its last
+    element. arrays[i] None: `counts[i]` elements of poison (an output)."""
+
+    def __init__(self, arrays, counts, dt, dev):
+        self.dt, self.isz, self.counts = dt, ll.ITEMSIZE[dt], counts
+        self.offs, cur = [], 16
+        for n in counts:
+            self.offs.append(cur)
+            cur += ll.ceil_div(n * self.isz, 16) * 16 + 32
+        self.host = np.full(cur, POISON, np.uint8)
+        for a, o in zip(arrays, self.offs):
+            if a is not None:
+                self.host[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8)
+        self.t = torch.from_numpy(self.host.copy()).to(dev)
+        assert self.t.data_ptr() % 16 == 0
+
+    def views(self):
+        return [self.t[o:o + n * self.isz].view(_TORCH[self.dt])
+                for o, n in zip(self.offs, self.counts)]
+
+    def check(self, want, what):
+        """Segment i holds want[i] bit for bit (NaNs by position; want None:
+        nothing at all was written) and every other byte is as it was."""
+        import sweep16 as sw
+        got = self.t.cpu().numpy()
+        if want is None:
+            assert np.array_equal(got, self.host), (what, "was written")
+            return
+        rest = got.copy()
+        for i, (w, o, n) in enumerate(zip(want, self.offs, self.counts)):
+            seg = got[o:o + n * self.isz]
+            if self.dt in _BITS16:
+                bad = sw.mismatches(self.dt, seg.view(np.uint16), np.ascontiguousarray(w).view(np.uint16))
+            else:
+                bad = sw.mismatches_float(seg.view(w.dtype), w)
+            assert bad.size == 0, (what, i, n, bad.size, bad[:4].tolist(), bad[-1])
+            rest[o:o + n * self.isz] = self.host[o:o + n * self.isz]
+        assert np.array_equal(rest, self.host), (what, "a byte outside the segments changed")
+
+
+def _update_data(kernel, shape, dt, seed):
+    """(counts, [(p, g, m, v)]) of standard-normal p, g, m and squared-normal v."""
+    counts = ll.update_shape(kernel, shape)
+    rng = np.random.default_rng(seed)
+    return counts, [tuple(_as_dt(rng.standard_normal(n) ** (2 if j == 3 else 1), dt)
+                          for j in range(4)) for n in counts]
+
+
+def _adam_hypers(n):
+    """A hyper of its own per segment: lr, decay mode and step differ."""
+    import adam_ref
+    modes = ((0.0, False), (1e-2, False), (1e-2, True), (0.0, False))
+    return [adam_ref.hyper(1e-2 / (1 + i), weight_decay=modes[i % 4][0], decoupled=modes[i % 4][1],
+                           step=1 + 2 * i) for i in range(n)]
+
+
+def _gate(skip):
+    """(hyper, reference gate, reference state, device gate, device states):
+    AdamW under a clip of 0.37 at step 5; the kernel reads group 1 of two."""
+    import adam_ref
+    import step_gate_ref
+    import test_sharded_adam_gated as gated
+    from kungfu_amd import ops
+    h = adam_ref.hyper(1e-2, weight_decay=1e-2, decoupled=True, step=5)
+    gate = dict(step_gate_ref.new_gate(), skip=skip, grad_mul=np.float32(0.37))
+    state = step_gate_ref.scalars_of(h)
+    g, st = ops.new_step_gate("cuda"), ops.new_step_states("cuda", 2)
+    gated.write_gate(g, gate)
+    gated.write_states(st, [step_gate_ref.new_state(), state])
+    return h, gate, state, g, st
+
+
+def _seat(segs, counts, dt, dev, roles=4):
+    return [Seated([seg[j] for seg in segs], counts, dt, dev) for j in range(roles)]
+
+
+@pytest.mark.parametrize("shape", ll.UPDATE_SHAPES)
+@pytest.mark.parametrize("dt", ["f32", "bf16", "f64"])
+def test_adam_rows_grid(dev, dt, shape):
+    import adam_ref
+    from kungfu_amd import ops
+    counts, segs = _update_data("adam-" + dt, shape, dt, 11)
+    hs = _adam_hypers(len(counts))
+    p, g, m, v = _seat(segs, counts, dt, dev)
+    ops.adam_update_batch_(p.views(), g.views(), m.views(), v.views(), hs, np_=UPDATE_NP)
+    torch.cuda.synchronize()
+    want = [adam_ref.step(*seg, dt, h, UPDATE_NP) for seg, h in zip(segs, hs)]
+    for j, (buf, what) in enumerate(((p, "param"), (m, "exp_avg"), (v, "exp_avg_sq"))):
+        buf.check([w[j] for w in want], (what, dt, shape))
+    g.check(None, ("grad", dt, shape))
+
+
+def _seat_master(segs, counts, dt, dev):
+    """(p16 as poison, g16, fp32 master, m, v)."""
+    g16 = Seated([seg[1] for seg in segs], counts, dt, dev)
+    p16 = Seated([None] * len(counts), counts, dt, dev)
+    return [p16, g16] + [Seated([seg[j] for seg in segs], counts, "f32", dev) for j in (0, 2, 3)]
+
+
+def _master_data(kernel, shape, dt, seed):
+    """fp32 master, m, v and a 16-bit gradient."""
+    counts, segs = _update_data(kernel, shape, "f32", seed)
+    return counts, [(seg[0], _as_dt(seg[1].astype(np.float64), dt), seg[2], seg[3]) for seg in segs]
+
+
+@pytest.mark.parametrize("shape", ll.UPDATE_SHAPES)
+@pytest.mark.parametrize("dt", _BITS16)
+def test_adam_master_rows_grid(dev, dt, shape):
+    import adam_master_ref
+    from kungfu_amd import ops
+    counts, segs = _master_data("master-" + dt, shape, dt, 12)
+    hs = _adam_hypers(len(counts))
+    bufs = _seat_master(segs, counts, dt, dev)
+    ops.adam_master_update_batch_(*[b.views() for b in bufs], hs, np_=UPDATE_NP)
+    torch.cuda.synchronize()
+    want = [adam_master_ref.step(w, _f16(g, dt), m, v, dt, h, UPDATE_NP)
+            for (w, g, m, v), h in zip(segs, hs)]
+    for j, (k, what) in enumerate(((0, "param16"), (2, "master"), (3, "exp_avg"), (4, "exp_avg_sq"))):
+        bufs[k].check([w[j] for w in want], (what, dt, shape))
+    bufs[1].check(None, ("grad", dt, shape))
+
+
+@pytest.mark.parametrize("skip", [0, 1])
+@pytest.mark.parametrize("shape", ll.UPDATE_SHAPES)
+@pytest.mark.parametrize("dt", ["f32", "bf16", "f64"])
+def test_adam_gated_rows_grid(dev, dt, shape, skip):
+    import step_gate_ref
+    from kungfu_amd import ops
+    counts, segs = _update_data("adam-" + dt, shape, dt, 13)
+    h, gate, state, dg, ds = _gate(skip)
+    p, g, m, v = _seat(segs, counts, dt, dev)
+    ops.adam_update_batch_gated_(p.views(), g.views(), m.views(), v.views(), h, dg, ds, group=1,
+                                 np_=UPDATE_NP)
+    torch.cuda.synchronize()
+    want = [step_gate_ref.update(*seg, dt, h, gate, state, UPDATE_NP) for seg in segs]
+    for j, (buf, what) in enumerate(((p, "param"), (m, "exp_avg"), (v, "exp_avg_sq"))):
+        buf.check(None if skip else [w[j] for w in want], (what, dt, shape, skip))
+    g.check(None, ("grad", dt, shape, skip))
+
+
+@pytest.mark.parametrize("skip", [0, 1])
+@pytest.mark.parametrize("shape", ll.UPDATE_SHAPES)
+@pytest.mark.parametrize("dt", _BITS16)
+def test_adam_master_gated_rows_grid(dev, dt, shape, skip):
+    import step_gate_ref
+    from kungfu_amd import ops
+    counts, segs = _master_data("master-" + dt, shape, dt, 14)
+    h, gate, state, dg, ds = _gate(skip)
+    bufs = _seat_master(segs, counts, dt, dev)
+    ops.adam_master_update_batch_gated_(*[b.views() for b in bufs], h, dg, ds, group=1, np_=UPDATE_NP)
+    torch.cuda.synchronize()
+    want = [step_gate_ref.update_master(w, _f16(g, dt), m, v, dt, h, gate, state, UPDATE_NP)
+            for w, g, m, v in segs]
+    for j, (k, what) in enumerate(((0, "param16"), (2, "master"), (3, "exp_avg"), (4, "exp_avg_sq"))):
+        bufs[k].check(None if skip else [w[j] for w in want], (what, dt, shape, skip))
+    bufs[1].check(None, ("grad", dt, shape, skip))
+
+
+@pytest.mark.parametrize("gated", [False, True], ids=["plain", "gated"])
+@pytest.mark.parametrize("shape", ll.UPDATE_SHAPES)
+def test_adam_sr_rows_grid(dev, shape, gated):
+    """The rows launch against the reference, then the same data as one
+    launch per segment (a 1-D grid each): the random bits depend on the
+    element index alone, so the bits are the same."""
+    import adam_sr_ref
+    from kungfu_amd import ops
+    dt = "bf16"
+    counts, segs = _update_data("sr-bf16", shape, dt, 15)
+    bases = [8 * (1000 * i + 3) for i in range(len(counts))]
+    streams = [(0x01234567 * (i + 1)) & 0xFFFFFFFF for i in range(len(counts))]
+    if gated:
+        h, gate, state, dg, ds = _gate(0)
+        want = [adam_sr_ref.step_gated(*seg, h, gate, state, b, s, SR_KEY, UPDATE_NP)
+                for seg, b, s in zip(segs, bases, streams)]
+    else:
+        hs = _adam_hypers(len(counts))
+        want = [adam_sr_ref.step(*seg, h, b, s, SR_KEY, UPDATE_NP)
+                for seg, h, b, s in zip(segs, hs, bases, streams)]
+
+    def run(which):
+        bufs = _seat(segs, counts, dt, dev)
+        cols = [b.views() for b in bufs]
+        for idx in which:
+            args = [[c[i] for i in idx] for c in cols]
+            tabs = ([bases[i] for i in idx], [streams[i] for i in idx], SR_KEY)
+            if gated:
+                ops.adam_sr_update_batch_gated_(*args, h, dg, ds, *tabs, group=1, np_=UPDATE_NP)
+            else:
+                ops.adam_sr_update_batch_(*args, [hs[i] for i in idx], *tabs, np_=UPDATE_NP)
+        torch.cuda.synchronize()
+        return bufs
+    together = run([list(range(len(counts)))])
+    apart = run([[i] for i in range(len(counts))])
+    for bufs, how in ((together, "rows"), (apart, "one launch per segment")):
+        for j, (k, what) in enumerate(((0, "param"), (2, "exp_avg"), (3, "exp_avg_sq"))):
+            bufs[k].check([w[j] for w in want], (what, shape, gated, how))
+        bufs[1].check(None, ("grad", shape, gated, how))
+    for a, b in zip(together, apart):
+        assert torch.equal(a.t, b.t), (shape, gated, "the grid shows in the bits")
+
+
+def _lamb_hypers(n):
+    import lamb_ref
+    return [lamb_ref.hyper(1e-2, betas=(0.9 - 0.1 * (i % 3), 0.999), eps=1e-6,
+                           weight_decay=(0.0, 1e-2)[i % 2], step=1 + i) for i in range(n)]
+
+
+@pytest.mark.parametrize("shape", ll.UPDATE_SHAPES)
+@pytest.mark.parametrize("dt", ["f32", "f64"])
+def test_lamb_moments_rows_grid(dev, dt, shape):
+    import lamb_ref
+    from kungfu_amd import ops
+    counts, segs = _update_data("lamb-" + dt, shape, dt, 16)
+    hs = _lamb_hypers(len(counts))
+    p, g, m, v = _seat(segs, counts, dt, dev)
+    u = Seated([None] * len(counts), counts, dt, dev)
+    ops.lamb_moments_batch_(p.views(), g.views(), m.views(), v.views(), u.views(), hs, np_=UPDATE_NP)
+    torch.cuda.synchronize()
+    want = [lamb_ref.moments(*seg, dt, h, UPDATE_NP) for seg, h in zip(segs, hs)]
+    for j, (buf, what) in enumerate(((m, "exp_avg"), (v, "exp_avg_sq"), (u, "update"))):
+        buf.check([w[j] for w in want], (what, dt, shape))
+    p.check(None, ("param", dt, shape))
+    g.check(None, ("grad", dt, shape))
+
+
+@pytest.mark.parametrize("shape", ll.UPDATE_SHAPES)
+@pytest.mark.parametrize("dt", _BITS16)
+def test_lamb_master_moments_rows_grid(dev, dt, shape):
+    import lamb_ref
+    from kungfu_amd import ops
+    counts, segs = _master_data("lamb_master-" + dt, shape, dt, 17)
+    hs = _lamb_hypers(len(counts))
+    g = Seated([seg[1] for seg in segs], counts, dt, dev)
+    w, m, v = (Seated([seg[j] for seg in segs], counts, "f32", dev) for j in (0, 2, 3))
+    u = Seated([None] * len(counts), counts, "f32", dev)
+    ops.lamb_master_moments_batch_(g.views(), w.views(), m.views(), v.views(), u.views(), hs,
+                                   np_=UPDATE_NP)
+    torch.cuda.synchronize()
+    want = [lamb_ref.moments(sw_, lamb_ref.widen16(sg, dt), sm, sv, "f32", h, UPDATE_NP)
+            for (sw_, sg, sm, sv), h in zip(segs, hs)]
+    for j, (buf, what) in enumerate(((m, "exp_avg"), (v, "exp_avg_sq"), (u, "update"))):
+        buf.check([x[j] for x in want], (what, dt, shape))
+    w.check(None, ("master", dt, shape))
+    g.check(None, ("grad", dt, shape))
 
 
 # ---- A3. grid-stride under a lowered block cap (keep these last) ---------------------------

@@ -12,6 +12,7 @@ import torch
 import adam_master_ref
 import adam_ref
 import loopback
+import sweep16
 import test_sharded_adam_gpu as gpu
 import test_sharded_adam_master as cpu
 
@@ -160,31 +161,9 @@ def test_other_dtypes_are_refused():
 
 # ---- the narrowing ------------------------------------------------------------
 
-def _narrowing_grid(dt):
-    """fp32 masters around every rounding boundary of dt: for every positive
-    finite 16-bit value, the exact tie between it and the next one (both
-    parities of the last kept bit; above the largest finite value the tie
-    narrows to inf: 65520 for f16), and one fp32 ulp either side of the tie;
-    all of that negated; fp32 subnormals, values that narrow to 16-bit
-    subnormals (in the ties already), +-0, +-inf, NaN, the fp32 extremes."""
-    top = 0x7F7F if dt == "bf16" else 0x7BFF
-    h = np.arange(0, top + 1, dtype=np.uint16)
-    lo = adam_master_ref.widen(h.view(adam_master_ref.STORAGE[dt]), dt).astype(np.float64)
-    hi = np.empty_like(lo)
-    hi[:-1] = lo[1:]
-    hi[-1] = 2.0 ** 128 if dt == "bf16" else 65536.0
-    tie = ((lo + hi) / 2).astype(np.float32)
-    assert np.array_equal(tie.astype(np.float64), (lo + hi) / 2)  # exact in fp32
-    below = np.nextafter(tie, np.float32(0))
-    above = np.nextafter(tie, np.float32(np.inf))
-    extra = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, np.finfo(np.float32).max,
-                      np.finfo(np.float32).smallest_subnormal, 2.0 ** -127, 2.0 ** -140,
-                      65504.0, 65519.996, 65520.0, 65520.004, 2.0 ** -24, 2.0 ** -25,
-                      2.0 ** -25 + 2.0 ** -48, 6.0e-8, 1.0, 1.0 + 2.0 ** -8, 1.0 + 2.0 ** -11],
-                     np.float32)
-    pos = np.concatenate([tie, below, above, lo.astype(np.float32), extra])
-    grid = np.concatenate([pos, -pos])
-    return grid[:grid.size - (grid.size % ELTS) + 3 - ELTS]  # a 3-element scalar tail
+# the grid of fp32 masters around every rounding boundary of dt, shared with
+# the LAMB apply pass's narrowing test (tests/test_sweep16_gpu.py)
+_narrowing_grid = sweep16.narrowing_grid
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])

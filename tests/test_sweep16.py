@@ -423,6 +423,267 @@ def test_master_cases(dt, np_, step):
     assert (s.want["m"][:n].astype(np.float64)[fin] != e[fin]).any()
 
 
+# ---- the gated, stochastic-rounding and LAMB cases ---------------------------------------
+
+def test_newer_kernels_constants_are_the_sources():
+    import test_sharded_adam_sr
+    import test_sharded_lamb
+    k = sw.kernels()
+    assert k["adam_sr"] == (8, 256 * 4, test_sharded_adam_sr.SR_SEG)
+    assert k["lamb_master"] == (4, 256 * 4, test_sharded_lamb.LAMB_MASTER_SEG)
+    assert k["lamb_apply"][:2] == (4, 256 * 4)
+    assert sw.NROWS == len(sw.adam_hypers(1))
+    assert sw.GATED_MULS == (2.0 ** -16, 0.37)
+
+
+def _no_mul(dt, g):
+    """Gradients on which a finite non-zero grad_mul cannot show: zeros,
+    infinities and NaNs."""
+    return sw.is_zero(g) | ~sw.is_finite(dt, g)
+
+
+@pytest.mark.parametrize("mul", sw.GATED_MULS)
+@pytest.mark.parametrize("step", sw.ADAM_STEPS)
+@pytest.mark.parametrize("np_", sw.ADAM_NPS)
+def test_gated_adam_cases(np_, step, mul):
+    import adam_ref
+    import test_sharded_adam
+    dt = "bf16"
+    decays = set()
+    for row in range(sw.NROWS):
+        s = sw.gated_adam_sweep(np_, step, mul, row)
+        assert [r for r, _ in s.swept] == ["p", "g", "m", "v"] and len(s.hypers) == 1
+        assert ALL_CLASSES - {"inexact"} <= _check_update(s, ("p", "m", "v"))
+        h = s.hypers[0]
+        assert (h["weight_decay"], h["decoupled"]) == test_sharded_adam.ROWS[row]
+        decays.add((h["weight_decay"] != 0, h["decoupled"]))
+        assert s.gate["skip"] == 0 and s.gate["grad_mul"] == np.float32(mul) != 1
+        assert s.state["step"] == step
+        # against the ungated update of the same inputs: other bits where the
+        # multiply can show, the same where it cannot
+        x = s.inputs
+        ungated = adam_ref.step(x["p"], x["g"], x["m"], x["v"], dt, h, np_)
+        masks = dict(s.swept)
+        for r, a in zip(("p", "m", "v"), ungated):
+            same = sw.mismatches(dt, s.want[r], a).size == 0
+            assert not same, (r, row)
+            quiet = _no_mul(dt, x["g"])
+            assert sw.mismatches(dt, s.want[r][quiet], a[quiet]).size == 0, (r, row)
+        assert (s.want["m"][masks["g"]] != ungated[1][masks["g"]]).any()
+        if mul == 2.0 ** -16:
+            # R(g * 2^-16) of a subnormal g is a zero: m' and v' of the g
+            # sweep's setting (p, m, v) = (1, 0, 0) are zeros there
+            sub = masks["g"] & sw.is_subnormal(dt, x["g"]) & (x["m"] == 0) & (x["v"] == 0)
+            if not (h["weight_decay"] != 0 and not h["decoupled"]):  # L2 adds wd * p to g
+                full = sub & (s.layout.label == sw.FULL)
+                assert np.unique(x["g"][full]).size == 2 * 127 and (sub & ~full).any()
+                assert sw.is_zero(s.want["m"][sub]).all() and sw.is_zero(s.want["v"][sub]).all()
+    assert len(decays) == 3  # all three decay modes
+
+
+def _subnormal_count(s, np_, mul):
+    """Distinct swept gradient patterns whose product is an fp32 subnormal."""
+    mask = dict(s.swept)["g"]
+    g = s.inputs["g"][mask]
+    return np.unique(g[sw.subnormal_products(s.dt, g, mul, np_)]).size
+
+
+@pytest.mark.parametrize("mul", sw.GATED_MULS)
+@pytest.mark.parametrize("step", sw.ADAM_STEPS)
+@pytest.mark.parametrize("np_", sw.ADAM_NPS)
+@pytest.mark.parametrize("dt", DTS)
+def test_gated_master_cases(dt, np_, step, mul):
+    """With grad_mul = 2^-16 every bf16 gradient below 2^-110 in magnitude,
+    the subnormals (2 * 127 patterns) and sixteen binades of normal values
+    (2 * 16 * 128), gives an exact, non-zero fp32-subnormal product: 4350
+    patterns at np = 0. The smallest f16 value is 2^-24: no f16 gradient
+    reaches that range."""
+    import adam_master_ref
+    for row in range(sw.NROWS):
+        s = sw.gated_master_sweep(dt, np_, step, mul, row)
+        got = _check_update(s, ("p16",))
+        assert "nan" in got and len(s.hypers) == 1
+        h, x = s.hypers[0], s.inputs
+        ungated = adam_master_ref.step(x["w"], sw.store(dt, x["g"]), x["m"], x["v"], dt, h, np_)
+        quiet = _no_mul(dt, x["g"])
+        for r, a in zip(("w", "m", "v"), ungated[1:]):
+            assert sw.mismatches_float(s.want[r], a).size, (r, row)
+            assert sw.mismatches_float(s.want[r][quiet], a[quiet]).size == 0, (r, row)
+        count = _subnormal_count(s, np_, mul)
+        print("fp32-subnormal products:", dt, np_, mul, count)
+        if dt == "f16":
+            assert count == 0
+            continue
+        if mul != 2.0 ** -16:  # a bf16 subnormal is an fp32 subnormal as it stands
+            assert count >= 2 * 127
+            continue
+        assert count == (4350 if np_ == 0 else count) and count >= 4350
+        if h["weight_decay"] != 0 and not h["decoupled"]:
+            continue  # L2 adds wd * master to the product
+        # they reach m' = c1 * that product as non-zero subnormals (m = 0)
+        hit = sw.subnormal_products(dt, x["g"], mul, np_) & (x["m"] == 0)
+        body = hit & (s.layout.label == sw.FULL)
+        tail = hit & (s.layout.label == sw.TAIL)
+        tiny = np.finfo(np.float32).tiny
+        for where in (body, tail):
+            m = np.abs(s.want["m"][where])
+            assert ((m > 0) & (m < tiny)).sum() > 1000
+
+
+@pytest.mark.parametrize("step", sw.ADAM_STEPS)
+@pytest.mark.parametrize("np_", sw.ADAM_NPS)
+def test_sr_cases(np_, step):
+    import adam_sr_ref
+    s = sw.sr_sweep(np_, step)
+    dt, lay = "bf16", s.layout
+    assert [r for r, _ in s.swept] == ["p", "g", "m", "v"] and len(s.hypers) == sw.NROWS
+    got = _check_update(s, ("p", "m", "v"))
+    assert {"overflow", "subnormal", "negzero", "nan"} <= got, got
+    # negative and NaN exp_avg_sq pass through the sqrt in a full tile and in a tail
+    l2 = np.repeat([h["weight_decay"] != 0 and not h["decoupled"] for h in s.hypers],
+                   lay.total // len(s.hypers))  # there wd * p joins the gradient
+    neg_v = dict(s.swept)["v"] & (s.inputs["v"] > 0x8000) & (s.inputs["g"] == 0) & ~l2
+    assert np.unique(s.inputs["v"][neg_v & (lay.label == sw.FULL)]).size == 0x7FFF
+    assert np.unique(s.inputs["v"][neg_v & (lay.label == sw.TAIL)]).size > 10000  # every third tail
+    for reg in (sw.FULL, sw.TAIL):
+        assert sw.is_nan(dt, s.want["p"][neg_v & (lay.label == reg)]).all()
+    # the tables: a base of its own (a multiple of 8) and a stream word of
+    # its own per segment, one long segment over element 2^32, a tail alone
+    # up to the last element a pair index can name
+    b, st = s.bases, s.streams
+    assert (b % 8 == 0).all() and np.unique(b).size == b.size and np.unique(st).size == st.size
+    assert (b + lay.n <= 1 << 33).all() and st.max() < 1 << 32
+    k = sw.SR_STRADDLES
+    assert b[k] < 1 << 32 < b[k] + lay.n[k] and (lay.label[lay.seg(k)] == sw.FULL).any()
+    cut = (1 << 32) - b[k]
+    assert lay.label[lay.seg(k)][cut] == sw.FULL  # the crossing is inside a full tile
+    assert b[-1] + 8 == 1 << 33 and lay.n[-1] == 7 and (lay.label[lay.seg(-1 % len(lay.n))] == sw.TAIL).all()
+    # stochastic somewhere: not the round-to-nearest bits; and where p' (v')
+    # is a bf16 already, that bf16 whatever the random word
+    for r in ("p", "v"):
+        wide = s.wide[r]
+        rne = sw.narrow(dt, wide)
+        fin = np.isfinite(wide)
+        diff = fin & (s.want[r] != rne)
+        assert diff.sum() > 1000, (r, diff.sum())
+        exact = fin & ((wide.view(np.uint32) & 0xFFFF) == 0)
+        assert exact.sum() > 1000 and (s.want[r][exact] == rne[exact]).all()
+        # never further than one bf16 from the truncation
+        trunc = (wide.view(np.uint32) >> 16).astype(np.uint16)
+        assert ((s.want[r][fin] == trunc[fin]) | (s.want[r][fin] == trunc[fin] + 1)).all()
+    assert sw.mismatches(dt, s.want["m"], sw.narrow(dt, s.wide["m"])).size == 0
+    # the whole-layout narrowing is adam_sr_ref.step segment by segment
+    rng = np.random.default_rng(np_ + 10 * step)
+    nbody = 12
+    pick = [0, k, 2, nbody, len(lay.n) - 1] + list(rng.integers(0, len(lay.n), 60))
+    for i in pick:
+        sl = lay.seg(int(i))
+        h = s.hypers[s.hyper_of_seg[i]]
+        want = adam_sr_ref.step(*(s.inputs[r][sl] for r in ("p", "g", "m", "v")), h, int(b[i]),
+                                int(st[i]), sw.SR_KEY, np_)
+        for r, a in zip(("p", "m", "v"), want):
+            assert sw.mismatches(dt, s.want[r][sl], a).size == 0, (i, r)
+            ok = ~sw.is_nan(dt, a)
+            assert np.array_equal(s.want[r][sl][ok], a[ok])
+
+
+def test_sr_gated_case():
+    import adam_sr_ref
+    np_, step, mul = 3, sw.ADAM_STEPS[1], sw.GATED_MULS[0]
+    for row in range(sw.NROWS):
+        s = sw.sr_gated_sweep(np_, step, mul, row)
+        lay = s.layout
+        _check_update(s, ("p", "m", "v"))
+        count = _subnormal_count(s, np_, mul)
+        print("fp32-subnormal products, SR:", row, count)
+        assert count >= 4350
+        plain = sw.sr_sweep(np_, step)
+        n = lay.total
+        sl = slice(row * n, (row + 1) * n)
+        assert np.array_equal(plain.inputs["g"][sl], s.inputs["g"])
+        assert sw.mismatches(s.dt, plain.want["m"][sl], s.want["m"]).size  # grad_mul took part
+        for i in (0, sw.SR_STRADDLES, len(lay.n) - 1, len(lay.n) // 2):
+            seg = lay.seg(i)
+            want = adam_sr_ref.step_gated(*(s.inputs[r][seg] for r in ("p", "g", "m", "v")),
+                                          s.hypers[0], s.gate, s.state, int(s.bases[i]),
+                                          int(s.streams[i]), sw.SR_KEY, np_)
+            for r, a in zip(("p", "m", "v"), want):
+                assert sw.mismatches(s.dt, s.want[r][seg], a).size == 0, (row, i, r)
+
+
+@pytest.mark.parametrize("wd", sw.LAMB_WDS)
+@pytest.mark.parametrize("np_", sw.LAMB_NPS)
+@pytest.mark.parametrize("dt", DTS)
+def test_lamb_master_cases(dt, np_, wd):
+    """Every widened gradient reaches the fp32 m, v and u through a full
+    tile's 8-byte loads and through the scalar tail."""
+    s = sw.lamb_master_sweep(dt, np_, wd)
+    _check_coverage(s)
+    lay = s.layout
+    assert not lay.res.any() and len(lay.n) > 2 * lay.per_launch
+    assert len(s.hypers) == len(sw.ADAM_STEPS) and all(h["weight_decay"] == wd for h in s.hypers)
+    assert set(s.want) == {"m", "v", "u", "g"} and np.array_equal(s.want["g"], s.inputs["g"])
+    body = lay.label == sw.FULL
+    for t in sw.MASTER_TRIPLES:
+        assert _holds_all(s.inputs["g"], np.flatnonzero(body & (s.inputs["w"] == np.float32(t[0]))))
+    g = s.inputs["g"]
+    bad = ~sw.is_finite(dt, g)
+    assert np.isnan(s.want["u"][bad]).all() and np.isfinite(s.want["u"][~bad]).all()
+    assert np.isinf(s.want["v"][sw.is_inf(dt, g)]).all()
+    # the weight decay shows in u alone
+    other = sw.lamb_master_sweep(dt, np_, sw.LAMB_WDS[1 - sw.LAMB_WDS.index(wd)])
+    assert sw.mismatches_float(s.want["u"], other.want["u"]).size
+    assert sw.mismatches_float(s.want["m"], other.want["m"]).size == 0
+
+
+@pytest.mark.parametrize("dt", DTS)
+def test_apply_narrowing_case(dt):
+    """Every value of the narrowing grid passes through a scalar head, a
+    16-byte unit and a scalar tail of the apply pass, by the kernel's own
+    split of a piece."""
+    c = sw.apply_case(dt)
+    unit, tile, _ = sw.kernels()["lamb_apply"]
+    grid = np.unique(c.grid)
+    for reg in (sw.APPLY_HEAD, sw.APPLY_UNIT, sw.APPLY_TAIL):
+        assert np.array_equal(np.unique(c.p[c.label == reg]), grid), reg
+    # the kernel's split, piece by piece: head = elements up to the first index
+    # at which the fp32 arrays (4 to 16 bytes) and p16 (8) are all aligned
+    seen = set()
+    for start, n in c.pieces[:1] + c.pieces[1::997] + c.pieces[-1:]:
+        head = next(h for h in range(9) if (start + h) % 4 == 0 and (start + h) % 8 == 0)
+        head = min(head, n)
+        nunit = (n - head) // unit
+        want = [sw.APPLY_HEAD] * head + [sw.APPLY_UNIT] * (nunit * unit) + \
+            [sw.APPLY_TAIL] * (n - head - nunit * unit)
+        assert np.array_equal(c.label[start:start + n], want), (start, n)
+        seen.add((start % 8, n, head))
+    n_long = c.long[1]
+    assert seen == {(0, n_long, 0), (1, 7, 7), (0, 3, 0)}
+    assert n_long // unit > tile and (n_long // unit) % tile and n_long % unit  # full, ragged, tail
+    # pieces do not touch: a guard element before and after every one
+    starts = np.array([s for s, _ in c.pieces])
+    ends = starts + np.array([n for _, n in c.pieces])
+    assert (np.diff(starts) > 0).all() and (starts[1:] > ends[:-1]).all()
+    assert not c.used[starts - 1].any() and not c.used[ends].any() and c.used.sum() == (ends - starts).sum()
+    assert not c.used[:8].any() and not c.used[-8:].any()
+    # what the narrowing is there for: ties, 16-bit subnormal results, the
+    # overflow to inf from a finite value, both zeros, NaN
+    f = c.p.view(np.float32)[c.used]
+    w16 = c.want16[c.used]
+    back = sw.widen(dt, w16).astype(np.float64)
+    fin = np.isfinite(f) & sw.is_finite(dt, w16)
+    mag = (w16 & 0x7FFF).astype(np.uint16)
+    up = sw.widen64(dt, mag + 1) - sw.widen64(dt, mag)
+    down = sw.widen64(dt, mag) - sw.widen64(dt, np.maximum(mag, 1) - 1)
+    with np.errstate(invalid="ignore"):  # inf - inf
+        err = np.abs(f.astype(np.float64) - back) * 2
+    tie = fin & (err > 0) & ((err == up) | (err == down))
+    assert tie.sum() > 3 * 30000 and ((w16[tie] & 1) == 0).all()  # ties go to even
+    assert sw.is_subnormal(dt, w16).any() and (np.isfinite(f) & sw.is_inf(dt, w16)).any()
+    assert (w16 == 0x8000).any() and (w16 == 0).any() and sw.is_nan(dt, w16).any()
+    assert sw.APPLY_NLR < 0
+
+
 # ---- the references against exact rational arithmetic ----------------------------------
 
 def _fields(dt, b):

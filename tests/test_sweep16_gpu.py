@@ -21,6 +21,22 @@ at a = 0 alone). Neither fails tests/test_pairavg_gpu.py or
 tests/test_monitor_gpu.py. A plain f32_to_f16 of the f16 products (the -0
 defect of the /np average's scalar edges) fails test_avg[f16] at every
 power-of-two np, head and tail, and test_sgd_update[f16-4].
+
+The kernels added after that sweep: the gated Adam updates (bf16, and bf16 /
+f16 gradients on fp32 masters) at grad_mul = 2^-16 and 0.37, one call per
+decay mode; the stochastic-rounding update (p, g, m and v through widen, the
+fp32 update, sr(p'), rne(m'), sr(v'); one segment over element 2^32, one up
+to 2^33) and its gated twin; LAMB's master moments pass; and the narrowing of
+LAMB's master apply pass through its scalar heads, 16-byte units and scalar
+tails. Measured on an MI355X: these 39 cases take 38 s (the 55 before them
+32 s); the slowest are test_adam_update_gated_bf16 (1.3 to 2.1 s a case, three
+calls each), test_adam_sr_update (1.3 to 1.5 s) and
+test_adam_master_update_gated (0.7 to 0.9 s). With one line of a kernel
+changed: without the g * grad_mul multiply every gated case fails; with p
+narrowed by r_v's bits every stochastic-rounding case; with the scalar tail on
+the blocks after the first (`blk` for `blk == 0`) every update case; with
+truncation in the apply pass's narrowing test_lamb_master_apply_narrowing of
+that type, in head, unit and tail.
 """
 import ctypes
 
@@ -326,7 +342,7 @@ def _run_update(dev, s, roles16, roles32, call, written):
     written roles with the reference and the others with what went in."""
     tdt = TORCH[s.dt]
     placed = {r: Placed(dev, s.layout, s.inputs.get(r)) for r in roles16}
-    placed.update({r: Placed(dev, s.layout, s.inputs[r], f32=True) for r in roles32})
+    placed.update({r: Placed(dev, s.layout, s.inputs.get(r), f32=True) for r in roles32})
     views = {r: placed[r].views(tdt) for r in roles16}
     views.update({r: placed[r].views(torch.float32) for r in roles32})
     hypers = [s.hypers[i] for i in s.hyper_of_seg]
@@ -371,3 +387,135 @@ def test_adam_master_update(dev, dt, np_, step):
                 lambda v, h: ops.adam_master_update_batch_(v["p16"], v["g"], v["w"], v["m"], v["v"],
                                                            h, np_=np_),
                 written=("p16", "w", "m", "v"))
+
+
+# ---- i, j. the gated updates --------------------------------------------------------------
+
+def _gate_tensors(s):
+    """The sweep's gate and step state on the device; the kernel reads group
+    1 of two."""
+    import step_gate_ref
+    import test_sharded_adam_gated as gated
+    from kungfu_amd import ops
+    g, st = ops.new_step_gate("cuda"), ops.new_step_states("cuda", 2)
+    gated.write_gate(g, s.gate)
+    gated.write_states(st, [step_gate_ref.new_state(), s.state])
+    return g, st
+
+
+@pytest.mark.parametrize("mul", sw.GATED_MULS)
+@pytest.mark.parametrize("step", sw.ADAM_STEPS)
+@pytest.mark.parametrize("np_", sw.ADAM_NPS)
+def test_adam_update_gated_bf16(dev, np_, step, mul):
+    """One call per row of ROWS: the gated entry takes one hyper."""
+    from kungfu_amd import ops
+    for row in range(sw.NROWS):
+        s = sw.gated_adam_sweep(np_, step, mul, row)
+        g, st = _gate_tensors(s)
+        _run_update(dev, s, ("p", "g", "m", "v"), (),
+                    lambda v, h: ops.adam_update_batch_gated_(v["p"], v["g"], v["m"], v["v"], h[0],
+                                                              g, st, group=1, np_=np_),
+                    written=("p", "m", "v"))
+
+
+@pytest.mark.parametrize("mul", sw.GATED_MULS)
+@pytest.mark.parametrize("step", sw.ADAM_STEPS)
+@pytest.mark.parametrize("np_", sw.ADAM_NPS)
+@pytest.mark.parametrize("dt", DTS)
+def test_adam_master_update_gated(dev, dt, np_, step, mul):
+    from kungfu_amd import ops
+    for row in range(sw.NROWS):
+        s = sw.gated_master_sweep(dt, np_, step, mul, row)
+        g, st = _gate_tensors(s)
+        _run_update(dev, s, ("p16", "g"), ("w", "m", "v"),
+                    lambda v, h: ops.adam_master_update_batch_gated_(
+                        v["p16"], v["g"], v["w"], v["m"], v["v"], h[0], g, st, group=1, np_=np_),
+                    written=("p16", "w", "m", "v"))
+
+
+# ---- k. the stochastic-rounding update -------------------------------------------------------
+
+@pytest.mark.parametrize("step", sw.ADAM_STEPS)
+@pytest.mark.parametrize("np_", sw.ADAM_NPS)
+def test_adam_sr_update(dev, np_, step):
+    from kungfu_amd import ops
+    s = sw.sr_sweep(np_, step)
+    _run_update(dev, s, ("p", "g", "m", "v"), (),
+                lambda v, h: ops.adam_sr_update_batch_(v["p"], v["g"], v["m"], v["v"], h,
+                                                       s.bases.tolist(), s.streams.tolist(),
+                                                       sw.SR_KEY, np_=np_),
+                written=("p", "m", "v"))
+
+
+def test_adam_sr_update_gated(dev):
+    """The unscale: grad_mul = 2^-16, a row of ROWS per call."""
+    from kungfu_amd import ops
+    np_, step, mul = 3, sw.ADAM_STEPS[1], sw.GATED_MULS[0]
+    for row in range(sw.NROWS):
+        s = sw.sr_gated_sweep(np_, step, mul, row)
+        g, st = _gate_tensors(s)
+        _run_update(dev, s, ("p", "g", "m", "v"), (),
+                    lambda v, h: ops.adam_sr_update_batch_gated_(
+                        v["p"], v["g"], v["m"], v["v"], h[0], g, st, s.bases.tolist(),
+                        s.streams.tolist(), sw.SR_KEY, group=1, np_=np_),
+                    written=("p", "m", "v"))
+
+
+# ---- l. LAMB's master moments pass -----------------------------------------------------------
+
+@pytest.mark.parametrize("wd", sw.LAMB_WDS)
+@pytest.mark.parametrize("np_", sw.LAMB_NPS)
+@pytest.mark.parametrize("dt", DTS)
+def test_lamb_master_moments(dev, dt, np_, wd):
+    from kungfu_amd import ops
+    s = sw.lamb_master_sweep(dt, np_, wd)
+    _run_update(dev, s, ("g",), ("w", "m", "v", "u"),
+                lambda v, h: ops.lamb_master_moments_batch_(v["g"], v["w"], v["m"], v["v"], v["u"],
+                                                            h, np_=np_),
+                written=("m", "v", "u"))
+
+
+# ---- m. LAMB's master apply pass: the narrowing ------------------------------------------------
+
+@pytest.mark.parametrize("dt", DTS)
+def test_lamb_master_apply_narrowing(dev, dt):
+    """The narrowing grid through the scalar heads, the 16-byte units and the
+    scalar tails of the apply pass, u = 0 and a negative nlr: the fp32
+    parameter comes back as it went in (-0 too), p16 is its round-to-nearest
+    narrowing, and the guard words between the pieces of all three arrays
+    keep their bits."""
+    from kungfu_amd import ops
+    c = sw.apply_case(dt)
+    p = torch.from_numpy(c.p.view(np.int32).copy()).to(dev).view(torch.float32)
+    u = torch.from_numpy(c.u.view(np.int32).copy()).to(dev).view(torch.float32)
+    p16 = torch.from_numpy(np.full(c.size, sw.GUARD, np.uint16).view(np.int16)).to(dev).view(TORCH[dt])
+    assert all(t.data_ptr() % 16 == 0 for t in (p, u, p16))
+
+    def views(t):
+        (a, n), (b, hrows), (cc, trows) = c.long, c.heads, c.tails
+        return ([t[a:a + n]] + list(t[b:b + 16 * hrows].view(hrows, 16)[:, 1:8].unbind(0))
+                + list(t[cc:cc + 8 * trows].view(trows, 8)[:, 0:3].unbind(0)))
+    vp, vu, v16 = views(p), views(u), views(p16)
+    assert len(vp) == len(c.pieces)
+    for i in (0, 1, len(vp) - 1):  # the views are the pieces
+        assert vp[i].data_ptr() == p.data_ptr() + 4 * c.pieces[i][0] and vp[i].numel() == c.pieces[i][1]
+    plan = ops.LambApplyPlan(vp, vu, [0] * len(vp), 1, v16)
+    try:
+        plan.run(torch.tensor([sw.APPLY_NLR], dtype=torch.float64, device=dev))
+        torch.cuda.synchronize()
+    finally:
+        plan.close()
+    gp = p.cpu().numpy().view(np.uint32)
+    g16 = p16.view(torch.int16).cpu().numpy().view(np.uint16)
+    names = ("head", "unit", "tail")
+    bad = sw.mismatches_float(gp.view(np.float32), c.p.view(np.float32))
+    assert bad.size == 0, ("fp32 parameter", dt, sorted({names[r] for r in c.label[bad] if r >= 0}),
+                           [(int(i), hex(int(gp[i])), hex(int(c.p[i]))) for i in bad[:8]])
+    bad = sw.mismatches(dt, g16, c.want16)
+    assert bad.size == 0, ("p16", dt, sorted({names[r] for r in c.label[bad] if r >= 0}),
+                           [(int(i), hex(int(c.p[i])), hex(int(g16[i])), hex(int(c.want16[i])))
+                            for i in bad[:8]])
+    assert np.array_equal(u.cpu().numpy().view(np.uint32), c.u), "the update was written"
+    # -0 went through all three paths
+    neg0 = c.used & (c.p == 0x80000000)
+    assert {int(r) for r in c.label[neg0]} == {0, 1, 2} and (g16[neg0] == 0x8000).all()
