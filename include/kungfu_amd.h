@@ -446,7 +446,8 @@ int kf_adam_sr_narrow(const void *x, const void *r, void *out, size_t n, void *s
  *
  * Non-finite gradients are NOT skipped: an inf or a NaN in a gradient reaches
  * m, v, u, the tensor's norms and through them its parameters, as it does in
- * torch.optim.Adam. There is no gate on this path. */
+ * torch.optim.Adam. There is no gate on this path; the entries under a gate
+ * are "LAMB under a gate" below. */
 
 /* The moments pass over nb segments of one dtype, one launch per 24 of them
  * (f32, f64) or per 32 (master path). kf_adam_update_batch's conventions:
@@ -499,6 +500,70 @@ kf_lamb_apply_t *kf_lamb_apply_create(void *const *params, const void *const *up
                                       int ntensor, KungFu_Datatype dt);
 int kf_lamb_apply_run(kf_lamb_apply_t *p, const double *nlr, void *stream);
 void kf_lamb_apply_destroy(kf_lamb_apply_t *p);
+
+/* ---- LAMB under a gate: clipping, loss scale and skipped steps -------------
+ *
+ * The LAMB step above under the gated step's verdict (kf_step_gate_update,
+ * DESIGN.md §19): kernels of their own beside the parents' in kf_lamb.hip,
+ * through the parents' bodies. A step is
+ *   A  every group: the exchange's reduce of the gradients to this rank's shards
+ *   B  per dtype: kf_segnorm over this rank's gradient shards -> one fp64 sum
+ *   C  kf_exchange_all_gather_doubles of those sums
+ *   D  kf_step_gate_update, unchanged, called with every group's lr = 1.0
+ *   E  every group: the gated moments pass
+ *   F  per (dtype, device): the norm plan over the 2T (p, u) pieces and the
+ *      all-gather of its sums, as without a gate
+ *   G  the gated trust update; the gated apply run
+ *   H  every group: the all-gather of the parameters
+ * all queued on one stream; nothing is allocated per step and the host never
+ * waits for the verdict.
+ *
+ * D, the lr = 1 rule. kf_step_state.nss_f64 is -(lr / (1 - beta1_pow)); with
+ * lr = 1 it is -(1 / bias_correction1). The gated moments kernel takes
+ * rb1 = -nss (nss_f64 for f64, nss otherwise) and s2 from the state. Negation
+ * is exact and the cast to fp32 commutes with it, so rb1 equals the ungated
+ * (C)(1 / bias_correction1) bit for bit whenever bias_correction1 ==
+ * 1 - beta1_pow. The real lr goes to the trust update only, as without a gate.
+ *
+ * E. Every block reads gate->skip; on a skipped step the kernel returns before
+ * touching exp_avgs, exp_avg_sqs, updates, params or masters. Otherwise it is
+ * pass 1 above with exactly one operation inserted directly after the /np:
+ *   g = (g * grad_mul)
+ * rounded to C (f32 on the master path), and with s2 and rb1 from *state. ONE
+ * hyper serves the whole call; its lr, decoupled and bias corrections are
+ * ignored (kf_adam_update_batch_gated's rule).
+ *
+ * F runs unconditionally: it only reads, and on a skipped step it reads the
+ * previous u.
+ *
+ * G. kf_lamb_trust_update_gated returns on skip and leaves nlr[] and ratio[] as
+ * they were: they describe the last applied step. kf_lamb_apply_run_gated
+ * returns on skip before any load of the table, params, updates or params16.
+ * Otherwise both are their parents' arithmetic, operation for operation.
+ *
+ * A skipped step leaves every byte of params, params16, masters, exp_avgs,
+ * exp_avg_sqs, updates, nlr, ratio and every group's step state as it was; the
+ * loss scale and the counters follow kf_step_gate_update's rule.
+ *
+ * Checks, all before any HIP call: the parents', plus gate and state not NULL
+ * (KF_ERR_ARG). gate and state are device pointers written by an earlier
+ * kf_step_gate_update on the same stream; state is the segments' group's. */
+int kf_lamb_moments_batch_gated(const void *const *params, const void *const *grads,
+                                void *const *exp_avgs, void *const *exp_avg_sqs,
+                                void *const *updates, const size_t *counts, int nb,
+                                KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
+                                const kf_step_gate *gate, const kf_step_state *state, void *stream);
+int kf_lamb_master_moments_batch_gated(const void *const *grads16, const void *const *masters,
+                                       void *const *exp_avgs, void *const *exp_avg_sqs,
+                                       void *const *updates, const size_t *counts, int nb,
+                                       KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
+                                       const kf_step_gate *gate, const kf_step_state *state,
+                                       void *stream);
+int kf_lamb_trust_update_gated(const double *sq, int world, int ntensor, const int *group_of,
+                               const kf_lamb_group *groups, int ngroup, double trust_clip,
+                               double *nlr, double *ratio, const kf_step_gate *gate, void *stream);
+int kf_lamb_apply_run_gated(kf_lamb_apply_t *p, const double *nlr, const kf_step_gate *gate,
+                            void *stream);
 
 /* ---- gradient monitors: segmented squared norms ------------------------- */
 

@@ -139,6 +139,10 @@ EXPORTED = (
     "kf_adam_sr_update_batch",
     "kf_adam_sr_update_batch_gated",
     "kf_adam_sr_narrow",
+    "kf_lamb_moments_batch_gated",
+    "kf_lamb_master_moments_batch_gated",
+    "kf_lamb_trust_update_gated",
+    "kf_lamb_apply_run_gated",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -572,6 +576,18 @@ def load():
     lib.kf_lamb_apply_create.restype = c_void_p
     lib.kf_lamb_apply_run.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.kf_lamb_apply_run.restype = c_int
+    lib.kf_lamb_moments_batch_gated.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_void_p),
+                                                P(c_void_p), P(c_size_t), c_int, c_int, c_int,
+                                                P(AdamHyper), c_void_p, c_void_p, c_void_p]
+    lib.kf_lamb_moments_batch_gated.restype = c_int
+    lib.kf_lamb_master_moments_batch_gated.argtypes = lib.kf_lamb_moments_batch_gated.argtypes
+    lib.kf_lamb_master_moments_batch_gated.restype = c_int
+    lib.kf_lamb_trust_update_gated.argtypes = [c_void_p, c_int, c_int, c_void_p, P(LambGroup),
+                                               c_int, ctypes.c_double, c_void_p, c_void_p,
+                                               c_void_p, c_void_p]
+    lib.kf_lamb_trust_update_gated.restype = c_int
+    lib.kf_lamb_apply_run_gated.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.kf_lamb_apply_run_gated.restype = c_int
     lib.kf_lamb_apply_destroy.argtypes = [c_void_p]
     lib.kf_lamb_apply_destroy.restype = None
     lib.kf_exchange_gather_params_batch.argtypes = [c_void_p, P(c_void_p), P(c_size_t), c_int,

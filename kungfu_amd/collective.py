@@ -128,6 +128,22 @@ class HipEpilogue:
         (ops.LambApplyPlan), built once over fixed views."""
         return ops.LambApplyPlan(params, updates, tensors, ntensor, params16)
 
+    # -- LAMB under a gate (DESIGN.md §19); the apply plan's run takes gate= --
+    def lamb_moments_gated_(self, params, grads, exp_avgs, exp_avg_sqs, updates, hyper, gate,
+                            states, group, np_):
+        return ops.lamb_moments_batch_gated_(params, grads, exp_avgs, exp_avg_sqs, updates, hyper,
+                                             gate, states, group, np_)
+
+    def lamb_master_moments_gated_(self, grads16, masters, exp_avgs, exp_avg_sqs, updates, hyper,
+                                   gate, states, group, np_):
+        return ops.lamb_master_moments_batch_gated_(grads16, masters, exp_avgs, exp_avg_sqs,
+                                                    updates, hyper, gate, states, group, np_)
+
+    def lamb_trust_update_gated_(self, sq, world, group_of, groups, nlr, ratio, gate,
+                                 trust_clip=0.0):
+        return ops.lamb_trust_update_gated_(sq, world, group_of, groups, nlr, ratio, gate,
+                                            trust_clip)
+
 
 def coalesce_runs(buckets):
     """Maximal runs of buckets that are consecutive in one storage, each as

@@ -24,6 +24,13 @@
 //
 // The arithmetic is kf_lamb_math.hpp's, one IEEE operation per parenthesis, no
 // contraction (the pragma of kf_reduce_kernels.hpp and -ffp-contract=off).
+//
+// Every kernel has a sibling under a step gate (include/kungfu_amd.h "LAMB
+// under a gate"), lamb_*_gated_kernel, which reads the verdict
+// of kf_step_gate.hip from device memory: a skipped step returns before it
+// touches anything, an applied one multiplies the gradient by grad_mul after
+// the /np and takes s2 and rb1 from the group's step state. They run the
+// parents' bodies; the parents' device code does not change with them.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -84,6 +91,11 @@ template <typename C, int NSEG> struct LambArgs {
 };
 static_assert(sizeof(LambArgs<double, kLambSeg>) + sizeof(Div) <= 3072, "kernarg budget");
 static_assert(sizeof(LambArgs<float, kLambMasterSeg>) + sizeof(Div) <= 3072, "kernarg budget");
+// the gated kernels: div, padding and the gate and step-state pointers behind it
+static_assert(sizeof(LambArgs<double, kLambSeg>) + sizeof(Div) + 8 + 2 * sizeof(void *) <= 3072,
+              "kernarg budget, gated");
+static_assert(sizeof(LambArgs<float, kLambMasterSeg>) + sizeof(Div) + 8 + 2 * sizeof(void *) <= 3072,
+              "kernarg budget, gated");
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
@@ -124,10 +136,11 @@ template <typename C> struct LambGrad<C, C> {
 };
 
 // one unit: m, v and u stored
-template <typename C, typename G, int DIV, int DECAY>
+template <typename C, typename G, int DIV, int DECAY, typename GATE = AdamNoGate>
 __device__ __forceinline__ void lamb_unit(const LambSeg<C> &h, const Div &d, size_t ui,
                                           const typename LambGrad<C, G>::R &rg, const u32x4 &rp,
-                                          const u32x4 &rm, const u32x4 &rv)
+                                          const u32x4 &rm, const u32x4 &rv,
+                                          const GATE &gate = GATE{})
 {
     using SV        = SgdVec<C>;
     using X         = typename SV::X;
@@ -137,15 +150,16 @@ __device__ __forceinline__ void lamb_unit(const LambSeg<C> &h, const Div &d, siz
     SV::unpack(rp, p);
     SV::unpack(rm, m);
     SV::unpack(rv, v);
-    lamb_math<C, DIV, DECAY, H, X>(p, g, m, v, u, h.k, d);
+    lamb_math<C, DIV, DECAY, H, X>(p, g, m, v, u, h.k, d, gate);
     st_u4<0>(h.m, ui, SV::pack(m));
     st_u4<0>(h.v, ui, SV::pack(v));
     st_u4<KF_LAMB_U_NT>(h.u, ui, SV::pack(u));
 }
 
 // Block `blk` of `nblk` on one segment.
-template <typename C, typename G, int DIV, int DECAY>
-__device__ __forceinline__ void lamb_body(const LambSeg<C> &h, const Div &d, size_t blk, size_t nblk)
+template <typename C, typename G, int DIV, int DECAY, typename GATE = AdamNoGate>
+__device__ __forceinline__ void lamb_body(const LambSeg<C> &h, const Div &d, size_t blk, size_t nblk,
+                                          const GATE &gate = GATE{})
 {
     using LG        = LambGrad<C, G>;
     constexpr int N = SgdVec<C>::N;
@@ -161,7 +175,7 @@ __device__ __forceinline__ void lamb_body(const LambSeg<C> &h, const Div &d, siz
         C *su = reinterpret_cast<C *>(h.u);
         const C p[1] = {sp[ti]};
         C g[1] = {LG::scalar(h.g, ti)}, m[1] = {sm[ti]}, v[1] = {sv[ti]}, u[1];
-        lamb_math<C, DIV, DECAY, 1, C>(p, g, m, v, u, h.k, d);
+        lamb_math<C, DIV, DECAY, 1, C>(p, g, m, v, u, h.k, d, gate);
         sm[ti] = m[0];
         sv[ti] = v[0];
         su[ti] = u[0];
@@ -186,7 +200,7 @@ __device__ __forceinline__ void lamb_body(const LambSeg<C> &h, const Div &d, siz
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                lamb_unit<C, G, DIV, DECAY>(h, d, u0 + u * B, rg[u], rp[u], rm[u], rv[u]);
+                lamb_unit<C, G, DIV, DECAY>(h, d, u0 + u * B, rg[u], rp[u], rm[u], rv[u], gate);
             }
         } else {
             // ragged last tile
@@ -196,20 +210,21 @@ __device__ __forceinline__ void lamb_body(const LambSeg<C> &h, const Div &d, siz
                 const typename LG::R rg = LG::ld(h.g, ui);
                 const u32x4 rp = ld_u4<KF_LAMB_P_NT>(h.p, ui), rm = ld_u4<KF_LAMB_MV_NT>(h.m, ui),
                             rv = ld_u4<KF_LAMB_MV_NT>(h.v, ui);
-                lamb_unit<C, G, DIV, DECAY>(h, d, ui, rg, rp, rm, rv);
+                lamb_unit<C, G, DIV, DECAY>(h, d, ui, rg, rp, rm, rv, gate);
             }
         }
     }
 }
 
-template <typename C, typename G, typename ARGS>
-__device__ __forceinline__ void lamb_moments(const ARGS &a, const Div &np, int div)
+template <typename C, typename G, typename ARGS, typename GATE = AdamNoGate>
+__device__ __forceinline__ void lamb_moments(const ARGS &a, const Div &np, int div,
+                                             const GATE &gate = GATE{})
 {
     size_t blk, nblk;  // kf_update_batch.hpp's two grids
     const LambSeg<C> &g = a.seg[batch_segment(a, blk, nblk)];
     dispatch_div(div, [&](auto DIV) {
-        if (g.k.decay) lamb_body<C, G, decltype(DIV)::value, 1>(g, np, blk, nblk);
-        else lamb_body<C, G, decltype(DIV)::value, 0>(g, np, blk, nblk);
+        if (g.k.decay) lamb_body<C, G, decltype(DIV)::value, 1>(g, np, blk, nblk, gate);
+        else lamb_body<C, G, decltype(DIV)::value, 0>(g, np, blk, nblk, gate);
     });
 }
 
@@ -229,6 +244,32 @@ __global__ void __launch_bounds__(kLambBlock)
     lamb_moments<float, T>(a, np, div);
 }
 
+// The moments pass under a step gate (include/kungfu_amd.h "LAMB under a
+// gate"): a skipped step returns before anything is loaded; otherwise grad_mul,
+// s2 and rb1 = -nss come from device memory, the segments' own s2 and rb1 are
+// not read.
+template <typename T>
+__global__ void __launch_bounds__(kLambBlock)
+    lamb_moments_gated_kernel(LambArgs<T, kLambSeg> a, Div np, int div,
+                              const kf_step_gate *__restrict__ gate,
+                              const kf_step_state *__restrict__ st)
+{
+    AdamGate<T> gt;
+    if (adam_gate_load(gate, st, gt)) return;
+    lamb_moments<T, T>(a, np, div, gt);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kLambBlock)
+    lamb_master_moments_gated_kernel(LambArgs<float, kLambMasterSeg> a, Div np, int div,
+                                     const kf_step_gate *__restrict__ gate,
+                                     const kf_step_state *__restrict__ st)
+{
+    AdamGate<float> gt;
+    if (adam_gate_load(gate, st, gt)) return;
+    lamb_moments<float, T>(a, np, div, gt);
+}
+
 // ---- the trust ratios ----------------------------------------------------------
 
 struct TrustArgs {
@@ -243,6 +284,44 @@ __global__ void __launch_bounds__(kLambBlock)
                       const int *__restrict__ group_of, TrustArgs a, double clip,
                       double *__restrict__ nlr, double *__restrict__ ratio)
 {
+    const size_t t = static_cast<size_t>(blockIdx.x) * kLambBlock + threadIdx.x;
+    if (t >= static_cast<size_t>(ntensor)) return;
+    const int j = group_of[t] - a.g0;
+    if (j < 0 || j >= a.ng) return;
+    const size_t row = 2 * static_cast<size_t>(ntensor);
+    double P = 0.0, U = 0.0;
+    for (int r = 0; r < world; ++r) {
+        P = __dadd_rn(P, sq[r * row + t]);
+        U = __dadd_rn(U, sq[r * row + ntensor + t]);
+    }
+    const double wn = __dsqrt_rn(P), un = __dsqrt_rn(U);
+    // kTrustGroups selects instead of an indexed kernarg read (no scratch copy)
+    double lr = 0.0;
+    int adapt = 0;
+#pragma unroll
+    for (int i = 0; i < kTrustGroups; ++i) {
+        if (i == j) {
+            lr    = a.lr[i];
+            adapt = a.adapt[i];
+        }
+    }
+    double x = (adapt && wn > 0.0 && un > 0.0) ? __ddiv_rn(wn, un) : 1.0;
+    if (clip > 0.0) x = x < clip ? x : clip;
+    nlr[t]   = -__dmul_rn(lr, x);
+    ratio[t] = x;
+}
+
+// Under a step gate: a skipped step leaves nlr[] and ratio[] as they were.
+// lamb_trust_kernel's statements, written out again: `a` handed to a shared
+// function is copied out of the kernarg segment first, and the parent's
+// instruction stream would change with it.
+__global__ void __launch_bounds__(kLambBlock)
+    lamb_trust_gated_kernel(const double *__restrict__ sq, int world, int ntensor,
+                            const int *__restrict__ group_of, TrustArgs a, double clip,
+                            double *__restrict__ nlr, double *__restrict__ ratio,
+                            const kf_step_gate *__restrict__ gate)
+{
+    if (gate->skip != 0) return;
     const size_t t = static_cast<size_t>(blockIdx.x) * kLambBlock + threadIdx.x;
     if (t >= static_cast<size_t>(ntensor)) return;
     const int j = group_of[t] - a.g0;
@@ -413,6 +492,27 @@ __global__ void __launch_bounds__(kLambBlock)
     lamb_apply<float, T>(tab, npiece, nlr);
 }
 
+// Under a step gate: a skipped step returns before the table, p, u or p16 are
+// loaded.
+template <typename T>
+__global__ void __launch_bounds__(kLambBlock)
+    lamb_apply_gated_kernel(const LambPiece *__restrict__ tab, int npiece,
+                            const double *__restrict__ nlr, const kf_step_gate *__restrict__ gate)
+{
+    if (gate->skip != 0) return;
+    lamb_apply<T, void>(tab, npiece, nlr);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kLambBlock)
+    lamb_master_apply_gated_kernel(const LambPiece *__restrict__ tab, int npiece,
+                                   const double *__restrict__ nlr,
+                                   const kf_step_gate *__restrict__ gate)
+{
+    if (gate->skip != 0) return;
+    lamb_apply<float, T>(tab, npiece, nlr);
+}
+
 }  // namespace kf
 
 struct kf_lamb_apply {
@@ -431,12 +531,17 @@ constexpr UpdateFail fail_master{"kf_lamb_master_moments_batch"};
 constexpr UpdateFail fail_trust{"kf_lamb_trust_update"};
 constexpr UpdateFail fail_create{"kf_lamb_apply_create"};
 constexpr UpdateFail fail_run{"kf_lamb_apply_run"};
+constexpr UpdateFail fail_moments_gated{"kf_lamb_moments_batch_gated"};
+constexpr UpdateFail fail_master_gated{"kf_lamb_master_moments_batch_gated"};
+constexpr UpdateFail fail_trust_gated{"kf_lamb_trust_update_gated"};
+constexpr UpdateFail fail_run_gated{"kf_lamb_apply_run_gated"};
 
-// C: compute type, NSEG: segments per launch
+// C: compute type, NSEG: segments per launch. one: hyper[0] is every
+// segment's (the gated entries), else hyper[b] is segment b's.
 template <typename C, int NSEG, typename LAUNCH>
 int launch_moments(const void *const *ps, const void *const *gs, void *const *ms, void *const *vs,
                    void *const *us, const size_t *counts, int nb, const kf_adam_hyper *hyper,
-                   LAUNCH &&launch)
+                   LAUNCH &&launch, bool one = false)
 {
     return plan_update_batch<LambArgs<C, NSEG>>(
         counts, nb, SgdVec<C>::N, static_cast<size_t>(kLambBlock) * kLambUnroll,
@@ -447,7 +552,7 @@ int launch_moments(const void *const *ps, const void *const *gs, void *const *ms
             g.v = vs[b];
             g.u = us[b];
             g.n = counts[b];
-            lamb_scalars<C>(g.k, hyper[b]);
+            lamb_scalars<C>(g.k, hyper[one ? 0 : b]);
         },
         launch);
 }
@@ -455,7 +560,7 @@ int launch_moments(const void *const *ps, const void *const *gs, void *const *ms
 // Both moments entries: every check comes before any HIP call.
 int moments_checks(const UpdateFail &fail, const void *const *ps, const void *const *gs,
                    void *const *ms, void *const *vs, void *const *us, const size_t *counts, int nb,
-                   int np, const kf_adam_hyper *hyper)
+                   int np, const kf_adam_hyper *hyper, bool one = false)
 {
     if (!ps || !gs || !ms || !vs || !us || !counts || !hyper) {
         return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
@@ -469,21 +574,94 @@ int moments_checks(const UpdateFail &fail, const void *const *ps, const void *co
         if (off16(ps[b]) || off16(gs[b]) || off16(ms[b]) || off16(vs[b]) || off16(us[b])) {
             return fail(KF_ERR_ARG, "KF_ERR_ARG", "pointers must be 16-byte aligned");
         }
-        if (!(hyper[b].bias_correction1 > 0) || !(hyper[b].bias_correction2 > 0)) {
+        const kf_adam_hyper &h = hyper[one ? 0 : b];
+        if (!(h.bias_correction1 > 0) || !(h.bias_correction2 > 0)) {
             return fail(KF_ERR_ARG, "KF_ERR_ARG", "bias corrections must be > 0");
         }
     }
     return KF_OK;
 }
 
-template <typename T> void launch_apply(const kf_lamb_apply *p, const double *nlr, hipStream_t s)
+// gate == nullptr: the parent kernel
+template <typename T>
+void launch_apply(const kf_lamb_apply *p, const double *nlr, hipStream_t s,
+                  const kf_step_gate *gate = nullptr)
 {
-    lamb_apply_kernel<T><<<p->blocks, kLambBlock, 0, s>>>(p->tab, p->npiece, nlr);
+    if (gate) {
+        lamb_apply_gated_kernel<T><<<p->blocks, kLambBlock, 0, s>>>(p->tab, p->npiece, nlr, gate);
+    } else {
+        lamb_apply_kernel<T><<<p->blocks, kLambBlock, 0, s>>>(p->tab, p->npiece, nlr);
+    }
 }
 template <typename T>
-void launch_master_apply(const kf_lamb_apply *p, const double *nlr, hipStream_t s)
+void launch_master_apply(const kf_lamb_apply *p, const double *nlr, hipStream_t s,
+                         const kf_step_gate *gate = nullptr)
 {
-    lamb_master_apply_kernel<T><<<p->blocks, kLambBlock, 0, s>>>(p->tab, p->npiece, nlr);
+    if (gate) {
+        lamb_master_apply_gated_kernel<T>
+            <<<p->blocks, kLambBlock, 0, s>>>(p->tab, p->npiece, nlr, gate);
+    } else {
+        lamb_master_apply_kernel<T><<<p->blocks, kLambBlock, 0, s>>>(p->tab, p->npiece, nlr);
+    }
+}
+
+// Both trust entries: every check comes before any HIP call. gate == nullptr:
+// the parent kernel.
+int trust_entry(const UpdateFail &fail, const double *sq, int world, int ntensor,
+                const int *group_of, const kf_lamb_group *groups, int ngroup, double trust_clip,
+                double *nlr, double *ratio, const kf_step_gate *gate, void *stream)
+{
+    if (world < 1 || ntensor < 1 || ngroup < 1) {
+        return fail(KF_ERR_ARG, "KF_ERR_ARG", "world, ntensor and ngroup must be at least 1");
+    }
+    if (!sq || !group_of || !groups || !nlr || !ratio) {
+        return fail(KF_ERR_ARG, "KF_ERR_ARG", "null pointer");
+    }
+    if (trust_clip != trust_clip) return fail(KF_ERR_ARG, "KF_ERR_ARG", "trust_clip is NaN");
+    hipStream_t s       = static_cast<hipStream_t>(stream);
+    const unsigned grid = (static_cast<unsigned>(ntensor) + kLambBlock - 1) / kLambBlock;
+    for (int g0 = 0; g0 < ngroup; g0 += kTrustGroups) {
+        TrustArgs a;
+        a.g0 = g0;
+        a.ng = ngroup - g0 < kTrustGroups ? ngroup - g0 : kTrustGroups;
+        for (int i = 0; i < kTrustGroups; ++i) {
+            a.lr[i]    = i < a.ng ? groups[g0 + i].lr : 0.0;
+            a.adapt[i] = i < a.ng ? (groups[g0 + i].adapt != 0) : 0;
+        }
+        if (gate) {
+            lamb_trust_gated_kernel<<<grid, kLambBlock, 0, s>>>(sq, world, ntensor, group_of, a,
+                                                                trust_clip, nlr, ratio, gate);
+        } else {
+            lamb_trust_kernel<<<grid, kLambBlock, 0, s>>>(sq, world, ntensor, group_of, a,
+                                                          trust_clip, nlr, ratio);
+        }
+        const int rc = launch_status(fail);
+        if (rc != KF_OK) return rc;
+    }
+    return KF_OK;
+}
+
+// Both apply entries.
+int apply_entry(const UpdateFail &fail, kf_lamb_apply *p, const double *nlr,
+                const kf_step_gate *gate, void *stream)
+{
+    if (p->blocks == 0) return KF_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (p->dt) {
+    case KungFu_FLOAT: launch_apply<float>(p, nlr, s, gate); break;
+    case KungFu_DOUBLE: launch_apply<double>(p, nlr, s, gate); break;
+    case KungFu_BFLOAT16: launch_master_apply<bf16_t>(p, nlr, s, gate); break;
+    default: launch_master_apply<f16_t>(p, nlr, s, gate); break;
+    }
+    return launch_status(fail);
+}
+
+// The bias corrections of a gated call's one hyper are the device's.
+kf_adam_hyper gated_hyper(const kf_adam_hyper *hyper)
+{
+    kf_adam_hyper one    = *hyper;
+    one.bias_correction1 = one.bias_correction2 = 1.0;
+    return one;
 }
 
 }  // namespace
@@ -559,30 +737,96 @@ int kf_lamb_trust_update(const double *sq, int world, int ntensor, const int *gr
                          const kf_lamb_group *groups, int ngroup, double trust_clip, double *nlr,
                          double *ratio, void *stream)
 {
-    const UpdateFail &fail = fail_trust;
-    if (world < 1 || ntensor < 1 || ngroup < 1) {
-        return fail(KF_ERR_ARG, "KF_ERR_ARG", "world, ntensor and ngroup must be at least 1");
+    return trust_entry(fail_trust, sq, world, ntensor, group_of, groups, ngroup, trust_clip, nlr,
+                       ratio, nullptr, stream);
+}
+
+int kf_lamb_trust_update_gated(const double *sq, int world, int ntensor, const int *group_of,
+                               const kf_lamb_group *groups, int ngroup, double trust_clip,
+                               double *nlr, double *ratio, const kf_step_gate *gate, void *stream)
+{
+    if (!gate) return fail_trust_gated(KF_ERR_ARG, "KF_ERR_ARG", "null gate");
+    return trust_entry(fail_trust_gated, sq, world, ntensor, group_of, groups, ngroup, trust_clip,
+                       nlr, ratio, gate, stream);
+}
+
+int kf_lamb_moments_batch_gated(const void *const *params, const void *const *grads,
+                                void *const *exp_avgs, void *const *exp_avg_sqs,
+                                void *const *updates, const size_t *counts, int nb,
+                                KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
+                                const kf_step_gate *gate, const kf_step_state *state, void *stream)
+{
+    const UpdateFail &fail = fail_moments_gated;
+    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
+    if (nb == 0) return KF_OK;
+    if (!gate || !state) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null gate or step state");
+    if (dt != KungFu_FLOAT && dt != KungFu_DOUBLE) {
+        return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
+                    "f32 and f64 only (bf16 and f16 take kf_lamb_master_moments_batch_gated)");
     }
-    if (!sq || !group_of || !groups || !nlr || !ratio) {
-        return fail(KF_ERR_ARG, "KF_ERR_ARG", "null pointer");
+    if (!hyper) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
+    const kf_adam_hyper one = gated_hyper(hyper);
+    const int rc = moments_checks(fail, params, grads, exp_avgs, exp_avg_sqs, updates, counts, nb,
+                                  np, &one, true);
+    if (rc != KF_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Div dv  = update_div(np);
+    const int div = update_div_code(np, dv);
+    if (dt == KungFu_FLOAT) {
+        return launch_moments<float, kLambSeg>(
+            params, grads, exp_avgs, exp_avg_sqs, updates, counts, nb, &one,
+            [&](unsigned gx, unsigned gy, const LambArgs<float, kLambSeg> &a) {
+                lamb_moments_gated_kernel<float>
+                    <<<dim3(gx, gy), kLambBlock, 0, s>>>(a, dv, div, gate, state);
+                return launch_status(fail);
+            },
+            true);
     }
-    if (trust_clip != trust_clip) return fail(KF_ERR_ARG, "KF_ERR_ARG", "trust_clip is NaN");
-    hipStream_t s       = static_cast<hipStream_t>(stream);
-    const unsigned grid = (static_cast<unsigned>(ntensor) + kLambBlock - 1) / kLambBlock;
-    for (int g0 = 0; g0 < ngroup; g0 += kTrustGroups) {
-        TrustArgs a;
-        a.g0 = g0;
-        a.ng = ngroup - g0 < kTrustGroups ? ngroup - g0 : kTrustGroups;
-        for (int i = 0; i < kTrustGroups; ++i) {
-            a.lr[i]    = i < a.ng ? groups[g0 + i].lr : 0.0;
-            a.adapt[i] = i < a.ng ? (groups[g0 + i].adapt != 0) : 0;
+    return launch_moments<double, kLambSeg>(
+        params, grads, exp_avgs, exp_avg_sqs, updates, counts, nb, &one,
+        [&](unsigned gx, unsigned gy, const LambArgs<double, kLambSeg> &a) {
+            lamb_moments_gated_kernel<double>
+                <<<dim3(gx, gy), kLambBlock, 0, s>>>(a, dv, div, gate, state);
+            return launch_status(fail);
+        },
+        true);
+}
+
+int kf_lamb_master_moments_batch_gated(const void *const *grads16, const void *const *masters,
+                                       void *const *exp_avgs, void *const *exp_avg_sqs,
+                                       void *const *updates, const size_t *counts, int nb,
+                                       KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
+                                       const kf_step_gate *gate, const kf_step_state *state,
+                                       void *stream)
+{
+    const UpdateFail &fail = fail_master_gated;
+    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
+    if (nb == 0) return KF_OK;
+    if (!gate || !state) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null gate or step state");
+    if (dt != KungFu_BFLOAT16 && dt != KungFu_FLOAT16) {
+        return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
+                    "bf16 and f16 gradients only (f32 and f64 take kf_lamb_moments_batch_gated)");
+    }
+    if (!hyper) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
+    const kf_adam_hyper one = gated_hyper(hyper);
+    const int rc = moments_checks(fail, masters, grads16, exp_avgs, exp_avg_sqs, updates, counts, nb,
+                                  np, &one, true);
+    if (rc != KF_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Div dv  = update_div(np);
+    const int div = update_div_code(np, dv);
+    auto launch   = [&](unsigned gx, unsigned gy, const LambArgs<float, kLambMasterSeg> &a) {
+        if (dt == KungFu_BFLOAT16) {
+            lamb_master_moments_gated_kernel<bf16_t>
+                <<<dim3(gx, gy), kLambBlock, 0, s>>>(a, dv, div, gate, state);
+        } else {
+            lamb_master_moments_gated_kernel<f16_t>
+                <<<dim3(gx, gy), kLambBlock, 0, s>>>(a, dv, div, gate, state);
         }
-        lamb_trust_kernel<<<grid, kLambBlock, 0, s>>>(sq, world, ntensor, group_of, a, trust_clip,
-                                                      nlr, ratio);
-        const int rc = launch_status(fail);
-        if (rc != KF_OK) return rc;
-    }
-    return KF_OK;
+        return launch_status(fail);
+    };
+    return launch_moments<float, kLambMasterSeg>(masters, grads16, exp_avgs, exp_avg_sqs, updates,
+                                                 counts, nb, &one, launch, true);
 }
 
 kf_lamb_apply_t *kf_lamb_apply_create(void *const *params, const void *const *updates,
@@ -678,17 +922,16 @@ kf_lamb_apply_t *kf_lamb_apply_create(void *const *params, const void *const *up
 
 int kf_lamb_apply_run(kf_lamb_apply_t *p, const double *nlr, void *stream)
 {
-    const UpdateFail &fail = fail_run;
-    if (!p || !nlr) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null plan or nlr");
-    if (p->blocks == 0) return KF_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (p->dt) {
-    case KungFu_FLOAT: launch_apply<float>(p, nlr, s); break;
-    case KungFu_DOUBLE: launch_apply<double>(p, nlr, s); break;
-    case KungFu_BFLOAT16: launch_master_apply<bf16_t>(p, nlr, s); break;
-    default: launch_master_apply<f16_t>(p, nlr, s); break;
-    }
-    return launch_status(fail);
+    if (!p || !nlr) return fail_run(KF_ERR_ARG, "KF_ERR_ARG", "null plan or nlr");
+    return apply_entry(fail_run, p, nlr, nullptr, stream);
+}
+
+int kf_lamb_apply_run_gated(kf_lamb_apply_t *p, const double *nlr, const kf_step_gate *gate,
+                            void *stream)
+{
+    if (!p || !nlr) return fail_run_gated(KF_ERR_ARG, "KF_ERR_ARG", "null plan or nlr");
+    if (!gate) return fail_run_gated(KF_ERR_ARG, "KF_ERR_ARG", "null gate");
+    return apply_entry(fail_run_gated, p, nlr, gate, stream);
 }
 
 void kf_lamb_apply_destroy(kf_lamb_apply_t *p)

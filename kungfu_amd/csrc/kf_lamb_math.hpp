@@ -32,16 +32,43 @@ template <typename C> inline void lamb_scalars(LambScalars<C> &k, const kf_adam_
     k.rb1   = static_cast<C>(1.0 / h.bias_correction1);
 }
 
+// s2 and rb1 of a moments pass: the segment's own, or the gate's (kf_adam_math.hpp's
+// AdamGate<C>, read by adam_gate_load). The gate's step state was advanced with
+// lr = 1, so its nss is -(1 / (1 - beta1_pow)) and rb1 = -nss, exactly.
+template <typename C> __device__ __forceinline__ C lamb_s2(const LambScalars<C> &h, const AdamNoGate &)
+{
+    return h.s2;
+}
+template <typename C> __device__ __forceinline__ C lamb_rb1(const LambScalars<C> &h, const AdamNoGate &)
+{
+    return h.rb1;
+}
+template <typename C> __device__ __forceinline__ C lamb_s2(const LambScalars<C> &, const AdamGate<C> &gate)
+{
+    return gate.s2;
+}
+template <typename C> __device__ __forceinline__ C lamb_rb1(const LambScalars<C> &, const AdamGate<C> &gate)
+{
+    return -gate.nss;
+}
+
 // The moments of H values (V = C) or H lane pairs (V = SgdElt<T>::X), T float
 // or double: g holds the summed gradients on entry; m and v are updated, u is
 // the update direction; p is only read. DECAY is the segment's choice, made
-// once per block.
-template <typename T, int DIV, int DECAY, int H, typename V, typename C>
+// once per block. A gate adds g = (g * mul) after the /np and replaces h.s2
+// and h.rb1 (include/kungfu_amd.h "LAMB under a gate").
+template <typename T, int DIV, int DECAY, int H, typename V, typename C,
+          typename GATE = AdamNoGate>
 __device__ __forceinline__ void lamb_math(const V (&p)[H], V (&g)[H], V (&m)[H], V (&v)[H],
-                                          V (&u)[H], const LambScalars<C> &h, const Div &d)
+                                          V (&u)[H], const LambScalars<C> &h, const Div &d,
+                                          const GATE &gate = GATE{})
 {
 #pragma unroll
     for (int i = 0; i < H; ++i) g[i] = SgdDiv<T, DIV>::run(g[i], d);
+    if constexpr (GATE::on) {
+#pragma unroll
+        for (int i = 0; i < H; ++i) g[i] = g[i] * gate.mul;
+    }
 #pragma unroll
     for (int i = 0; i < H; ++i) {
         const V t = h.b1 * m[i];
@@ -56,10 +83,10 @@ __device__ __forceinline__ void lamb_math(const V (&p)[H], V (&g)[H], V (&m)[H],
 #pragma unroll
     for (int i = 0; i < H; ++i) {
         const V r = adam_sqrt(v[i]);
-        const V e = adam_div(r, h.s2);
+        const V e = adam_div(r, lamb_s2(h, gate));
         const V f = e + h.eps;
         const V q = adam_div(m[i], f);
-        u[i]      = h.rb1 * q;
+        u[i]      = lamb_rb1(h, gate) * q;
         if constexpr (DECAY != 0) u[i] = u[i] + h.w * p[i];
     }
 }

@@ -597,6 +597,96 @@ def lamb_trust_update_(sq, world, group_of, groups, nlr, ratio, trust_clip=0.0, 
     return nlr
 
 
+# -- LAMB under a gate (include/kungfu_amd.h "LAMB under a gate")
+
+def lamb_moments_batch_gated_(params, grads, exp_avgs, exp_avg_sqs, updates, hyper, gate, states,
+                              group=0, np_=0, stream=None):
+    """lamb_moments_batch_ under a step gate (kf_lamb_moments_batch_gated): one
+    `hyper` dict for every segment (betas, eps, weight_decay; no step: the bias
+    corrections are the device's), the gate and group `group` of `states` as a
+    step_gate_update_ with every group's lr = 1 left them. A skipped step
+    leaves exp_avgs, exp_avg_sqs and updates untouched; otherwise g is
+    multiplied by the gate's grad_mul directly after the /np_."""
+    params, grads = list(params), list(grads)
+    ms, vs, us = list(exp_avgs), list(exp_avg_sqs), list(updates)
+    if not (len(params) == len(grads) == len(ms) == len(vs) == len(us)):
+        raise ValueError("lamb_moments_batch_gated_: one grad, exp_avg, exp_avg_sq and update "
+                         "per param segment")
+    if not params:
+        return us
+    _check_dev(params + grads + ms + vs + us)
+    _check_gate(gate, states, int(group) + 1)
+    for p, g, m, v, u in zip(params, grads, ms, vs, us):
+        if p.dtype != params[0].dtype or \
+                any(x.numel() != p.numel() or x.dtype != p.dtype for x in (g, m, v, u)):
+            raise ValueError("lamb_moments_batch_gated_: shape/dtype mismatch")
+    cnt = (ctypes.c_size_t * len(params))(*[p.numel() for p in params])
+    rc = _lib.load().kf_lamb_moments_batch_gated(
+        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (params, grads, ms, vs, us)],
+        cnt, len(params), int(kungfu_dtype(params[0])), int(np_),
+        _lib.adam_hyper_array([dict(hyper, step=1)]), gate.data_ptr(), _state_ptr(states, group),
+        _stream(stream, params[0].device))
+    _lib.check(rc, "kf_lamb_moments_batch_gated", source="")
+    return us
+
+
+def lamb_master_moments_batch_gated_(grads16, masters, exp_avgs, exp_avg_sqs, updates, hyper, gate,
+                                     states, group=0, np_=0, stream=None):
+    """lamb_master_moments_batch_ under a step gate
+    (kf_lamb_master_moments_batch_gated); hyper, gate, states and group as
+    lamb_moments_batch_gated_ takes them."""
+    grads, ws = list(grads16), list(masters)
+    ms, vs, us = list(exp_avgs), list(exp_avg_sqs), list(updates)
+    if not (len(grads) == len(ws) == len(ms) == len(vs) == len(us)):
+        raise ValueError("lamb_master_moments_batch_gated_: one master, exp_avg, exp_avg_sq and "
+                         "update per gradient segment")
+    if not grads:
+        return us
+    _check_dev(grads + ws + ms + vs + us)
+    _check_gate(gate, states, int(group) + 1)
+    if grads[0].dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("lamb_master_moments_batch_gated_: bf16 or f16 gradients")
+    for g, w, m, v, u in zip(grads, ws, ms, vs, us):
+        if g.dtype != grads[0].dtype or \
+                any(x.numel() != g.numel() or x.dtype != torch.float32 for x in (w, m, v, u)):
+            raise ValueError("lamb_master_moments_batch_gated_: shape/dtype mismatch")
+    cnt = (ctypes.c_size_t * len(grads))(*[g.numel() for g in grads])
+    rc = _lib.load().kf_lamb_master_moments_batch_gated(
+        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (grads, ws, ms, vs, us)],
+        cnt, len(grads), int(kungfu_dtype(grads[0])), int(np_),
+        _lib.adam_hyper_array([dict(hyper, step=1)]), gate.data_ptr(), _state_ptr(states, group),
+        _stream(stream, grads[0].device))
+    _lib.check(rc, "kf_lamb_master_moments_batch_gated", source="")
+    return us
+
+
+def lamb_trust_update_gated_(sq, world, group_of, groups, nlr, ratio, gate, trust_clip=0.0,
+                             stream=None):
+    """lamb_trust_update_ under a step gate (kf_lamb_trust_update_gated): a
+    skipped step leaves nlr and ratio as they were."""
+    groups = list(groups)
+    _check_dev([sq, group_of, nlr, ratio])
+    _check_gate(gate)
+    T = group_of.numel()
+    if group_of.dtype != torch.int32 or T < 1 or not groups:
+        raise ValueError("lamb_trust_update_gated_: group_of is a non-empty int32 tensor, and at "
+                         "least one group")
+    if sq.dtype != torch.float64 or sq.numel() != int(world) * 2 * T or int(world) < 1:
+        raise ValueError("lamb_trust_update_gated_: sq is world * 2 * T float64 values")
+    for t in (nlr, ratio):
+        if t.dtype != torch.float64 or t.numel() != T:
+            raise ValueError("lamb_trust_update_gated_: nlr and ratio are T float64 values")
+    garr = (_lib.LambGroup * len(groups))()
+    for a, h in zip(garr, groups):
+        a.lr, a.adapt = float(h["lr"]), int(bool(h["adapt"]))
+    rc = _lib.load().kf_lamb_trust_update_gated(
+        sq.data_ptr(), int(world), T, group_of.data_ptr(), garr, len(groups),
+        float(trust_clip or 0.0), nlr.data_ptr(), ratio.data_ptr(), gate.data_ptr(),
+        _stream(stream, sq.device))
+    _lib.check(rc, "kf_lamb_trust_update_gated", source="")
+    return nlr
+
+
 class LambApplyPlan:
     """LAMB's apply pass over "tensor ∩ own shard" pieces (kf_lamb_apply_*):
     built once over views that never move, run(nlr) is one launch whatever
@@ -608,7 +698,9 @@ class LambApplyPlan:
     master pieces and params16[i] = params[i] narrowed, round-to-nearest-even.
     Pieces are aligned to the element only; a piece's tensors must share their
     element offset from a 16-byte boundary. A piece may be empty. The plan
-    keeps the tensors alive. nlr: ntensor float64 values on the device."""
+    keeps the tensors alive. nlr: ntensor float64 values on the device.
+    run(nlr, gate=gate) is the same launch under a step gate
+    (kf_lamb_apply_run_gated): a skipped step touches nothing."""
 
     def __init__(self, params, updates, tensors, ntensor, params16=None):
         ps, us, ts = list(params), list(updates), [int(t) for t in tensors]
@@ -648,7 +740,7 @@ class LambApplyPlan:
             raise _lib.KungFuAMDError("kf_lamb_apply_create failed: %s"
                                       % lib.kf_last_error().decode())
 
-    def run(self, nlr, stream=None):
+    def run(self, nlr, stream=None, gate=None):
         if not self.npiece:
             return
         if self._plan is None:
@@ -657,6 +749,12 @@ class LambApplyPlan:
         if nlr.dtype != torch.float64 or nlr.numel() != self.ntensor or nlr.device != self.device:
             raise ValueError("LambApplyPlan.run: nlr must be %d float64 values on %s"
                              % (self.ntensor, self.device))
+        if gate is not None:
+            _check_gate(gate)
+            rc = _lib.load().kf_lamb_apply_run_gated(self._plan, nlr.data_ptr(), gate.data_ptr(),
+                                                     _stream(stream, self.device))
+            _lib.check(rc, "kf_lamb_apply_run_gated", source="")
+            return
         rc = _lib.load().kf_lamb_apply_run(self._plan, nlr.data_ptr(),
                                            _stream(stream, self.device))
         _lib.check(rc, "kf_lamb_apply_run", source="")

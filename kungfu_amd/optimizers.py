@@ -919,8 +919,8 @@ class _ShardedAdam(_Sharded):
             from . import ops
             devices = {p.device for p in self._kf_params}
             if len(devices) != 1:
-                raise ValueError("ShardedAdamOptimizer: a gated step needs all parameters on one "
-                                 "device")
+                raise ValueError("%s: a gated step needs all parameters on one device"
+                                 % self._kf_name)
             self._kf_gate = ops.new_step_gate(devices.pop(), self._kf_rule["init_scale"])
         return self._kf_gate
 
@@ -946,10 +946,11 @@ class _ShardedAdam(_Sharded):
         self._kf_sq = torch.zeros(n, dtype=torch.float64, device=gate.device)
         self._kf_sq_all = torch.zeros(n * ex.world, dtype=torch.float64, device=gate.device)
 
-    def _kf_step_gated(self):
+    def _kf_gate_verdict(self, gate_lr=None):
         """A (every group's reduce), B (the norm pass), C (the all-gather of
-        the plans' sums), D (the verdict), E (every group's gated update and
-        the parameters' all-gather): queued, nothing waits for the verdict."""
+        the plans' sums), D (the verdict): queued, nothing waits. Returns
+        every group's hyper. gate_lr: the lr the step states are advanced
+        with in place of the groups' own (LAMB: 1.0)."""
         ex, ep, groups = self._kf_ex, self._kf_gate_ops(), self._kf_groups
         for j, G in enumerate(groups):
             self._kf_states(G)
@@ -957,8 +958,8 @@ class _ShardedAdam(_Sharded):
         nps = []
         for k, (js, plan, out) in enumerate(self._kf_plans):
             if len({groups[j]["np"] for j in js}) != 1:
-                raise ValueError("ShardedAdamOptimizer: bucket groups of one dtype were reduced "
-                                 "differently")
+                raise ValueError("%s: bucket groups of one dtype were reduced differently"
+                                 % self._kf_name)
             nps.append(groups[js[0]]["np"])
             plan.run("sq", out=out)
             self._kf_sq[k:k + 1].copy_(out[-1:])
@@ -970,10 +971,18 @@ class _ShardedAdam(_Sharded):
                        "eps": float(pg["eps"]), "weight_decay": float(pg["weight_decay"]),
                        "decoupled": self._kf_decoupled})
         r = self._kf_rule
-        ep.step_gate_update_(self._kf_sq_all, ex.world, nps, hs, self._kf_gstates, self._kf_gate,
+        ghs = hs if gate_lr is None else [dict(h, lr=float(gate_lr)) for h in hs]
+        ep.step_gate_update_(self._kf_sq_all, ex.world, nps, ghs, self._kf_gstates, self._kf_gate,
                              max_norm=self._kf_max_norm, growth_factor=r["growth_factor"],
                              backoff_factor=r["backoff_factor"],
                              growth_interval=r["growth_interval"])
+        return hs
+
+    def _kf_step_gated(self):
+        """A to D (_kf_gate_verdict), E (every group's gated update and the
+        parameters' all-gather): queued, nothing waits for the verdict."""
+        ex, groups = self._kf_ex, self._kf_groups
+        hs = self._kf_gate_verdict()
         for j, (G, h) in enumerate(zip(groups, hs)):
             if G["sr"]:
                 G["draw"] += 1  # the host's count: a step the device skips draws too
@@ -986,9 +995,11 @@ class _ShardedAdam(_Sharded):
             ex.adam_gated_step_(G["pb"].buckets, G["gb"].buckets, G["w"], G["m"], G["v"], h,
                                 G["np"], self._kf_gate, self._kf_gstates, j, ("gated", j))
 
+    _kf_gate_words = "max_grad_norm or loss_scale"  # what turns the gate on
+
     def _kf_need_gate(self, what):
         if not self._kf_gated:
-            raise ValueError("ShardedAdamOptimizer.%s needs max_grad_norm or loss_scale" % what)
+            raise ValueError("%s.%s needs %s" % (self._kf_name, what, self._kf_gate_words))
 
     def scale_loss(self, loss):
         """loss * loss_scale, a device multiply by the gate's current scale:
@@ -1212,6 +1223,7 @@ class _ShardedLAMB(_ShardedAdam):
     _kf_trust_clip = 0.0
     _kf_always_adapt = False
     _kf_lamb = None  # the plans, one per (dtype, device)
+    _kf_gate_words = "gate="
 
     def _kf_new_group(self):
         return dict(super()._kf_new_group(), u=None)
@@ -1275,6 +1287,10 @@ class _ShardedLAMB(_ShardedAdam):
         ex, ep, groups = self._kf_ex, self._kf_lamb_ops(), self._kf_groups
         for G in groups:
             _SyncSGD._kf_place(G["ps"], G["gb"])
+        if self._kf_gated:
+            self._kf_step_gated()
+            _finish(ex)
+            return loss
         for j, G in enumerate(groups):
             G["np"] = ex.reduce_shards_(G["gb"].buckets, ("lamb", j))
         for j, G in enumerate(groups):
@@ -1304,9 +1320,41 @@ class _ShardedLAMB(_ShardedAdam):
         _finish(ex)
         return loss
 
+    def _kf_step_gated(self):
+        """The step under a gate (include/kungfu_amd.h "LAMB under a gate",
+        DESIGN.md §19): A to D are _ShardedAdam's with every group's lr = 1
+        for the step states, E the gated moments, F the norms of (p, u), G the
+        gated trust ratios and apply pass, H the parameters' all-gather.
+        Queued; nothing waits for the verdict."""
+        ex, ep, groups = self._kf_ex, self._kf_lamb_ops(), self._kf_groups
+        gate, states = self._kf_gate, self._kf_gstates
+        hs = self._kf_gate_verdict(gate_lr=1.0)
+        for j, (G, h) in enumerate(zip(groups, hs)):
+            wd = h["weight_decay"]
+            G["h"] = dict(h, decoupled=False, adapt=wd != 0 or self._kf_always_adapt)
+            shards = ex.grad_shards_(G["gb"].buckets, ("gated", j))
+            if G["w"] is not None:
+                ep.lamb_master_moments_gated_(shards, G["w"], G["m"], G["v"], G["u"], G["h"], gate,
+                                              states, j, G["np"])
+            else:
+                q = [b.numel() // ex.world for b in G["pb"].buckets]
+                mine = [b[ex.rank * n:(ex.rank + 1) * n] for b, n in zip(G["pb"].buckets, q)]
+                ep.lamb_moments_gated_(mine, shards, G["m"], G["v"], G["u"], G["h"], gate, states,
+                                       j, G["np"])
+        for L in self._kf_lamb:
+            L["norm"].run("sq", out=L["out"])  # unconditional: read-only
+            ex.gather_doubles_(L["out"][:2 * L["T"]], L["sq"])
+            ep.lamb_trust_update_gated_(L["sq"], ex.world, L["group_of"],
+                                        [groups[j]["h"] for j in L["js"]], L["nlr"], L["ratio"],
+                                        gate, self._kf_trust_clip)
+            L["apply"].run(L["nlr"], gate=gate)
+        for G in groups:
+            ex.gather_params_(G["pb"].buckets)
+
     def last_trust_ratios(self):
         """{parameter: the trust ratio its last step used} (1.0 before the
-        first step); synchronises with the device."""
+        first step; under a gate, the last applied step's); synchronises
+        with the device."""
         out = {}
         for L in self._kf_lamb or []:
             for p, r in zip(L["owners"], L["ratio"].cpu().tolist()):
@@ -1549,15 +1597,16 @@ _DYNAMIC_SCALE = {"init_scale": 65536.0, "growth_factor": 2.0, "backoff_factor":
                   "growth_interval": 2000}
 
 
-def _gate_rule(max_grad_norm, loss_scale):
-    """(max_norm, rule) of a gated ShardedAdamOptimizer from its two keywords,
+def _gate_rule(max_grad_norm, loss_scale, name="ShardedAdamOptimizer"):
+    """(max_norm, rule) of a gated optimizer `name` from the two settings
+    (ShardedAdamOptimizer's keywords, ShardedLAMBOptimizer's gate= entries),
     ValueError for anything else."""
     import math
     max_norm = 0.0
     if max_grad_norm is not None:
         if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or \
                 not (0 < max_grad_norm < math.inf):
-            raise ValueError("ShardedAdamOptimizer: max_grad_norm must be a positive finite "
+            raise ValueError(name + ": max_grad_norm must be a positive finite "
                              "number or None, not %r" % (max_grad_norm,))
         max_norm = float(max_grad_norm)
     static = {"init_scale": 1.0, "growth_factor": 1.0, "backoff_factor": 1.0, "growth_interval": 0}
@@ -1565,35 +1614,36 @@ def _gate_rule(max_grad_norm, loss_scale):
         return max_norm, static
     if isinstance(loss_scale, str):
         if loss_scale != "dynamic":
-            raise ValueError("ShardedAdamOptimizer: loss_scale must be None, a positive number, "
+            raise ValueError(name + ": loss_scale must be None, a positive number, "
                              "'dynamic' or a dict, not %r" % (loss_scale,))
         return max_norm, dict(_DYNAMIC_SCALE)
     if isinstance(loss_scale, dict):
         unknown = set(loss_scale) - set(_DYNAMIC_SCALE)
         if unknown:
-            raise ValueError("ShardedAdamOptimizer: loss_scale has unknown keys %s (known: %s)"
+            raise ValueError(name + ": loss_scale has unknown keys %s (known: %s)"
                              % (sorted(unknown), sorted(_DYNAMIC_SCALE)))
         rule = dict(_DYNAMIC_SCALE, **loss_scale)
         for k in ("init_scale", "growth_factor", "backoff_factor"):
             v = rule[k]
             if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0 < v < math.inf):
-                raise ValueError("ShardedAdamOptimizer: loss_scale[%r] must be a positive finite "
+                raise ValueError(name + ": loss_scale[%r] must be a positive finite "
                                  "number, not %r" % (k, v))
             rule[k] = float(v)
         n = rule["growth_interval"]
         if isinstance(n, bool) or not isinstance(n, int) or n < 0:
-            raise ValueError("ShardedAdamOptimizer: loss_scale['growth_interval'] must be an "
+            raise ValueError(name + ": loss_scale['growth_interval'] must be an "
                              "integer >= 0, not %r" % (n,))
         return max_norm, rule
     if isinstance(loss_scale, bool) or not isinstance(loss_scale, (int, float)) or \
             not (0 < loss_scale < math.inf):
-        raise ValueError("ShardedAdamOptimizer: loss_scale must be None, a positive number, "
+        raise ValueError(name + ": loss_scale must be None, a positive number, "
                          "'dynamic' or a dict, not %r" % (loss_scale,))
     return max_norm, dict(static, init_scale=float(loss_scale))
 
 
 def ShardedLAMBOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20,
-                         master_weights=False, trust_clip=None, always_adapt=False, **unsupported):
+                         master_weights=False, trust_clip=None, always_adapt=False, gate=None,
+                         **unsupported):
     """LAMB (layer-wise adaptive moments for large batches) with the update
     and its state sharded over the ranks as ShardedAdamOptimizer's are
     (DESIGN.md §17). Every step is
@@ -1610,7 +1660,8 @@ def ShardedLAMBOptimizer(optimizer, named_parameters=None, exchange=None, bucket
     spread over the ranks' shards at element offsets; the sums are added in
     rank order, so every rank computes the same ratios bit for bit. The
     arithmetic is include/kungfu_amd.h's ("LAMB"): apex FusedLAMB's
-    formulation with bias correction, without its global gradient clipping.
+    formulation with bias correction, without its global gradient clipping
+    unless gate= asks for it.
 
     `optimizer` must be a torch.optim.Adam or torch.optim.AdamW (TypeError
     otherwise); it only lends its class and its param_groups (lr, betas, eps,
@@ -1629,7 +1680,24 @@ def ShardedLAMBOptimizer(optimizer, named_parameters=None, exchange=None, bucket
         the master narrowed. Without it bf16 and f16 parameters are refused
         (TypeError on the first step): f32 and f64 only.
       * Non-finite gradients are not skipped: they reach the parameters as
-        they do in torch.optim.Adam.
+        they do in torch.optim.Adam. That is the behaviour without a gate.
+      * gate: None, or a dict with the keys "max_grad_norm" and / or
+        "loss_scale", whose values are what ShardedAdamOptimizer's keywords
+        of those names take (FusedLAMB's default is {"max_grad_norm": 1.0}; an
+        f16 model wants "loss_scale": "dynamic" too). The step then runs under
+        ShardedAdamOptimizer's device-side gate: one verdict
+        per step from the global norm of the averaged gradient, which the
+        moments pass multiplies the gradient by (clipping and unscaling), and
+        a step whose gradients are not finite is skipped: parameters, master,
+        exp_avg, exp_avg_sq, the trust ratios and the step count stay as they
+        were, and a dynamic loss scale backs off. The host never waits for the
+        verdict. scale_loss(), loss_scale_value(), last_grad_norm(),
+        skipped_steps(), applied_steps(), scaler_state() and
+        load_scaler_state() are ShardedAdamOptimizer's; without a gate they
+        raise ValueError. The bias corrections are then the device's running
+        products, and state_buffers() reports the device's step count. An
+        empty dict, an unknown key or anything that is not a dict is a
+        ValueError. All parameters must be on one device.
       * A parameter without a gradient is updated as with a zero gradient,
         and p.grad does not hold the averaged gradient after step().
 
@@ -1638,14 +1706,16 @@ def ShardedLAMBOptimizer(optimizer, named_parameters=None, exchange=None, bucket
     is scratch and is not part of it. last_trust_ratios() returns {parameter:
     float} of the last step and synchronises.
 
-    Not offered: max_grad_norm / loss_scale gating, overlap=True, the
-    hierarchical (multi-host) path, amsgrad, maximize, capturable,
-    differentiable, and any optimizer other than Adam / AdamW."""
+    Not offered: max_grad_norm= / loss_scale= as keywords (they are gate='s
+    entries), overlap=True, the hierarchical (multi-host) path, amsgrad,
+    maximize, capturable, differentiable, and any optimizer other than Adam /
+    AdamW."""
     import math
     import torch
     for k in unsupported:
         if k in ("max_grad_norm", "loss_scale"):
-            raise ValueError("ShardedLAMBOptimizer: %s (the gated step) is not offered" % k)
+            raise ValueError("ShardedLAMBOptimizer: %s is not a keyword here; the gated step "
+                             "is gate={%r: ...}" % (k, k))
         raise TypeError("ShardedLAMBOptimizer got an unexpected keyword argument %r" % k)
     if not isinstance(optimizer, (torch.optim.Adam, torch.optim.AdamW)):
         raise TypeError("ShardedLAMBOptimizer wraps a torch.optim.Adam or AdamW, not %s"
@@ -1671,4 +1741,13 @@ def ShardedLAMBOptimizer(optimizer, named_parameters=None, exchange=None, bucket
         opt._kf_master = True
         opt._kf_dtypes = ("float32", "float16", "bfloat16", "float64")
         opt._kf_dtype_words = "f32, f16, bf16 and f64"
+    if gate is not None:
+        known = ("max_grad_norm", "loss_scale")
+        if not isinstance(gate, dict) or not gate or set(gate) - set(known) or \
+                all(v is None for v in gate.values()):
+            raise ValueError("ShardedLAMBOptimizer: gate must be None or a dict with the keys "
+                             "'max_grad_norm' and / or 'loss_scale', not %r" % (gate,))
+        opt._kf_max_norm, opt._kf_rule = _gate_rule(gate.get("max_grad_norm"),
+                                                    gate.get("loss_scale"), opt._kf_name)
+        opt._kf_gated = True
     return opt

@@ -85,5 +85,6 @@ def ShardedAdamOptimizer(optimizer, named_parameters, **kwargs):
 def ShardedLAMBOptimizer(optimizer, named_parameters, **kwargs):
     """kungfu_amd.optimizers.ShardedLAMBOptimizer with `named_parameters`
     positional. Keywords pass through: `exchange`, `bucket_bytes`,
-    `master_weights`, `trust_clip` and `always_adapt`."""
+    `master_weights`, `trust_clip`, `always_adapt` and `gate` (a dict with
+    `max_grad_norm` and / or `loss_scale`: the step under the device-side gate)."""
     return _opt.ShardedLAMBOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
