@@ -402,6 +402,90 @@ int kf_adam_sr_update_batch_gated(void *const *params, const void *const *grads,
                                   void *stream);
 int kf_adam_sr_narrow(const void *x, const void *r, void *out, size_t n, void *stream);
 
+/* ---- Adam, 8-bit block-wise state ------------------------------------------
+ *
+ * exp_avg and exp_avg_sq held as one uint8 code per element and one f32 scale
+ * per block of 64 consecutive elements (Dettmers et al., "8-bit Optimizers via
+ * Block-wise Quantization"): 2.125 bytes of state per element where
+ * kf_adam_update_batch keeps 8, and 16.25 bytes of kernel traffic where it
+ * moves 28 (kungfu_amd/csrc/kf_adam8.hip).
+ *
+ * The format, for one block x[0..64) of f32 values and one of two tables T of
+ * 256 f32 values (kf_adam8_codebook: which = 0 the signed table of exp_avg,
+ * which = 1 the unsigned table of exp_avg_sq), sorted ascending, with
+ * mid[k] = (float)(((double)T[k] + (double)T[k+1]) / 2), k = 0..254:
+ *   mag = max |x_j|;  a = +mag if some x_j == +mag, else -mag;
+ *   a = NaN (0x7FC00000) if any x_j is NaN           the block's scale
+ *   y_j = a == 0 ? 0 : x_j / a                       correctly rounded
+ *   code_j = the number of k with mid[k] < y_j       (a NaN y: 0)
+ *   x_j' = T[code_j] * a                             dequantized, one multiply
+ * The element of largest magnitude has code 255 (T[255] = 1) and comes back
+ * exactly. Infinities follow from IEEE arithmetic on these formulas. A zeroed
+ * state is scale 0 with code 127 (signed) or 0 (unsigned): not all zero bytes.
+ *
+ * The tables, built in double and rounded once to f32. Decade i = 0..6 has n_i
+ * equal intervals on [0.1, 1], b_k = 0.1 + 0.9*k/n_i, and the values
+ * 10^(i-6) * (b_k + b_{k+1}) / 2. Signed: n_i = 2^i, both signs, 0 and 1 (127
+ * + 127 + 2 values; T[0] = -0.99296874, T[127] = 0, T[254] = 0.99296874).
+ * Unsigned: n_i = 2^(i+1), 0 and 1 (254 + 2 values; T[1] = 3.25e-07, T[254] =
+ * 0.9964844).
+ *
+ * The update of a block: dequantize m and v, run kf_adam_update_batch's f32
+ * arithmetic on them operation for operation (kf_adam_master_update_batch's
+ * for 16-bit parameters: the f32 update on the master, params16 = the master
+ * narrowed), the parameter from the unquantized new m and v, then quantize the
+ * new m and v. Gradients are only read. Nothing is written beyond counts[b]
+ * parameters, counts[b] code bytes and counts[b] / 64 scales per state.
+ *
+ * kf_adam8_update_batch: f32 parameters and gradients. m_codes[b] / v_codes[b]
+ * hold counts[b] bytes, m_scales[b] / v_scales[b] counts[b] / 64 floats.
+ * kf_adam8_master_update_batch: bf16 or f16 params16 (written, never read) and
+ * grads16, f32 masters. The _gated twins follow kf_adam_update_batch_gated's
+ * rules: one hyper, grad_mul, s2 and nss from the device, and a skipped step
+ * returns before any load and leaves every byte of the parameters, masters,
+ * codes and scales as it was. Checks, all before any HIP call: null tables or
+ * pointers of a non-empty segment, np < 0, bias corrections <= 0, a gate or a
+ * state missing (KF_ERR_ARG); dt other than KungFu_FLOAT, or for the master
+ * entries other than KungFu_BFLOAT16 / KungFu_FLOAT16 (KF_ERR_DTYPE);
+ * parameter, gradient, master and codes pointers 16-byte aligned, scales
+ * pointers 4-byte aligned, counts[b] a multiple of 64 (KF_ERR_ARG): there is
+ * no scalar tail. One launch per 24 segments.
+ *
+ * kf_adam8_quantize / kf_adam8_dequantize are the format alone on the device,
+ * n a multiple of 64 f32 values, for the checkpoint path and for sweeping the
+ * quantizer's domain: src / dst and codes 16-byte aligned, scales 4-byte
+ * aligned, which 0 or 1 (KF_ERR_ARG otherwise). Requantizing a dequantized
+ * block gives the same codes and scale, except where |scale| is so small that
+ * T[c] * a is subnormal. kf_adam8_codebook writes table `which` to the host
+ * array out[256] and needs no device. */
+int kf_adam8_codebook(int which, float *out);
+int kf_adam8_update_batch(void *const *params, const void *const *grads, void *const *m_codes,
+                          void *const *v_codes, void *const *m_scales, void *const *v_scales,
+                          const size_t *counts, int nb, KungFu_Datatype dt, int np,
+                          const kf_adam_hyper *hyper, void *stream);
+int kf_adam8_update_batch_gated(void *const *params, const void *const *grads,
+                                void *const *m_codes, void *const *v_codes,
+                                void *const *m_scales, void *const *v_scales,
+                                const size_t *counts, int nb, KungFu_Datatype dt, int np,
+                                const kf_adam_hyper *hyper, const kf_step_gate *gate,
+                                const kf_step_state *state, void *stream);
+int kf_adam8_master_update_batch(void *const *params16, const void *const *grads16,
+                                 void *const *masters, void *const *m_codes, void *const *v_codes,
+                                 void *const *m_scales, void *const *v_scales,
+                                 const size_t *counts, int nb, KungFu_Datatype dt, int np,
+                                 const kf_adam_hyper *hyper, void *stream);
+int kf_adam8_master_update_batch_gated(void *const *params16, const void *const *grads16,
+                                       void *const *masters, void *const *m_codes,
+                                       void *const *v_codes, void *const *m_scales,
+                                       void *const *v_scales, const size_t *counts, int nb,
+                                       KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
+                                       const kf_step_gate *gate, const kf_step_state *state,
+                                       void *stream);
+int kf_adam8_quantize(const void *src, void *codes, void *scales, size_t n, int which,
+                      void *stream);
+int kf_adam8_dequantize(const void *codes, const void *scales, void *dst, size_t n, int which,
+                        void *stream);
+
 /* ---- LAMB: layer-wise trust ratios on the sharded step --------------------
  *
  * LAMB (kungfu_amd/csrc/kf_lamb.hip) where the averaged

@@ -143,6 +143,13 @@ EXPORTED = (
     "kf_lamb_master_moments_batch_gated",
     "kf_lamb_trust_update_gated",
     "kf_lamb_apply_run_gated",
+    "kf_adam8_codebook",
+    "kf_adam8_update_batch",
+    "kf_adam8_update_batch_gated",
+    "kf_adam8_master_update_batch",
+    "kf_adam8_master_update_batch_gated",
+    "kf_adam8_quantize",
+    "kf_adam8_dequantize",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -604,6 +611,24 @@ def load():
     lib.kf_adam_sr_update_batch_gated.restype = c_int
     lib.kf_adam_sr_narrow.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.kf_adam_sr_narrow.restype = c_int
+    lib.kf_adam8_codebook.argtypes = [c_int, P(ctypes.c_float)]
+    lib.kf_adam8_codebook.restype = c_int
+    lib.kf_adam8_update_batch.argtypes = [P(c_void_p)] * 6 + [P(c_size_t), c_int, c_int, c_int,
+                                                              P(AdamHyper), c_void_p]
+    lib.kf_adam8_update_batch.restype = c_int
+    lib.kf_adam8_update_batch_gated.argtypes = [P(c_void_p)] * 6 + [
+        P(c_size_t), c_int, c_int, c_int, P(AdamHyper), c_void_p, c_void_p, c_void_p]
+    lib.kf_adam8_update_batch_gated.restype = c_int
+    lib.kf_adam8_master_update_batch.argtypes = [P(c_void_p)] * 7 + [
+        P(c_size_t), c_int, c_int, c_int, P(AdamHyper), c_void_p]
+    lib.kf_adam8_master_update_batch.restype = c_int
+    lib.kf_adam8_master_update_batch_gated.argtypes = [P(c_void_p)] * 7 + [
+        P(c_size_t), c_int, c_int, c_int, P(AdamHyper), c_void_p, c_void_p, c_void_p]
+    lib.kf_adam8_master_update_batch_gated.restype = c_int
+    lib.kf_adam8_quantize.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+    lib.kf_adam8_quantize.restype = c_int
+    lib.kf_adam8_dequantize.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+    lib.kf_adam8_dequantize.restype = c_int
     _lib = lib
     # HIP resources go back while the runtime is alive, before the C exit
     # handlers run (include/kungfu_amd.h kf_shutdown)

@@ -108,6 +108,37 @@ class HipEpilogue:
         return ops.adam_sr_update_batch_gated_(params, grads, exp_avgs, exp_avg_sqs, hyper, gate,
                                                states, bases, streams, key, group, np_)
 
+    # -- Adam with 8-bit block-wise state --
+    def adam8_update_(self, params, grads, m_codes, v_codes, m_scales, v_scales, hypers, np_):
+        """The Adam / AdamW update of f32 shards with 8-bit state
+        (ops.adam8_update_batch_), one launch."""
+        return ops.adam8_update_batch_(params, grads, m_codes, v_codes, m_scales, v_scales,
+                                       hypers, np_)
+
+    def adam8_master_update_(self, params16, grads16, masters, m_codes, v_codes, m_scales,
+                             v_scales, hypers, np_):
+        return ops.adam8_master_update_batch_(params16, grads16, masters, m_codes, v_codes,
+                                              m_scales, v_scales, hypers, np_)
+
+    def adam8_update_gated_(self, params, grads, m_codes, v_codes, m_scales, v_scales, hyper,
+                            gate, states, group, np_):
+        return ops.adam8_update_batch_gated_(params, grads, m_codes, v_codes, m_scales, v_scales,
+                                             hyper, gate, states, group, np_)
+
+    def adam8_master_update_gated_(self, params16, grads16, masters, m_codes, v_codes, m_scales,
+                                   v_scales, hyper, gate, states, group, np_):
+        return ops.adam8_master_update_batch_gated_(params16, grads16, masters, m_codes, v_codes,
+                                                    m_scales, v_scales, hyper, gate, states,
+                                                    group, np_)
+
+    def adam8_quantize_(self, x, which, codes, scales):
+        """x in table `which`'s format into (codes, scales) (ops.adam8_quantize)."""
+        return ops.adam8_quantize(x, which, codes, scales)
+
+    def adam8_dequantize(self, codes, scales, which):
+        """A new f32 tensor of (codes, scales)'s values (ops.adam8_dequantize)."""
+        return ops.adam8_dequantize(codes, scales, which)
+
     # -- LAMB (DESIGN.md §17) --
     def lamb_moments_(self, params, grads, exp_avgs, exp_avg_sqs, updates, hypers, np_):
         """LAMB's moments pass over the shards (ops.lamb_moments_batch_)."""

@@ -503,6 +503,175 @@ def adam_sr_narrow(x, r):
     return out
 
 
+# -- Adam, 8-bit block-wise state (include/kungfu_amd.h) --------
+
+ADAM8_BLOCK = 64                 # elements per quantization block
+ADAM8_ZERO_CODE = (127, 0)       # the code of 0.0: signed (exp_avg), unsigned (exp_avg_sq)
+
+
+def adam8_codebook(which):
+    """Table `which` (0: signed, exp_avg; 1: unsigned, exp_avg_sq) as a float32
+    numpy array of 256 values (kf_adam8_codebook; no device needed)."""
+    import numpy as np
+    out = (ctypes.c_float * 256)()
+    _lib.check(_lib.load().kf_adam8_codebook(int(which), out), "kf_adam8_codebook", source="")
+    return np.frombuffer(out, np.float32).copy()
+
+
+def adam8_zero_state(n, device):
+    """(exp_avg codes, exp_avg_sq codes, exp_avg scales, exp_avg_sq scales) of
+    n zeros: scale 0, code 127 and code 0. n must be a multiple of 64."""
+    if n % ADAM8_BLOCK:
+        raise ValueError("adam8_zero_state: n must be a multiple of 64")
+    return (torch.full((n,), ADAM8_ZERO_CODE[0], dtype=torch.uint8, device=device),
+            torch.full((n,), ADAM8_ZERO_CODE[1], dtype=torch.uint8, device=device),
+            torch.zeros(n // ADAM8_BLOCK, dtype=torch.float32, device=device),
+            torch.zeros(n // ADAM8_BLOCK, dtype=torch.float32, device=device))
+
+
+def _adam8_tables(name, params, grads, masters, mcs, vcs, mss, vss):
+    """The checked pointer tables and counts of the four 8-bit update entries;
+    None for no segments. masters is None for f32 parameters."""
+    lists = [params, grads] + ([masters] if masters is not None else []) + [mcs, vcs, mss, vss]
+    if not all(len(x) == len(params) for x in lists):
+        raise ValueError("%s: one grad, codes and scales tensor of each state%s per param segment"
+                         % (name, " and a master" if masters is not None else ""))
+    if not params:
+        return None
+    _check_dev([t for ts in lists for t in ts])
+    want = (torch.bfloat16, torch.float16) if masters is not None else (torch.float32,)
+    if params[0].dtype not in want:
+        raise ValueError("%s: %s parameters" % (name, " or ".join(str(d) for d in want)))
+    for i, (p, g, mc, vc, ms, vs) in enumerate(zip(params, grads, mcs, vcs, mss, vss)):
+        n = p.numel()
+        if p.dtype != params[0].dtype or g.dtype != p.dtype or g.numel() != n or \
+                any(c.dtype != torch.uint8 or c.numel() != n for c in (mc, vc)) or \
+                any(s.dtype != torch.float32 or s.numel() * ADAM8_BLOCK != n for s in (ms, vs)) or \
+                (masters is not None and (masters[i].dtype != torch.float32 or
+                                          masters[i].numel() != n)):
+            raise ValueError("%s: shape/dtype mismatch (uint8 codes of the parameters' length, "
+                             "one f32 scale per 64 elements)" % name)
+    return [_lib.ptr_array([t.data_ptr() for t in ts]) for ts in lists] + \
+        [(ctypes.c_size_t * len(params))(*[p.numel() for p in params])]
+
+
+def adam8_update_batch_(params, grads, m_codes, v_codes, m_scales, v_scales, hypers, np_=0,
+                        stream=None):
+    """The Adam / AdamW update of many flat f32 segments whose exp_avg and
+    exp_avg_sq are block-wise 8-bit codes (kf_adam8_update_batch,
+    kungfu_amd/csrc/kf_adam8.hip), one launch per 24 segments, in place on
+    params, codes and scales: dequantize, adam_update_batch_'s f32 arithmetic,
+    quantize. Every segment's length is a multiple of 64; codes are uint8 of
+    that length, scales f32 of a 64th of it. hypers[b] as adam_update_batch_
+    takes them. grads are only read."""
+    params, grads, hypers = list(params), list(grads), list(hypers)
+    if len(hypers) != len(params):
+        raise ValueError("adam8_update_batch_: one hyper per param segment")
+    t = _adam8_tables("adam8_update_batch_", params, grads, None, list(m_codes), list(v_codes),
+                      list(m_scales), list(v_scales))
+    if t is None:
+        return params
+    rc = _lib.load().kf_adam8_update_batch(
+        *t, len(params), int(kungfu_dtype(params[0])), int(np_), _lib.adam_hyper_array(hypers),
+        _stream(stream, params[0].device))
+    _lib.check(rc, "kf_adam8_update_batch", source="")
+    return params
+
+
+def adam8_update_batch_gated_(params, grads, m_codes, v_codes, m_scales, v_scales, hyper, gate,
+                              states, group=0, np_=0, stream=None):
+    """adam8_update_batch_ under a step gate (kf_adam8_update_batch_gated);
+    hyper, gate, states and group as adam_update_batch_gated_ takes them. A
+    skipped step leaves params, codes and scales untouched."""
+    params, grads = list(params), list(grads)
+    t = _adam8_tables("adam8_update_batch_gated_", params, grads, None, list(m_codes),
+                      list(v_codes), list(m_scales), list(v_scales))
+    if t is None:
+        return params
+    _check_gate(gate, states, int(group) + 1)
+    rc = _lib.load().kf_adam8_update_batch_gated(
+        *t, len(params), int(kungfu_dtype(params[0])), int(np_),
+        _lib.adam_hyper_array([dict(hyper, step=1)]), gate.data_ptr(), _state_ptr(states, group),
+        _stream(stream, params[0].device))
+    _lib.check(rc, "kf_adam8_update_batch_gated", source="")
+    return params
+
+
+def adam8_master_update_batch_(params16, grads16, masters, m_codes, v_codes, m_scales, v_scales,
+                               hypers, np_=0, stream=None):
+    """adam8_update_batch_ for bf16 or f16 parameters with an fp32 master copy
+    (kf_adam8_master_update_batch): the f32 update runs on (masters, widened
+    grads16, dequantized state) and params16 = masters narrowed,
+    round-to-nearest-even. params16 is written, never read."""
+    params, grads, hypers = list(params16), list(grads16), list(hypers)
+    if len(hypers) != len(params):
+        raise ValueError("adam8_master_update_batch_: one hyper per param segment")
+    t = _adam8_tables("adam8_master_update_batch_", params, grads, list(masters), list(m_codes),
+                      list(v_codes), list(m_scales), list(v_scales))
+    if t is None:
+        return params
+    rc = _lib.load().kf_adam8_master_update_batch(
+        *t, len(params), int(kungfu_dtype(params[0])), int(np_), _lib.adam_hyper_array(hypers),
+        _stream(stream, params[0].device))
+    _lib.check(rc, "kf_adam8_master_update_batch", source="")
+    return params
+
+
+def adam8_master_update_batch_gated_(params16, grads16, masters, m_codes, v_codes, m_scales,
+                                     v_scales, hyper, gate, states, group=0, np_=0, stream=None):
+    """adam8_master_update_batch_ under a step gate
+    (kf_adam8_master_update_batch_gated). A skipped step leaves params16,
+    masters, codes and scales untouched."""
+    params, grads = list(params16), list(grads16)
+    t = _adam8_tables("adam8_master_update_batch_gated_", params, grads, list(masters),
+                      list(m_codes), list(v_codes), list(m_scales), list(v_scales))
+    if t is None:
+        return params
+    _check_gate(gate, states, int(group) + 1)
+    rc = _lib.load().kf_adam8_master_update_batch_gated(
+        *t, len(params), int(kungfu_dtype(params[0])), int(np_),
+        _lib.adam_hyper_array([dict(hyper, step=1)]), gate.data_ptr(), _state_ptr(states, group),
+        _stream(stream, params[0].device))
+    _lib.check(rc, "kf_adam8_master_update_batch_gated", source="")
+    return params
+
+
+def adam8_quantize(x, which, codes=None, scales=None, stream=None):
+    """(codes, scales) of the flat f32 tensor x in table `which`'s format
+    (kf_adam8_quantize): uint8 codes of x's length and one f32 scale per 64
+    elements, new tensors unless given."""
+    n = x.numel()
+    if x.dtype != torch.float32 or n % ADAM8_BLOCK:
+        raise ValueError("adam8_quantize: a flat f32 tensor of a multiple of 64 elements")
+    codes = torch.empty(n, dtype=torch.uint8, device=x.device) if codes is None else codes
+    scales = torch.empty(n // ADAM8_BLOCK, dtype=torch.float32, device=x.device) \
+        if scales is None else scales
+    _check_dev([x, codes, scales])
+    if codes.dtype != torch.uint8 or codes.numel() != n or scales.dtype != torch.float32 or \
+            scales.numel() * ADAM8_BLOCK != n:
+        raise ValueError("adam8_quantize: uint8 codes of x's length, one f32 scale per 64 elements")
+    rc = _lib.load().kf_adam8_quantize(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), n,
+                                       int(which), _stream(stream, x.device))
+    _lib.check(rc, "kf_adam8_quantize", source="")
+    return codes, scales
+
+
+def adam8_dequantize(codes, scales, which, out=None, stream=None):
+    """The f32 values of (codes, scales) in table `which`'s format
+    (kf_adam8_dequantize), a new tensor unless `out` is given."""
+    n = codes.numel()
+    out = torch.empty(n, dtype=torch.float32, device=codes.device) if out is None else out
+    _check_dev([codes, scales, out])
+    if codes.dtype != torch.uint8 or n % ADAM8_BLOCK or scales.dtype != torch.float32 or \
+            scales.numel() * ADAM8_BLOCK != n or out.dtype != torch.float32 or out.numel() != n:
+        raise ValueError("adam8_dequantize: uint8 codes of a multiple of 64 elements, one f32 "
+                         "scale per 64 and an f32 result of the codes' length")
+    rc = _lib.load().kf_adam8_dequantize(codes.data_ptr(), scales.data_ptr(), out.data_ptr(), n,
+                                         int(which), _stream(stream, codes.device))
+    _lib.check(rc, "kf_adam8_dequantize", source="")
+    return out
+
+
 # -- LAMB (include/kungfu_amd.h "LAMB", DESIGN.md §17) -------------------------
 
 def lamb_moments_batch_(params, grads, exp_avgs, exp_avg_sqs, updates, hypers, np_=0, stream=None):

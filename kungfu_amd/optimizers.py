@@ -850,9 +850,11 @@ class _ShardedAdam(_Sharded):
     _kf_master = False
     _kf_sr = False      # stochastic rounding of the bf16 groups
     _kf_sr_seed = 0
+    _kf_state_bits = 32  # 8: exp_avg / exp_avg_sq as block-wise codes
 
     def _kf_new_group(self):
-        return {"m": None, "v": None, "w": None, "step": 0, "sr": False, "draw": 0}
+        return {"m": None, "v": None, "w": None, "step": 0, "sr": False, "draw": 0, "b8": False,
+                "ms": None, "vs": None}
 
     def _kf_build_sharded(self):
         import torch
@@ -869,8 +871,47 @@ class _ShardedAdam(_Sharded):
                 G["sr"] = True
                 G["streams"] = [sr_stream_word(self._kf_sr_seed, j, i)
                                 for i in range(len(G["pb"].buckets))]
+        for G in self._kf_groups if self._kf_state_bits == 8 else []:
+            G["b8"] = True  # the dtypes were checked when the optimizer was made
         if self._kf_gated:
             self._kf_build_gated()
+
+    # -- 8-bit block-wise state ---------------------------------
+    def _kf_adam8_ops(self):
+        """Where the 8-bit updates and the quantizer run: the exchange's
+        epilogue (collective.Exchange; injectable for CPU tests) or the HIP
+        one."""
+        from .collective import HipEpilogue
+        ep = getattr(self._kf_ex, "epilogue", None)
+        return ep if hasattr(ep, "adam8_update_") else HipEpilogue()
+
+    def _kf_mine(self, G):
+        """This rank's slices of the group's parameter buckets."""
+        ex = self._kf_ex
+        q = [b.numel() // ex.world for b in G["pb"].buckets]
+        return [b[ex.rank * n:(ex.rank + 1) * n] for b, n in zip(G["pb"].buckets, q)]
+
+    def _kf_adam8_update(self, G, shards, hyper, np_, gated=None):
+        """The 8-bit update of one group on this rank's shards. hyper: one per
+        bucket, or with gated = (gate, states, group) the one hyper."""
+        ep, mine = self._kf_adam8_ops(), self._kf_mine(G)
+        state = (G["m"], G["v"], G["ms"], G["vs"])
+        if gated is None:
+            if G["w"] is not None:
+                ep.adam8_master_update_(mine, shards, G["w"], *state, hyper, np_)
+            else:
+                ep.adam8_update_(mine, shards, *state, hyper, np_)
+        elif G["w"] is not None:
+            ep.adam8_master_update_gated_(mine, shards, G["w"], *state, hyper, *gated, np_)
+        else:
+            ep.adam8_update_gated_(mine, shards, *state, hyper, *gated, np_)
+
+    def _kf_adam8_f32(self, G, which):
+        """One f32 shard per bucket: the group's exp_avg (which = 0) or
+        exp_avg_sq (1) dequantized."""
+        ep = self._kf_adam8_ops()
+        codes, scales = (G["m"], G["ms"]) if which == 0 else (G["v"], G["vs"])
+        return [ep.adam8_dequantize(c, s, which) for c, s in zip(codes, scales)]
 
     # -- stochastic rounding (DESIGN.md §18) -----------------------------------
     def _kf_sr_ops(self):
@@ -891,6 +932,20 @@ class _ShardedAdam(_Sharded):
     def _kf_states(self, G):
         """The group's zeroed exp_avg / exp_avg_sq shards, allocated on the
         first step (fp32 where the group has master weights)."""
+        if G["m"] is None and G["b8"]:
+            # the zero state: scale 0, exp_avg code 127, exp_avg_sq code 0
+            from .ops import ADAM8_BLOCK, ADAM8_ZERO_CODE
+            import torch
+            G["m"] = self._kf_zero_shards(G, torch.uint8)
+            G["v"] = self._kf_zero_shards(G, torch.uint8)
+            for c in G["m"]:
+                c.fill_(ADAM8_ZERO_CODE[0])
+            for c in G["v"]:
+                c.fill_(ADAM8_ZERO_CODE[1])
+            world = self._kf_ex.world
+            for key in ("ms", "vs"):
+                G[key] = [torch.zeros(b.numel() // world // ADAM8_BLOCK, dtype=torch.float32,
+                                      device=b.device) for b in G["pb"].buckets]
         if G["m"] is None:
             import torch
             dtype = torch.float32 if G["w"] is not None else None
@@ -992,6 +1047,11 @@ class _ShardedAdam(_Sharded):
                     self._kf_gate, self._kf_gstates, j, G["np"], bases, G["streams"], key)
                 ex.gather_params_(G["pb"].buckets)
                 continue
+            if G["b8"]:
+                self._kf_adam8_update(G, ex.grad_shards_(G["gb"].buckets, ("gated", j)), h,
+                                      G["np"], (self._kf_gate, self._kf_gstates, j))
+                ex.gather_params_(G["pb"].buckets)
+                continue
             ex.adam_gated_step_(G["pb"].buckets, G["gb"].buckets, G["w"], G["m"], G["v"], h,
                                 G["np"], self._kf_gate, self._kf_gstates, j, ("gated", j))
 
@@ -1083,6 +1143,12 @@ class _ShardedAdam(_Sharded):
                     mine, ex.grad_shards_(G["gb"].buckets, ("sr", j)), ms, vs, [h] * nb, np_,
                     bases, G["streams"], key)
                 ex.gather_params_(G["pb"].buckets)
+            elif G["b8"]:
+                ex = self._kf_ex
+                np_ = ex.reduce_shards_(G["gb"].buckets, ("adam8", j))
+                self._kf_adam8_update(G, ex.grad_shards_(G["gb"].buckets, ("adam8", j)),
+                                      [h] * nb, np_)
+                ex.gather_params_(G["pb"].buckets)
             elif G["w"] is not None:
                 self._kf_ex.adam_master_step_(G["pb"].buckets, G["gb"].buckets, G["w"], ms, vs,
                                               [h] * nb)
@@ -1104,7 +1170,11 @@ class _ShardedAdam(_Sharded):
         for G, step in zip(self._kf_groups or [], self._kf_steps()):
             if G["m"] is None or step == 0:
                 continue
-            m, v = self._kf_unshard(G, G["m"]), self._kf_unshard(G, G["v"])
+            if G["b8"]:  # dequantized: a form that does not depend on world or layout
+                m = self._kf_unshard(G, self._kf_adam8_f32(G, 0))
+                v = self._kf_unshard(G, self._kf_adam8_f32(G, 1))
+            else:
+                m, v = self._kf_unshard(G, G["m"]), self._kf_unshard(G, G["v"])
             for p in m:
                 out[p] = {"step": step, "exp_avg": m[p], "exp_avg_sq": v[p]}
             if G["w"] is not None:
@@ -1139,8 +1209,21 @@ class _ShardedAdam(_Sharded):
                 raise ValueError("load_state_buffers: the parameters of one group differ in "
                                  "step: %s" % sorted(steps))
             ms, vs = self._kf_states(G)
-            self._kf_reshard(G, ms, lambda p: mapping[p]["exp_avg"] if p in mapping else None)
-            self._kf_reshard(G, vs, lambda p: mapping[p]["exp_avg_sq"] if p in mapping else None)
+            if G["b8"]:  # requantized; idempotent on what state_buffers() gave
+                import torch
+                ep = self._kf_adam8_ops()
+                for which, key, codes, scales in ((0, "exp_avg", ms, G["ms"]),
+                                                  (1, "exp_avg_sq", vs, G["vs"])):
+                    full = [torch.zeros(c.numel(), dtype=torch.float32, device=c.device)
+                            for c in codes]
+                    self._kf_reshard(G, full,
+                                     lambda p, key=key: mapping[p][key] if p in mapping else None)
+                    for x, c, s in zip(full, codes, scales):
+                        ep.adam8_quantize_(x, which, c, s)
+            else:
+                self._kf_reshard(G, ms, lambda p: mapping[p]["exp_avg"] if p in mapping else None)
+                self._kf_reshard(G, vs,
+                                 lambda p: mapping[p]["exp_avg_sq"] if p in mapping else None)
             if G["w"] is not None:
                 self._kf_reshard(G, G["w"], lambda p: mapping.get(p, {}).get("master", p.data))
             G["step"] = steps.pop()
@@ -1411,7 +1494,7 @@ def ShardedSGDOptimizer(optimizer, named_parameters=None, exchange=None, bucket_
 
 def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20,
                          master_weights=False, max_grad_norm=None, loss_scale=None,
-                         stochastic_rounding=False, sr_seed=0):
+                         stochastic_rounding=False, sr_seed=0, state_bits=32):
     """Synchronous Adam / AdamW with the optimizer update and its state
     sharded over the ranks, as ShardedSGDOptimizer does for SGD: every step is
 
@@ -1538,6 +1621,41 @@ def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket
         group and load_state_buffers() restores it (absent: draw = step), so
         a resumed run draws the bits the uninterrupted run would have drawn.
 
+    state_bits=8 (32, the default, is everything above): exp_avg
+    and exp_avg_sq are kept as block-wise 8-bit codes (Dettmers et al., "8-bit
+    Optimizers via Block-wise Quantization"): one uint8 code per element and
+    state and one f32 scale per block of 64 consecutive bucket elements and
+    state, 2.125 / world bytes per element and rank where f32 state takes 8,
+    and 16.25 bytes of kernel traffic per element where the f32 update moves
+    28. With master_weights=True a bf16 / f16 group keeps its fp32 master
+    beside them: 6.125 / world bytes where it kept 12.
+      * The update (ops.adam8_update_batch_ / ops.adam8_master_update_batch_,
+        under max_grad_norm / loss_scale their _gated twins) dequantizes a
+        block, runs the f32 arithmetic above on it bit for bit, takes the
+        parameter from the unquantized new moments and quantizes them again;
+        include/kungfu_amd.h states the format. The step follows
+        stochastic_rounding's pattern: reduce_shards_, grad_shards_, the
+        update on this rank's slices, gather_params_.
+      * Shards are 256-byte aligned, so every shard boundary is a block
+        boundary: parameters and state are identical bit for bit for any
+        world, given identical averaged gradients.
+      * Quality: a value is held to within 0.9/128 (exp_avg) or 0.9/256
+        (exp_avg_sq) of its block's largest magnitude, and an exp_avg_sq below
+        about 3e-7 of its block's largest becomes 0, where the update divides
+        by eps alone. That is the format's known weakness; it is not
+        bitsandbytes' table and makes no claim to match its results.
+      * f32 groups take the f32 kernel; bf16 and f16 groups need
+        master_weights=True; f64 groups, stochastic_rounding=True and any
+        state_bits other than 8 and 32 are refused (ValueError).
+      * state_buffers() returns the dequantized f32 exp_avg / exp_avg_sq per
+        parameter (and "master", "step"), a form that depends on neither world
+        nor layout; load_state_buffers() quantizes them again. Quantizing a
+        dequantized block gives the same codes and scale, so save -> load ->
+        continue is bit-identical to the uninterrupted run, also when the
+        world changes, as long as the buckets' layout (bucket_bytes, the
+        parameters' order) stays. A block whose scale is so small that
+        table value * scale is subnormal is outside that guarantee.
+
     state_buffers() (collective) and load_state_buffers(mapping) are the
     checkpoint path for the sharded state.
 
@@ -1589,6 +1707,24 @@ def ShardedAdamOptimizer(optimizer, named_parameters=None, exchange=None, bucket
                                  "exchange with %s() (collective.Exchange or "
                                  "exchange.NativeExchange)" % method)
         opt._kf_sr, opt._kf_sr_seed = True, sr_seed
+    if isinstance(state_bits, bool) or state_bits not in (8, 32):
+        raise ValueError("ShardedAdamOptimizer: state_bits must be 8 or 32, not %r"
+                         % (state_bits,))
+    if state_bits == 8:
+        if stochastic_rounding:
+            raise ValueError("ShardedAdamOptimizer: state_bits=8 and stochastic_rounding=True "
+                             "do not combine")
+        for p in opt._kf_params:
+            if p.dtype == torch.float64:
+                raise ValueError("ShardedAdamOptimizer: state_bits=8 takes no f64 parameters")
+            if p.dtype in (torch.bfloat16, torch.float16) and not master_weights:
+                raise ValueError("ShardedAdamOptimizer: state_bits=8 needs master_weights=True "
+                                 "for %s parameters" % str(p.dtype).replace("torch.", ""))
+        for method in ("reduce_shards_", "grad_shards_", "gather_params_"):
+            if not hasattr(opt._kf_ex, method):
+                raise ValueError("ShardedAdamOptimizer(state_bits=8) needs an exchange with "
+                                 "%s() (collective.Exchange or exchange.NativeExchange)" % method)
+        opt._kf_state_bits = 8
     return opt
 
 
@@ -1713,6 +1849,11 @@ def ShardedLAMBOptimizer(optimizer, named_parameters=None, exchange=None, bucket
     import math
     import torch
     for k in unsupported:
+        if k == "state_bits":
+            if unsupported[k] == 32 and not isinstance(unsupported[k], bool):
+                continue
+            raise ValueError("ShardedLAMBOptimizer: state_bits=%r is not supported (8-bit state "
+                             "is ShardedAdamOptimizer's)" % (unsupported[k],))
         if k in ("max_grad_norm", "loss_scale"):
             raise ValueError("ShardedLAMBOptimizer: %s is not a keyword here; the gated step "
                              "is gate={%r: ...}" % (k, k))
