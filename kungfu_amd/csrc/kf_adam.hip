@@ -247,33 +247,22 @@ int launch_adam(void *const *params, const void *const *grads, void *const *ms, 
 // Both entries: every check comes before any HIP call.
 int adam_entry(const UpdateFail &fail, void *const *params, const void *const *grads,
                void *const *exp_avgs, void *const *exp_avg_sqs, const size_t *counts, int nb,
-               KungFu_Datatype dt, int np, const kf_adam_hyper *hyper, const kf_step_gate *gate,
-               const kf_step_state *state, void *stream)
+               KungFu_Datatype dt, int np, const kf_adam_hyper *hyper, UpdateGate *g, void *stream)
 {
-    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
-    if (nb == 0) return KF_OK;
-    if (!params || !grads || !exp_avgs || !exp_avg_sqs || !counts || !hyper) {
-        return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
-    }
-    if (dt != KungFu_FLOAT && dt != KungFu_DOUBLE && dt != KungFu_BFLOAT16) {
-        return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
-                    "f32, bf16 and f64 only (eps = 1e-8 is 0 in f16: 0 / 0 where v == 0)");
-    }
-    if (np < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "np < 0");
-    for (int b = 0; b < nb; ++b) {
-        if (counts[b] == 0) continue;
-        if (!params[b] || !grads[b] || !exp_avgs[b] || !exp_avg_sqs[b]) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "null pointer in a non-empty segment");
-        }
-        if (off16(params[b]) || off16(grads[b]) || off16(exp_avgs[b]) || off16(exp_avg_sqs[b])) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "pointers must be 16-byte aligned");
-        }
-        const kf_adam_hyper &h = hyper[gate ? 0 : b];
-        if (!(h.bias_correction1 > 0) || !(h.bias_correction2 > 0)) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "bias corrections must be > 0");
-        }
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int rc = check_update_batch(
+        fail, {{params, 16, kOff16}, {grads, 16, kOff16}, {exp_avgs, 16, kOff16},
+               {exp_avg_sqs, 16, kOff16}},
+        {}, counts, nb, np, hyper, g, false,
+        [&]() -> int {
+            if (dt == KungFu_FLOAT || dt == KungFu_DOUBLE || dt == KungFu_BFLOAT16) return KF_OK;
+            return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
+                        "f32, bf16 and f64 only (eps = 1e-8 is 0 in f16: 0 / 0 where v == 0)");
+        },
+        no_check, no_check);
+    if (rc != KF_OK || nb == 0) return rc;
+    hipStream_t s              = static_cast<hipStream_t>(stream);
+    const kf_step_gate *gate   = g ? g->gate : nullptr;
+    const kf_step_state *state = g ? g->state : nullptr;
     switch (dt) {
     case KungFu_FLOAT:
         return launch_adam<float>(params, grads, exp_avgs, exp_avg_sqs, counts, nb, np, hyper, s,
@@ -296,7 +285,7 @@ int kf_adam_update_batch(void *const *params, const void *const *grads, void *co
                          KungFu_Datatype dt, int np, const kf_adam_hyper *hyper, void *stream)
 {
     return adam_entry(fail, params, grads, exp_avgs, exp_avg_sqs, counts, nb, dt, np, hyper, nullptr,
-                      nullptr, stream);
+                      stream);
 }
 
 int kf_adam_update_batch_gated(void *const *params, const void *const *grads,
@@ -305,17 +294,9 @@ int kf_adam_update_batch_gated(void *const *params, const void *const *grads,
                                const kf_adam_hyper *hyper, const kf_step_gate *gate,
                                const kf_step_state *state, void *stream)
 {
-    if (nb > 0 && (!gate || !state)) {
-        return fail_gated(KF_ERR_ARG, "KF_ERR_ARG", "null gate or step state");
-    }
-    if (nb <= 0 || !hyper) {
-        return adam_entry(fail_gated, params, grads, exp_avgs, exp_avg_sqs, counts, nb, dt, np,
-                          hyper, gate, state, stream);
-    }
-    kf_adam_hyper one    = *hyper;  // its bias corrections are the device's, not the caller's
-    one.bias_correction1 = one.bias_correction2 = 1.0;
-    return adam_entry(fail_gated, params, grads, exp_avgs, exp_avg_sqs, counts, nb, dt, np, &one,
-                      gate, state, stream);
+    UpdateGate g = {gate, state, {}};
+    return adam_entry(fail_gated, params, grads, exp_avgs, exp_avg_sqs, counts, nb, dt, np, hyper,
+                      &g, stream);
 }
 
 }  // extern "C"

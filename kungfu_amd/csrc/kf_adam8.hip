@@ -469,67 +469,39 @@ int launch_adam8(const UpdateFail &fail, const Adam8Tabs &t, const size_t *count
 
 // All four entries: every check comes before any HIP call.
 int adam8_entry(const UpdateFail &fail, bool master, const Adam8Tabs &t, const size_t *counts,
-                int nb, KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
-                const kf_step_gate *gate, const kf_step_state *state, void *stream)
+                int nb, KungFu_Datatype dt, int np, const kf_adam_hyper *hyper, UpdateGate *g,
+                void *stream)
 {
-    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
-    if (nb == 0) return KF_OK;
-    if ((master && !t.params16) || !t.grads || !t.params || !t.m_codes || !t.v_codes ||
-        !t.m_scales || !t.v_scales || !counts || !hyper) {
-        return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
-    }
-    if (master) {
-        if (dt != KungFu_BFLOAT16 && dt != KungFu_FLOAT16) {
+    constexpr const char *off4_text  = "scales pointers must be 4-byte aligned";
+    constexpr const char *off16_text =
+        "parameter, gradient and codes pointers must be 16-byte aligned";
+    const int rc = check_update_batch(
+        fail, {{t.params16, 16, off16_text, !master}, {t.grads, 16, off16_text},
+               {t.params, 16, off16_text}, {t.m_codes, 16, off16_text},
+               {t.v_codes, 16, off16_text}, {t.m_scales, 4, off4_text},
+               {t.v_scales, 4, off4_text}},
+        {}, counts, nb, np, hyper, g, false,
+        [&]() -> int {
+            const bool half = dt == KungFu_BFLOAT16 || dt == KungFu_FLOAT16;
+            if (master ? half : dt == KungFu_FLOAT) return KF_OK;
             return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
-                        "bf16 and f16 parameters only (f32 takes kf_adam8_update_batch)");
-        }
-    } else if (dt != KungFu_FLOAT) {
-        return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
-                    "f32 only (bf16 and f16 take kf_adam8_master_update_batch)");
-    }
-    if (np < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "np < 0");
-    for (int b = 0; b < nb; ++b) {
-        if (counts[b] == 0) continue;
-        if (counts[b] % kAdam8Blk) {
+                        master ? "bf16 and f16 parameters only (f32 takes kf_adam8_update_batch)"
+                               : "f32 only (bf16 and f16 take kf_adam8_master_update_batch)");
+        },
+        [&](int b) -> int {
+            if (counts[b] % kAdam8Blk == 0) return KF_OK;
             return fail(KF_ERR_ARG, "KF_ERR_ARG", "counts must be multiples of 64 (a block)");
-        }
-        if ((master && !t.params16[b]) || !t.grads[b] || !t.params[b] || !t.m_codes[b] ||
-            !t.v_codes[b] || !t.m_scales[b] || !t.v_scales[b]) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "null pointer in a non-empty segment");
-        }
-        if ((master && off16(t.params16[b])) || off16(t.grads[b]) || off16(t.params[b]) ||
-            off16(t.m_codes[b]) || off16(t.v_codes[b])) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG",
-                        "parameter, gradient and codes pointers must be 16-byte aligned");
-        }
-        if (off4(t.m_scales[b]) || off4(t.v_scales[b])) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "scales pointers must be 4-byte aligned");
-        }
-        const kf_adam_hyper &h = hyper[gate ? 0 : b];
-        if (!(h.bias_correction1 > 0) || !(h.bias_correction2 > 0)) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "bias corrections must be > 0");
-        }
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
+        },
+        no_check);
+    if (rc != KF_OK || nb == 0) return rc;
+    hipStream_t s              = static_cast<hipStream_t>(stream);
+    const kf_step_gate *gate   = g ? g->gate : nullptr;
+    const kf_step_state *state = g ? g->state : nullptr;
     if (dt == KungFu_FLOAT) return launch_adam8<float>(fail, t, counts, nb, np, hyper, s, gate, state);
     if (dt == KungFu_BFLOAT16) {
         return launch_adam8<bf16_t>(fail, t, counts, nb, np, hyper, s, gate, state);
     }
     return launch_adam8<f16_t>(fail, t, counts, nb, np, hyper, s, gate, state);
-}
-
-// the gated entries: a gate and a state, and the device's bias corrections
-int adam8_gated_entry(const UpdateFail &fail, bool master, const Adam8Tabs &t, const size_t *counts,
-                      int nb, KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
-                      const kf_step_gate *gate, const kf_step_state *state, void *stream)
-{
-    if (nb > 0 && (!gate || !state)) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null gate or step state");
-    if (nb <= 0 || !hyper) {
-        return adam8_entry(fail, master, t, counts, nb, dt, np, hyper, gate, state, stream);
-    }
-    kf_adam_hyper one    = *hyper;  // its bias corrections are the device's, not the caller's
-    one.bias_correction1 = one.bias_correction2 = 1.0;
-    return adam8_entry(fail, master, t, counts, nb, dt, np, &one, gate, state, stream);
 }
 
 int codec_entry(const UpdateFail &fail, const void *f32, const void *codes, const void *scales,
@@ -567,7 +539,7 @@ int kf_adam8_update_batch(void *const *params, const void *const *grads, void *c
                           const kf_adam_hyper *hyper, void *stream)
 {
     const Adam8Tabs t = {nullptr, grads, params, m_codes, v_codes, m_scales, v_scales};
-    return adam8_entry(fail, false, t, counts, nb, dt, np, hyper, nullptr, nullptr, stream);
+    return adam8_entry(fail, false, t, counts, nb, dt, np, hyper, nullptr, stream);
 }
 
 int kf_adam8_update_batch_gated(void *const *params, const void *const *grads,
@@ -578,7 +550,8 @@ int kf_adam8_update_batch_gated(void *const *params, const void *const *grads,
                                 const kf_step_state *state, void *stream)
 {
     const Adam8Tabs t = {nullptr, grads, params, m_codes, v_codes, m_scales, v_scales};
-    return adam8_gated_entry(fail_gated, false, t, counts, nb, dt, np, hyper, gate, state, stream);
+    UpdateGate g = {gate, state, {}};
+    return adam8_entry(fail_gated, false, t, counts, nb, dt, np, hyper, &g, stream);
 }
 
 int kf_adam8_master_update_batch(void *const *params16, const void *const *grads16,
@@ -588,7 +561,7 @@ int kf_adam8_master_update_batch(void *const *params16, const void *const *grads
                                  const kf_adam_hyper *hyper, void *stream)
 {
     const Adam8Tabs t = {params16, grads16, masters, m_codes, v_codes, m_scales, v_scales};
-    return adam8_entry(fail_master, true, t, counts, nb, dt, np, hyper, nullptr, nullptr, stream);
+    return adam8_entry(fail_master, true, t, counts, nb, dt, np, hyper, nullptr, stream);
 }
 
 int kf_adam8_master_update_batch_gated(void *const *params16, const void *const *grads16,
@@ -600,8 +573,8 @@ int kf_adam8_master_update_batch_gated(void *const *params16, const void *const 
                                        void *stream)
 {
     const Adam8Tabs t = {params16, grads16, masters, m_codes, v_codes, m_scales, v_scales};
-    return adam8_gated_entry(fail_master_gated, true, t, counts, nb, dt, np, hyper, gate, state,
-                             stream);
+    UpdateGate g = {gate, state, {}};
+    return adam8_entry(fail_master_gated, true, t, counts, nb, dt, np, hyper, &g, stream);
 }
 
 int kf_adam8_quantize(const void *src, void *codes, void *scales, size_t n, int which,

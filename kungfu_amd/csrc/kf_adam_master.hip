@@ -303,34 +303,22 @@ int launch_master(void *const *params16, const void *const *grads16, void *const
 int master_entry(const UpdateFail &fail, void *const *params16, const void *const *grads16,
                  void *const *masters, void *const *exp_avgs, void *const *exp_avg_sqs,
                  const size_t *counts, int nb, KungFu_Datatype dt, int np,
-                 const kf_adam_hyper *hyper, const kf_step_gate *gate, const kf_step_state *state,
-                 void *stream)
+                 const kf_adam_hyper *hyper, UpdateGate *g, void *stream)
 {
-    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
-    if (nb == 0) return KF_OK;
-    if (!params16 || !grads16 || !masters || !exp_avgs || !exp_avg_sqs || !counts || !hyper) {
-        return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
-    }
-    if (dt != KungFu_BFLOAT16 && dt != KungFu_FLOAT16) {
-        return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
-                    "bf16 and f16 parameters only (f32 and f64 take kf_adam_update_batch)");
-    }
-    if (np < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "np < 0");
-    for (int b = 0; b < nb; ++b) {
-        if (counts[b] == 0) continue;
-        if (!params16[b] || !grads16[b] || !masters[b] || !exp_avgs[b] || !exp_avg_sqs[b]) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "null pointer in a non-empty segment");
-        }
-        if (off16(params16[b]) || off16(grads16[b]) || off16(masters[b]) || off16(exp_avgs[b]) ||
-            off16(exp_avg_sqs[b])) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "pointers must be 16-byte aligned");
-        }
-        const kf_adam_hyper &h = hyper[gate ? 0 : b];
-        if (!(h.bias_correction1 > 0) || !(h.bias_correction2 > 0)) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "bias corrections must be > 0");
-        }
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int rc = check_update_batch(
+        fail, {{params16, 16, kOff16}, {grads16, 16, kOff16}, {masters, 16, kOff16},
+               {exp_avgs, 16, kOff16}, {exp_avg_sqs, 16, kOff16}},
+        {}, counts, nb, np, hyper, g, false,
+        [&]() -> int {
+            if (dt == KungFu_BFLOAT16 || dt == KungFu_FLOAT16) return KF_OK;
+            return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
+                        "bf16 and f16 parameters only (f32 and f64 take kf_adam_update_batch)");
+        },
+        no_check, no_check);
+    if (rc != KF_OK || nb == 0) return rc;
+    hipStream_t s              = static_cast<hipStream_t>(stream);
+    const kf_step_gate *gate   = g ? g->gate : nullptr;
+    const kf_step_state *state = g ? g->state : nullptr;
     if (dt == KungFu_BFLOAT16) {
         return launch_master<bf16_t>(params16, grads16, masters, exp_avgs, exp_avg_sqs, counts, nb,
                                      np, hyper, s, gate, state);
@@ -350,7 +338,7 @@ int kf_adam_master_update_batch(void *const *params16, const void *const *grads1
                                 void *stream)
 {
     return master_entry(fail, params16, grads16, masters, exp_avgs, exp_avg_sqs, counts, nb, dt, np,
-                        hyper, nullptr, nullptr, stream);
+                        hyper, nullptr, stream);
 }
 
 int kf_adam_master_update_batch_gated(void *const *params16, const void *const *grads16,
@@ -360,17 +348,9 @@ int kf_adam_master_update_batch_gated(void *const *params16, const void *const *
                                       const kf_step_gate *gate, const kf_step_state *state,
                                       void *stream)
 {
-    if (nb > 0 && (!gate || !state)) {
-        return fail_gated(KF_ERR_ARG, "KF_ERR_ARG", "null gate or step state");
-    }
-    if (nb <= 0 || !hyper) {
-        return master_entry(fail_gated, params16, grads16, masters, exp_avgs, exp_avg_sqs, counts,
-                            nb, dt, np, hyper, gate, state, stream);
-    }
-    kf_adam_hyper one    = *hyper;  // its bias corrections are the device's, not the caller's
-    one.bias_correction1 = one.bias_correction2 = 1.0;
+    UpdateGate g = {gate, state, {}};
     return master_entry(fail_gated, params16, grads16, masters, exp_avgs, exp_avg_sqs, counts, nb,
-                        dt, np, &one, gate, state, stream);
+                        dt, np, hyper, &g, stream);
 }
 
 }  // extern "C"

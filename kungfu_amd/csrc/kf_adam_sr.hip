@@ -328,41 +328,31 @@ int launch_adam_sr(void *const *params, const void *const *grads, void *const *m
 int adam_sr_entry(const UpdateFail &fail, void *const *params, const void *const *grads,
                   void *const *exp_avgs, void *const *exp_avg_sqs, const size_t *counts,
                   const uint64_t *bases, const uint32_t *streams, int nb, KungFu_Datatype dt,
-                  int np, const kf_adam_hyper *hyper, uint32_t key, const kf_step_gate *gate,
-                  const kf_step_state *state, void *stream)
+                  int np, const kf_adam_hyper *hyper, uint32_t key, UpdateGate *g, void *stream)
 {
-    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
-    if (nb == 0) return KF_OK;
-    if (!params || !grads || !exp_avgs || !exp_avg_sqs || !counts || !bases || !streams ||
-        !hyper) {
-        return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
-    }
-    if (dt != KungFu_BFLOAT16) {
-        return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
-                    "bf16 only (f32 and f64 take kf_adam_update_batch; f16 the master path)");
-    }
-    if (np < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "np < 0");
-    for (int b = 0; b < nb; ++b) {
-        if (counts[b] == 0) continue;
-        if (!params[b] || !grads[b] || !exp_avgs[b] || !exp_avg_sqs[b]) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "null pointer in a non-empty segment");
-        }
-        if (off16(params[b]) || off16(grads[b]) || off16(exp_avgs[b]) || off16(exp_avg_sqs[b])) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "pointers must be 16-byte aligned");
-        }
-        const kf_adam_hyper &h = hyper[gate ? 0 : b];
-        if (!(h.bias_correction1 > 0) || !(h.bias_correction2 > 0)) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "bias corrections must be > 0");
-        }
-        if (bases[b] % kAdamSrElts != 0) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "bases must be multiples of 8 elements");
-        }
-        if (bases[b] > kMaxElement || counts[b] > kMaxElement - bases[b]) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "base + count must be at most 2^33");
-        }
-    }
+    const int rc = check_update_batch(
+        fail, {{params, 16, kOff16}, {grads, 16, kOff16}, {exp_avgs, 16, kOff16},
+               {exp_avg_sqs, 16, kOff16}},
+        {bases, streams}, counts, nb, np, hyper, g, false,
+        [&]() -> int {
+            if (dt == KungFu_BFLOAT16) return KF_OK;
+            return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
+                        "bf16 only (f32 and f64 take kf_adam_update_batch; f16 the master path)");
+        },
+        no_check,
+        [&](int b) -> int {
+            if (bases[b] % kAdamSrElts != 0) {
+                return fail(KF_ERR_ARG, "KF_ERR_ARG", "bases must be multiples of 8 elements");
+            }
+            if (bases[b] > kMaxElement || counts[b] > kMaxElement - bases[b]) {
+                return fail(KF_ERR_ARG, "KF_ERR_ARG", "base + count must be at most 2^33");
+            }
+            return KF_OK;
+        });
+    if (rc != KF_OK || nb == 0) return rc;
     return launch_adam_sr(params, grads, exp_avgs, exp_avg_sqs, counts, bases, streams, nb, np,
-                          hyper, key, static_cast<hipStream_t>(stream), gate, state);
+                          hyper, key, static_cast<hipStream_t>(stream), g ? g->gate : nullptr,
+                          g ? g->state : nullptr);
 }
 
 }  // namespace
@@ -375,7 +365,7 @@ int kf_adam_sr_update_batch(void *const *params, const void *const *grads, void 
                             const kf_adam_hyper *hyper, uint32_t key, void *stream)
 {
     return adam_sr_entry(fail, params, grads, exp_avgs, exp_avg_sqs, counts, bases, streams, nb, dt,
-                         np, hyper, key, nullptr, nullptr, stream);
+                         np, hyper, key, nullptr, stream);
 }
 
 int kf_adam_sr_update_batch_gated(void *const *params, const void *const *grads,
@@ -386,17 +376,9 @@ int kf_adam_sr_update_batch_gated(void *const *params, const void *const *grads,
                                   const kf_step_gate *gate, const kf_step_state *state,
                                   void *stream)
 {
-    if (nb > 0 && (!gate || !state)) {
-        return fail_gated(KF_ERR_ARG, "KF_ERR_ARG", "null gate or step state");
-    }
-    if (nb <= 0 || !hyper) {
-        return adam_sr_entry(fail_gated, params, grads, exp_avgs, exp_avg_sqs, counts, bases,
-                             streams, nb, dt, np, hyper, key, gate, state, stream);
-    }
-    kf_adam_hyper one    = *hyper;  // its bias corrections are the device's, not the caller's
-    one.bias_correction1 = one.bias_correction2 = 1.0;
+    UpdateGate g = {gate, state, {}};
     return adam_sr_entry(fail_gated, params, grads, exp_avgs, exp_avg_sqs, counts, bases, streams,
-                         nb, dt, np, &one, key, gate, state, stream);
+                         nb, dt, np, hyper, key, &g, stream);
 }
 
 int kf_adam_sr_narrow(const void *x, const void *r, void *out, size_t n, void *stream)

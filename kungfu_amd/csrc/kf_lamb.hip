@@ -557,29 +557,18 @@ int launch_moments(const void *const *ps, const void *const *gs, void *const *ms
         launch);
 }
 
-// Both moments entries: every check comes before any HIP call.
+// All four moments entries: every check comes before any HIP call, the dtype
+// before the tables. bad_dtype: the refusal's text, or nullptr where dt is fine.
 int moments_checks(const UpdateFail &fail, const void *const *ps, const void *const *gs,
                    void *const *ms, void *const *vs, void *const *us, const size_t *counts, int nb,
-                   int np, const kf_adam_hyper *hyper, bool one = false)
+                   int np, const kf_adam_hyper *&hyper, UpdateGate *g, const char *bad_dtype)
 {
-    if (!ps || !gs || !ms || !vs || !us || !counts || !hyper) {
-        return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
-    }
-    if (np < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "np < 0");
-    for (int b = 0; b < nb; ++b) {
-        if (counts[b] == 0) continue;
-        if (!ps[b] || !gs[b] || !ms[b] || !vs[b] || !us[b]) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "null pointer in a non-empty segment");
-        }
-        if (off16(ps[b]) || off16(gs[b]) || off16(ms[b]) || off16(vs[b]) || off16(us[b])) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "pointers must be 16-byte aligned");
-        }
-        const kf_adam_hyper &h = hyper[one ? 0 : b];
-        if (!(h.bias_correction1 > 0) || !(h.bias_correction2 > 0)) {
-            return fail(KF_ERR_ARG, "KF_ERR_ARG", "bias corrections must be > 0");
-        }
-    }
-    return KF_OK;
+    return check_update_batch(
+        fail, {{ps, 16, kOff16}, {gs, 16, kOff16}, {ms, 16, kOff16}, {vs, 16, kOff16},
+               {us, 16, kOff16}},
+        {}, counts, nb, np, hyper, g, true,
+        [&]() -> int { return bad_dtype ? fail(KF_ERR_DTYPE, "KF_ERR_DTYPE", bad_dtype) : KF_OK; },
+        no_check, no_check);
 }
 
 // gate == nullptr: the parent kernel
@@ -656,14 +645,6 @@ int apply_entry(const UpdateFail &fail, kf_lamb_apply *p, const double *nlr,
     return launch_status(fail);
 }
 
-// The bias corrections of a gated call's one hyper are the device's.
-kf_adam_hyper gated_hyper(const kf_adam_hyper *hyper)
-{
-    kf_adam_hyper one    = *hyper;
-    one.bias_correction1 = one.bias_correction2 = 1.0;
-    return one;
-}
-
 }  // namespace
 
 extern "C" {
@@ -674,15 +655,11 @@ int kf_lamb_moments_batch(const void *const *params, const void *const *grads,
                           const kf_adam_hyper *hyper, void *stream)
 {
     const UpdateFail &fail = fail_moments;
-    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
-    if (nb == 0) return KF_OK;
-    if (dt != KungFu_FLOAT && dt != KungFu_DOUBLE) {
-        return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
-                    "f32 and f64 only (bf16 and f16 take kf_lamb_master_moments_batch)");
-    }
-    const int rc = moments_checks(fail, params, grads, exp_avgs, exp_avg_sqs, updates, counts, nb,
-                                  np, hyper);
-    if (rc != KF_OK) return rc;
+    const int rc = moments_checks(
+        fail, params, grads, exp_avgs, exp_avg_sqs, updates, counts, nb, np, hyper, nullptr,
+        dt == KungFu_FLOAT || dt == KungFu_DOUBLE ? nullptr
+        : "f32 and f64 only (bf16 and f16 take kf_lamb_master_moments_batch)");
+    if (rc != KF_OK || nb == 0) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Div dv  = update_div(np);
     const int div = update_div_code(np, dv);
@@ -709,15 +686,11 @@ int kf_lamb_master_moments_batch(const void *const *grads16, const void *const *
                                  void *stream)
 {
     const UpdateFail &fail = fail_master;
-    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
-    if (nb == 0) return KF_OK;
-    if (dt != KungFu_BFLOAT16 && dt != KungFu_FLOAT16) {
-        return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
-                    "bf16 and f16 gradients only (f32 and f64 take kf_lamb_moments_batch)");
-    }
-    const int rc = moments_checks(fail, masters, grads16, exp_avgs, exp_avg_sqs, updates, counts, nb,
-                                  np, hyper);
-    if (rc != KF_OK) return rc;
+    const int rc = moments_checks(
+        fail, masters, grads16, exp_avgs, exp_avg_sqs, updates, counts, nb, np, hyper, nullptr,
+        dt == KungFu_BFLOAT16 || dt == KungFu_FLOAT16 ? nullptr
+        : "bf16 and f16 gradients only (f32 and f64 take kf_lamb_moments_batch)");
+    if (rc != KF_OK || nb == 0) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Div dv  = update_div(np);
     const int div = update_div_code(np, dv);
@@ -757,24 +730,18 @@ int kf_lamb_moments_batch_gated(const void *const *params, const void *const *gr
                                 const kf_step_gate *gate, const kf_step_state *state, void *stream)
 {
     const UpdateFail &fail = fail_moments_gated;
-    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
-    if (nb == 0) return KF_OK;
-    if (!gate || !state) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null gate or step state");
-    if (dt != KungFu_FLOAT && dt != KungFu_DOUBLE) {
-        return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
-                    "f32 and f64 only (bf16 and f16 take kf_lamb_master_moments_batch_gated)");
-    }
-    if (!hyper) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
-    const kf_adam_hyper one = gated_hyper(hyper);
-    const int rc = moments_checks(fail, params, grads, exp_avgs, exp_avg_sqs, updates, counts, nb,
-                                  np, &one, true);
-    if (rc != KF_OK) return rc;
+    UpdateGate g = {gate, state, {}};
+    const int rc = moments_checks(
+        fail, params, grads, exp_avgs, exp_avg_sqs, updates, counts, nb, np, hyper, &g,
+        dt == KungFu_FLOAT || dt == KungFu_DOUBLE ? nullptr
+        : "f32 and f64 only (bf16 and f16 take kf_lamb_master_moments_batch_gated)");
+    if (rc != KF_OK || nb == 0) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Div dv  = update_div(np);
     const int div = update_div_code(np, dv);
     if (dt == KungFu_FLOAT) {
         return launch_moments<float, kLambSeg>(
-            params, grads, exp_avgs, exp_avg_sqs, updates, counts, nb, &one,
+            params, grads, exp_avgs, exp_avg_sqs, updates, counts, nb, hyper,
             [&](unsigned gx, unsigned gy, const LambArgs<float, kLambSeg> &a) {
                 lamb_moments_gated_kernel<float>
                     <<<dim3(gx, gy), kLambBlock, 0, s>>>(a, dv, div, gate, state);
@@ -783,7 +750,7 @@ int kf_lamb_moments_batch_gated(const void *const *params, const void *const *gr
             true);
     }
     return launch_moments<double, kLambSeg>(
-        params, grads, exp_avgs, exp_avg_sqs, updates, counts, nb, &one,
+        params, grads, exp_avgs, exp_avg_sqs, updates, counts, nb, hyper,
         [&](unsigned gx, unsigned gy, const LambArgs<double, kLambSeg> &a) {
             lamb_moments_gated_kernel<double>
                 <<<dim3(gx, gy), kLambBlock, 0, s>>>(a, dv, div, gate, state);
@@ -800,18 +767,12 @@ int kf_lamb_master_moments_batch_gated(const void *const *grads16, const void *c
                                        void *stream)
 {
     const UpdateFail &fail = fail_master_gated;
-    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
-    if (nb == 0) return KF_OK;
-    if (!gate || !state) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null gate or step state");
-    if (dt != KungFu_BFLOAT16 && dt != KungFu_FLOAT16) {
-        return fail(KF_ERR_DTYPE, "KF_ERR_DTYPE",
-                    "bf16 and f16 gradients only (f32 and f64 take kf_lamb_moments_batch_gated)");
-    }
-    if (!hyper) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
-    const kf_adam_hyper one = gated_hyper(hyper);
-    const int rc = moments_checks(fail, masters, grads16, exp_avgs, exp_avg_sqs, updates, counts, nb,
-                                  np, &one, true);
-    if (rc != KF_OK) return rc;
+    UpdateGate g = {gate, state, {}};
+    const int rc = moments_checks(
+        fail, masters, grads16, exp_avgs, exp_avg_sqs, updates, counts, nb, np, hyper, &g,
+        dt == KungFu_BFLOAT16 || dt == KungFu_FLOAT16 ? nullptr
+        : "bf16 and f16 gradients only (f32 and f64 take kf_lamb_moments_batch_gated)");
+    if (rc != KF_OK || nb == 0) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Div dv  = update_div(np);
     const int div = update_div_code(np, dv);
@@ -826,7 +787,7 @@ int kf_lamb_master_moments_batch_gated(const void *const *grads16, const void *c
         return launch_status(fail);
     };
     return launch_moments<float, kLambMasterSeg>(masters, grads16, exp_avgs, exp_avg_sqs, updates,
-                                                 counts, nb, &one, launch, true);
+                                                 counts, nb, hyper, launch, true);
 }
 
 kf_lamb_apply_t *kf_lamb_apply_create(void *const *params, const void *const *updates,

@@ -1,9 +1,10 @@
 // kf_update_batch.hpp — the launch machinery the batched optimizer-update
-// kernels share (kf_sgd.hip, kf_adam.hip, kf_adam_master.hip): the host's
-// launch planner, the device's segment lookup and /np dispatch, and the entry
-// points' small validation helpers. The arithmetic is shared in
-// kf_sgd_elt.hpp and kf_adam_math.hpp; the tile loops are each kernel's own
-// (DESIGN.md §13).
+// kernels share (kf_sgd.hip, kf_adam.hip, kf_adam_master.hip, kf_adam_sr.hip,
+// kf_adam8.hip, kf_lamb.hip; kf_step_gate.hip takes the failure reporter): the
+// host's launch planner, the device's segment lookup and /np dispatch, and the
+// entry points' validation ladder. The arithmetic is shared in kf_sgd_elt.hpp,
+// kf_adam_math.hpp and kf_lamb_math.hpp; the tile loops are each kernel's own
+// (DESIGN.md §13, §21).
 //
 // A kernarg struct ARGS has `seg[NSEG]` (one entry per segment, the kernel's
 // own type), `unsigned blk0[NSEG + 1]` and `int nseg`. Segments of about equal
@@ -14,6 +15,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 #include <string>
 #include <type_traits>
 
@@ -35,6 +37,98 @@ struct UpdateFail {
 };
 
 inline bool off16(const void *p) { return (reinterpret_cast<uintptr_t>(p) % 16) != 0; }
+
+// One pointer table of an Adam-family update call: a pointer per segment, what
+// a non-empty segment's pointer must be a multiple of (a power of two), and the
+// refusal's text where it is not. ptr == nullptr with `absent`: the entry has
+// no such table.
+struct UpdateTab {
+    const void *const *ptr;
+    unsigned align;
+    const char *misaligned;
+    bool absent = false;
+};
+constexpr const char *kOff16 = "pointers must be 16-byte aligned";
+
+// A gated call's gate and step state, and, once the checks have run, its one
+// hyper: the caller's with both bias corrections 1 (they are the device's).
+struct UpdateGate {
+    const kf_step_gate *gate;
+    const kf_step_state *state;
+    kf_adam_hyper one;
+};
+
+inline int no_check(int) { return KF_OK; }
+
+// The checks every Adam-family entry makes before its first HIP call, in the
+// one order they all keep: nb < 0, nb == 0 (KF_OK: the caller returns on
+// nb == 0 too), a gated call's gate and state, the tables (`also`: further
+// arrays of the entry's own that must not be null), np, and per non-empty
+// segment first(b), null pointers, alignment in table order, the bias
+// corrections, last(b). dtype() is the entry's own check with its own
+// text; it comes after the tables' check, or before it with dtype_first
+// (LAMB). Afterwards `hyper` is what the kernels take: with a gate, g->one for
+// every segment, else hyper[b].
+template <size_t N, typename DTYPE, typename FIRST, typename LAST>
+int check_update_batch(const UpdateFail &fail, const UpdateTab (&tabs)[N],
+                       std::initializer_list<const void *> also, const size_t *counts, int nb,
+                       int np, const kf_adam_hyper *&hyper, UpdateGate *g, bool dtype_first,
+                       DTYPE &&dtype, FIRST &&first, LAST &&last)
+{
+    if (nb < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "nb < 0");
+    if (nb == 0) return KF_OK;
+    if (g && (!g->gate || !g->state)) {
+        return fail(KF_ERR_ARG, "KF_ERR_ARG", "null gate or step state");
+    }
+    int rc = dtype_first ? dtype() : KF_OK;
+    if (rc != KF_OK) return rc;
+    // the tables that are there, once: the segment loop does not look at `absent`
+    const void *const *ptr[N];
+    uintptr_t mask[N];
+    size_t n   = 0;
+    bool null = !counts || !hyper;
+    for (const UpdateTab &t : tabs) {
+        null = null || (!t.absent && !t.ptr);
+        if (!t.ptr) continue;
+        ptr[n]    = t.ptr;
+        mask[n++] = t.align - 1;
+    }
+    for (const void *p : also) null = null || !p;
+    if (null) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
+    rc = dtype_first ? KF_OK : dtype();
+    if (rc != KF_OK) return rc;
+    if (np < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "np < 0");
+    if (g) {
+        g->one                  = *hyper;
+        g->one.bias_correction1 = g->one.bias_correction2 = 1.0;
+        hyper                   = &g->one;
+    }
+    for (int b = 0; b < nb; ++b) {
+        if (counts[b] == 0) continue;
+        if ((rc = first(b)) != KF_OK) return rc;
+        bool none     = false;  // one pass: a null pointer, and the pointers' stray low bits
+        uintptr_t off = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const uintptr_t p = reinterpret_cast<uintptr_t>(ptr[i][b]);
+            none              = none || p == 0;
+            off |= p & mask[i];
+        }
+        if (none) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null pointer in a non-empty segment");
+        if (off != 0) {  // the first misaligned table's text, in table order
+            for (const UpdateTab &t : tabs) {
+                if (t.ptr && (reinterpret_cast<uintptr_t>(t.ptr[b]) & (t.align - 1)) != 0) {
+                    return fail(KF_ERR_ARG, "KF_ERR_ARG", t.misaligned);
+                }
+            }
+        }
+        const kf_adam_hyper &h = hyper[g ? 0 : b];
+        if (!(h.bias_correction1 > 0) || !(h.bias_correction2 > 0)) {
+            return fail(KF_ERR_ARG, "KF_ERR_ARG", "bias corrections must be > 0");
+        }
+        if ((rc = last(b)) != KF_OK) return rc;
+    }
+    return KF_OK;
+}
 
 // The launches of one update call over counts[0..nb): every non-empty segment
 // takes the next entry of an ARGS, filled by fill(a.seg[i], b), and

@@ -214,6 +214,142 @@ def sgd_update_batch_(params, grads, moms, hypers, np_=0, stream=None):
     return params
 
 
+# -- the batched Adam-family updates: one implementation -------
+
+ADAM8_BLOCK = 64                 # elements per quantization block
+_HALF = (torch.bfloat16, torch.float16)
+
+
+# What a table's tensor must be beside the lead tensor p of its segment: (its
+# dtype, None for p's; how many of p's elements one of its elements stands for).
+_same, _f32, _u8 = (None, 1), (torch.float32, 1), (torch.uint8, 1)
+_scale = (torch.float32, ADAM8_BLOCK)
+
+
+class _Update:
+    """One wrapper's row: its name, the C entry (`fn` once it has been looked
+    up), the rules of the tables after the lead one, and its refusals' words."""
+
+    def __init__(self, name, rules, words, mismatch="shape/dtype mismatch", lead=None,
+                 lead_words=None, ret=0, hypers_first=False, gate_last=False):
+        self.name, self.entry, self.fn = name, "kf_" + name.rstrip("_"), None
+        self.rules, self.words, self.mismatch = rules, words, mismatch
+        self.lead, self.lead_words = lead, lead_words  # None: the dtype is the C entry's check
+        self.ret = ret                                 # the table the wrapper returns
+        self.hypers_first = hypers_first               # the hypers are counted on their own, first
+        self.gate_last = gate_last                     # the gate is looked at after the tables
+
+
+_ADAM8 = (_same, _u8, _u8, _scale, _scale)
+_ADAM8_MASTER = (_same, _f32, _u8, _u8, _scale, _scale)
+_MISMATCH_SR = "bf16 tensors of one shape per segment"
+_MISMATCH_8 = ("shape/dtype mismatch (uint8 codes of the parameters' length, one f32 scale per 64 "
+               "elements)")
+_WORDS_SR = "one grad, exp_avg, exp_avg_sq, base and stream word per param segment"
+_WORDS_8 = "one grad, codes and scales tensor of each state per param segment"
+_WORDS_8_MASTER = "one grad, codes and scales tensor of each state and a master per param segment"
+# One row per wrapper, bound once: _<wrapper> is the row of <wrapper>_.
+_adam_update_batch = _Update("adam_update_batch_", (_same,) * 3,
+    "one grad, exp_avg, exp_avg_sq and hyper per param segment")
+_adam_update_batch_gated = _Update("adam_update_batch_gated_", (_same,) * 3,
+    "one grad, exp_avg and exp_avg_sq per param segment")
+_adam_master_update_batch = _Update("adam_master_update_batch_", (_same, _f32, _f32, _f32),
+    "one grad, master, exp_avg, exp_avg_sq and hyper per param segment",
+    lead=_HALF, lead_words="bf16 or f16 parameters")
+_adam_master_update_batch_gated = _Update(
+    "adam_master_update_batch_gated_", (_same, _f32, _f32, _f32),
+    "one grad, master, exp_avg and exp_avg_sq per param segment",
+    lead=_HALF, lead_words="bf16 or f16 parameters")
+_adam_sr_update_batch = _Update("adam_sr_update_batch_", (_same,) * 3, _WORDS_SR, _MISMATCH_SR,
+    lead=(torch.bfloat16,), lead_words=_MISMATCH_SR, hypers_first=True)
+_adam_sr_update_batch_gated = _Update(
+    "adam_sr_update_batch_gated_", (_same,) * 3, _WORDS_SR, _MISMATCH_SR,
+    lead=(torch.bfloat16,), lead_words=_MISMATCH_SR, gate_last=True)
+_adam8_update_batch = _Update("adam8_update_batch_", _ADAM8, _WORDS_8, _MISMATCH_8,
+    lead=(torch.float32,), lead_words="torch.float32 parameters", hypers_first=True)
+_adam8_update_batch_gated = _Update("adam8_update_batch_gated_", _ADAM8, _WORDS_8, _MISMATCH_8,
+    lead=(torch.float32,), lead_words="torch.float32 parameters", gate_last=True)
+_adam8_master_update_batch = _Update(
+    "adam8_master_update_batch_", _ADAM8_MASTER, _WORDS_8_MASTER, _MISMATCH_8,
+    lead=_HALF, lead_words="torch.bfloat16 or torch.float16 parameters", hypers_first=True)
+_adam8_master_update_batch_gated = _Update(
+    "adam8_master_update_batch_gated_", _ADAM8_MASTER, _WORDS_8_MASTER, _MISMATCH_8,
+    lead=_HALF, lead_words="torch.bfloat16 or torch.float16 parameters", gate_last=True)
+_lamb_moments_batch = _Update("lamb_moments_batch_", (_same,) * 4,
+    "one grad, exp_avg, exp_avg_sq, update and hyper per param segment", ret=4)
+_lamb_moments_batch_gated = _Update("lamb_moments_batch_gated_", (_same,) * 4,
+    "one grad, exp_avg, exp_avg_sq and update per param segment", ret=4)
+_lamb_master_moments_batch = _Update("lamb_master_moments_batch_", (_f32,) * 4,
+    "one master, exp_avg, exp_avg_sq, update and hyper per gradient segment",
+    lead=_HALF, lead_words="bf16 or f16 gradients", ret=4)
+_lamb_master_moments_batch_gated = _Update("lamb_master_moments_batch_gated_", (_f32,) * 4,
+    "one master, exp_avg, exp_avg_sq and update per gradient segment",
+    lead=_HALF, lead_words="bf16 or f16 gradients", ret=4)
+
+
+def _update_batch(row, tables, hyper, gated, np_, stream, sr=None):
+    """The body of every wrapper that has an _Update row. tables: the tensor tables, the
+    lead one first; hyper: one dict per segment, or with gated = (gate, states,
+    group) the one dict; sr: (bases, streams, key). Checks, then the C call."""
+    name = row.name
+    tables = [list(t) for t in tables]
+    lead = tables[0]
+    nb = len(lead)
+    fits = True
+    for t in tables:
+        fits = fits and len(t) == nb
+    if gated is None:
+        hyper = list(hyper)
+        if len(hyper) != nb:
+            if row.hypers_first:
+                raise ValueError("%s: one hyper per param segment" % name)
+            fits = False
+    if sr is not None:
+        bases, streams = [int(b) for b in sr[0]], [int(x) for x in sr[1]]
+        fits = fits and len(bases) == nb == len(streams)
+    if not fits:
+        raise ValueError("%s: %s" % (name, row.words))
+    if sr is not None:
+        key = int(sr[2])
+        if not 0 <= key < 1 << 32 or any(not 0 <= x < 1 << 32 for x in streams) or \
+                any(not 0 <= b < 1 << 64 for b in bases):
+            raise ValueError("%s: key and stream words are 32-bit, bases 64-bit unsigned" % name)
+    if not lead:
+        return tables[row.ret]
+    for ts in tables:
+        _check_dev(ts)
+    if gated is not None and not row.gate_last:
+        _check_gate(gated[0], gated[1], int(gated[2]) + 1)
+    if row.lead is not None and lead[0].dtype not in row.lead:
+        raise ValueError("%s: %s" % (name, row.lead_words))
+    first, counts, bad = lead[0].dtype, [p.numel() for p in lead], False
+    for p in lead:
+        bad = bad or p.dtype != first
+    for (dtype, k), ts in zip(row.rules, tables[1:]):
+        dtype = dtype or first
+        for t, n in zip(ts, counts):
+            bad = bad or t.dtype != dtype or t.numel() * k != n
+    if bad:
+        raise ValueError("%s: %s" % (name, row.mismatch))
+    if gated is not None and row.gate_last:
+        _check_gate(gated[0], gated[1], int(gated[2]) + 1)
+    args = [_lib.ptr_array([t.data_ptr() for t in ts]) for ts in tables]
+    args.append((ctypes.c_size_t * nb)(*counts))
+    if sr is not None:
+        args += [(ctypes.c_uint64 * nb)(*bases), (ctypes.c_uint32 * nb)(*streams)]
+    args += [nb, int(kungfu_dtype(lead[0])), int(np_),
+             _lib.adam_hyper_array(hyper if gated is None else [dict(hyper, step=1)])]
+    if sr is not None:
+        args.append(key)
+    if gated is not None:
+        args += [gated[0].data_ptr(), _state_ptr(gated[1], gated[2])]
+    if row.fn is None:
+        row.fn = getattr(_lib.load(), row.entry)
+    rc = row.fn(*args, _stream(stream, lead[0].device))
+    _lib.check(rc, row.entry, source="")
+    return tables[row.ret]
+
+
 def adam_update_batch_(params, grads, exp_avgs, exp_avg_sqs, hypers, np_=0, stream=None):
     """The Adam / AdamW update of many flat segments of one dtype (f32, bf16
     or f64) in one launch per 24 of them (kf_adam_update_batch,
@@ -226,28 +362,8 @@ def adam_update_batch_(params, grads, exp_avgs, exp_avg_sqs, hypers, np_=0, stre
     rounded as include/kungfu_amd.h states. hypers[b] is a dict with lr,
     step (>= 1) and optionally betas, eps, weight_decay, decoupled. Every
     tensor starts 16-byte aligned. grads are only read."""
-    params, grads, hypers = list(params), list(grads), list(hypers)
-    ms, vs = list(exp_avgs), list(exp_avg_sqs)
-    if not (len(params) == len(grads) == len(ms) == len(vs) == len(hypers)):
-        raise ValueError("adam_update_batch_: one grad, exp_avg, exp_avg_sq and hyper "
-                         "per param segment")
-    if not params:
-        return params
-    _check_dev(params + grads + ms + vs)
-    for p, g, m, v in zip(params, grads, ms, vs):
-        if p.dtype != params[0].dtype or \
-                any(x.numel() != p.numel() or x.dtype != p.dtype for x in (g, m, v)):
-            raise ValueError("adam_update_batch_: shape/dtype mismatch")
-    lib = _lib.load()
-    cnt = (ctypes.c_size_t * len(params))(*[p.numel() for p in params])
-    rc = lib.kf_adam_update_batch(_lib.ptr_array([p.data_ptr() for p in params]),
-                                  _lib.ptr_array([g.data_ptr() for g in grads]),
-                                  _lib.ptr_array([m.data_ptr() for m in ms]),
-                                  _lib.ptr_array([v.data_ptr() for v in vs]),
-                                  cnt, len(params), int(kungfu_dtype(params[0])), int(np_),
-                                  _lib.adam_hyper_array(hypers), _stream(stream, params[0].device))
-    _lib.check(rc, "kf_adam_update_batch", source="")
-    return params
+    return _update_batch(_adam_update_batch, (params, grads, exp_avgs, exp_avg_sqs), hypers,
+                         None, np_, stream)
 
 
 def adam_master_update_batch_(params16, grads16, masters, exp_avgs, exp_avg_sqs, hypers, np_=0,
@@ -260,28 +376,9 @@ def adam_master_update_batch_(params16, grads16, masters, exp_avgs, exp_avg_sqs,
     rounding to 16 bits. params16 is written, never read; grads16 only read.
     hypers[b] as adam_update_batch_ takes them. Every tensor starts 16-byte
     aligned."""
-    params, grads, hypers = list(params16), list(grads16), list(hypers)
-    ws, ms, vs = list(masters), list(exp_avgs), list(exp_avg_sqs)
-    if not (len(params) == len(grads) == len(ws) == len(ms) == len(vs) == len(hypers)):
-        raise ValueError("adam_master_update_batch_: one grad, master, exp_avg, exp_avg_sq and "
-                         "hyper per param segment")
-    if not params:
-        return params
-    _check_dev(params + grads + ws + ms + vs)
-    if params[0].dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError("adam_master_update_batch_: bf16 or f16 parameters")
-    for p, g, w, m, v in zip(params, grads, ws, ms, vs):
-        if p.dtype != params[0].dtype or g.dtype != p.dtype or g.numel() != p.numel() or \
-                any(x.numel() != p.numel() or x.dtype != torch.float32 for x in (w, m, v)):
-            raise ValueError("adam_master_update_batch_: shape/dtype mismatch")
-    lib = _lib.load()
-    cnt = (ctypes.c_size_t * len(params))(*[p.numel() for p in params])
-    rc = lib.kf_adam_master_update_batch(
-        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (params, grads, ws, ms, vs)],
-        cnt, len(params), int(kungfu_dtype(params[0])), int(np_),
-        _lib.adam_hyper_array(hypers), _stream(stream, params[0].device))
-    _lib.check(rc, "kf_adam_master_update_batch", source="")
-    return params
+    return _update_batch(_adam_master_update_batch,
+                         (params16, grads16, masters, exp_avgs, exp_avg_sqs),
+                         hypers, None, np_, stream)
 
 
 def new_step_gate(device, loss_scale=1.0):
@@ -365,27 +462,8 @@ def adam_update_batch_gated_(params, grads, exp_avgs, exp_avg_sqs, hyper, gate, 
     of `states` as step_gate_update_ left them. A skipped step leaves params
     and both states untouched; otherwise g is multiplied by the gate's
     grad_mul directly after the /np_."""
-    params, grads = list(params), list(grads)
-    ms, vs = list(exp_avgs), list(exp_avg_sqs)
-    if not (len(params) == len(grads) == len(ms) == len(vs)):
-        raise ValueError("adam_update_batch_gated_: one grad, exp_avg and exp_avg_sq per param "
-                         "segment")
-    if not params:
-        return params
-    _check_dev(params + grads + ms + vs)
-    _check_gate(gate, states, int(group) + 1)
-    for p, g, m, v in zip(params, grads, ms, vs):
-        if p.dtype != params[0].dtype or \
-                any(x.numel() != p.numel() or x.dtype != p.dtype for x in (g, m, v)):
-            raise ValueError("adam_update_batch_gated_: shape/dtype mismatch")
-    cnt = (ctypes.c_size_t * len(params))(*[p.numel() for p in params])
-    rc = _lib.load().kf_adam_update_batch_gated(
-        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (params, grads, ms, vs)],
-        cnt, len(params), int(kungfu_dtype(params[0])), int(np_),
-        _lib.adam_hyper_array([dict(hyper, step=1)]), gate.data_ptr(), _state_ptr(states, group),
-        _stream(stream, params[0].device))
-    _lib.check(rc, "kf_adam_update_batch_gated", source="")
-    return params
+    return _update_batch(_adam_update_batch_gated, (params, grads, exp_avgs, exp_avg_sqs),
+                         hyper, (gate, states, group), np_, stream)
 
 
 def adam_master_update_batch_gated_(params16, grads16, masters, exp_avgs, exp_avg_sqs, hyper, gate,
@@ -394,54 +472,12 @@ def adam_master_update_batch_gated_(params16, grads16, masters, exp_avgs, exp_av
     (kf_adam_master_update_batch_gated); hyper, gate, states and group as
     adam_update_batch_gated_ takes them. A skipped step leaves params16,
     masters and both states untouched."""
-    params, grads = list(params16), list(grads16)
-    ws, ms, vs = list(masters), list(exp_avgs), list(exp_avg_sqs)
-    if not (len(params) == len(grads) == len(ws) == len(ms) == len(vs)):
-        raise ValueError("adam_master_update_batch_gated_: one grad, master, exp_avg and "
-                         "exp_avg_sq per param segment")
-    if not params:
-        return params
-    _check_dev(params + grads + ws + ms + vs)
-    _check_gate(gate, states, int(group) + 1)
-    if params[0].dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError("adam_master_update_batch_gated_: bf16 or f16 parameters")
-    for p, g, w, m, v in zip(params, grads, ws, ms, vs):
-        if p.dtype != params[0].dtype or g.dtype != p.dtype or g.numel() != p.numel() or \
-                any(x.numel() != p.numel() or x.dtype != torch.float32 for x in (w, m, v)):
-            raise ValueError("adam_master_update_batch_gated_: shape/dtype mismatch")
-    cnt = (ctypes.c_size_t * len(params))(*[p.numel() for p in params])
-    rc = _lib.load().kf_adam_master_update_batch_gated(
-        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (params, grads, ws, ms, vs)],
-        cnt, len(params), int(kungfu_dtype(params[0])), int(np_),
-        _lib.adam_hyper_array([dict(hyper, step=1)]), gate.data_ptr(), _state_ptr(states, group),
-        _stream(stream, params[0].device))
-    _lib.check(rc, "kf_adam_master_update_batch_gated", source="")
-    return params
+    return _update_batch(_adam_master_update_batch_gated,
+                         (params16, grads16, masters, exp_avgs, exp_avg_sqs),
+                         hyper, (gate, states, group), np_, stream)
 
 
 # -- Adam, stochastic rounding (include/kungfu_amd.h, DESIGN.md §18) -----------
-
-def _sr_tables(name, params, grads, ms, vs, bases, streams, key):
-    """The checked segment tables of the two stochastic-rounding entries."""
-    bases, streams = [int(b) for b in bases], [int(s) for s in streams]
-    if not (len(params) == len(grads) == len(ms) == len(vs) == len(bases) == len(streams)):
-        raise ValueError("%s: one grad, exp_avg, exp_avg_sq, base and stream word per param "
-                         "segment" % name)
-    if not 0 <= int(key) < 1 << 32 or any(not 0 <= s < 1 << 32 for s in streams) or \
-            any(not 0 <= b < 1 << 64 for b in bases):
-        raise ValueError("%s: key and stream words are 32-bit, bases 64-bit unsigned" % name)
-    if not params:
-        return None
-    _check_dev(params + grads + ms + vs)
-    for p, g, m, v in zip(params, grads, ms, vs):
-        if p.dtype != torch.bfloat16 or \
-                any(x.numel() != p.numel() or x.dtype != p.dtype for x in (g, m, v)):
-            raise ValueError("%s: bf16 tensors of one shape per segment" % name)
-    nb = len(params)
-    return [_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (params, grads, ms, vs)] + \
-        [(ctypes.c_size_t * nb)(*[p.numel() for p in params]), (ctypes.c_uint64 * nb)(*bases),
-         (ctypes.c_uint32 * nb)(*streams)]
-
 
 def adam_sr_update_batch_(params, grads, exp_avgs, exp_avg_sqs, hypers, bases, streams, key,
                           np_=0, stream=None):
@@ -455,18 +491,8 @@ def adam_sr_update_batch_(params, grads, exp_avgs, exp_avg_sqs, hypers, bases, s
     `key` the call's 32-bit key: the random bits are Philox2x32-10 of (key,
     stream word, element index) and of nothing else. hypers[b] as
     adam_update_batch_ takes them. grads are only read."""
-    params, grads, hypers = list(params), list(grads), list(hypers)
-    ms, vs = list(exp_avgs), list(exp_avg_sqs)
-    if len(hypers) != len(params):
-        raise ValueError("adam_sr_update_batch_: one hyper per param segment")
-    t = _sr_tables("adam_sr_update_batch_", params, grads, ms, vs, bases, streams, key)
-    if t is None:
-        return params
-    rc = _lib.load().kf_adam_sr_update_batch(
-        *t, len(params), int(kungfu_dtype(params[0])), int(np_), _lib.adam_hyper_array(hypers),
-        int(key), _stream(stream, params[0].device))
-    _lib.check(rc, "kf_adam_sr_update_batch", source="")
-    return params
+    return _update_batch(_adam_sr_update_batch, (params, grads, exp_avgs, exp_avg_sqs), hypers,
+                         None, np_, stream, (bases, streams, key))
 
 
 def adam_sr_update_batch_gated_(params, grads, exp_avgs, exp_avg_sqs, hyper, gate, states, bases,
@@ -474,18 +500,8 @@ def adam_sr_update_batch_gated_(params, grads, exp_avgs, exp_avg_sqs, hyper, gat
     """adam_sr_update_batch_ under a step gate (kf_adam_sr_update_batch_gated);
     hyper, gate, states and group as adam_update_batch_gated_ takes them. A
     skipped step leaves params and both states untouched."""
-    params, grads = list(params), list(grads)
-    ms, vs = list(exp_avgs), list(exp_avg_sqs)
-    t = _sr_tables("adam_sr_update_batch_gated_", params, grads, ms, vs, bases, streams, key)
-    if t is None:
-        return params
-    _check_gate(gate, states, int(group) + 1)
-    rc = _lib.load().kf_adam_sr_update_batch_gated(
-        *t, len(params), int(kungfu_dtype(params[0])), int(np_),
-        _lib.adam_hyper_array([dict(hyper, step=1)]), int(key), gate.data_ptr(),
-        _state_ptr(states, group), _stream(stream, params[0].device))
-    _lib.check(rc, "kf_adam_sr_update_batch_gated", source="")
-    return params
+    return _update_batch(_adam_sr_update_batch_gated, (params, grads, exp_avgs, exp_avg_sqs),
+                         hyper, (gate, states, group), np_, stream, (bases, streams, key))
 
 
 def adam_sr_narrow(x, r):
@@ -505,7 +521,6 @@ def adam_sr_narrow(x, r):
 
 # -- Adam, 8-bit block-wise state (include/kungfu_amd.h) --------
 
-ADAM8_BLOCK = 64                 # elements per quantization block
 ADAM8_ZERO_CODE = (127, 0)       # the code of 0.0: signed (exp_avg), unsigned (exp_avg_sq)
 
 
@@ -529,32 +544,6 @@ def adam8_zero_state(n, device):
             torch.zeros(n // ADAM8_BLOCK, dtype=torch.float32, device=device))
 
 
-def _adam8_tables(name, params, grads, masters, mcs, vcs, mss, vss):
-    """The checked pointer tables and counts of the four 8-bit update entries;
-    None for no segments. masters is None for f32 parameters."""
-    lists = [params, grads] + ([masters] if masters is not None else []) + [mcs, vcs, mss, vss]
-    if not all(len(x) == len(params) for x in lists):
-        raise ValueError("%s: one grad, codes and scales tensor of each state%s per param segment"
-                         % (name, " and a master" if masters is not None else ""))
-    if not params:
-        return None
-    _check_dev([t for ts in lists for t in ts])
-    want = (torch.bfloat16, torch.float16) if masters is not None else (torch.float32,)
-    if params[0].dtype not in want:
-        raise ValueError("%s: %s parameters" % (name, " or ".join(str(d) for d in want)))
-    for i, (p, g, mc, vc, ms, vs) in enumerate(zip(params, grads, mcs, vcs, mss, vss)):
-        n = p.numel()
-        if p.dtype != params[0].dtype or g.dtype != p.dtype or g.numel() != n or \
-                any(c.dtype != torch.uint8 or c.numel() != n for c in (mc, vc)) or \
-                any(s.dtype != torch.float32 or s.numel() * ADAM8_BLOCK != n for s in (ms, vs)) or \
-                (masters is not None and (masters[i].dtype != torch.float32 or
-                                          masters[i].numel() != n)):
-            raise ValueError("%s: shape/dtype mismatch (uint8 codes of the parameters' length, "
-                             "one f32 scale per 64 elements)" % name)
-    return [_lib.ptr_array([t.data_ptr() for t in ts]) for ts in lists] + \
-        [(ctypes.c_size_t * len(params))(*[p.numel() for p in params])]
-
-
 def adam8_update_batch_(params, grads, m_codes, v_codes, m_scales, v_scales, hypers, np_=0,
                         stream=None):
     """The Adam / AdamW update of many flat f32 segments whose exp_avg and
@@ -564,18 +553,9 @@ def adam8_update_batch_(params, grads, m_codes, v_codes, m_scales, v_scales, hyp
     quantize. Every segment's length is a multiple of 64; codes are uint8 of
     that length, scales f32 of a 64th of it. hypers[b] as adam_update_batch_
     takes them. grads are only read."""
-    params, grads, hypers = list(params), list(grads), list(hypers)
-    if len(hypers) != len(params):
-        raise ValueError("adam8_update_batch_: one hyper per param segment")
-    t = _adam8_tables("adam8_update_batch_", params, grads, None, list(m_codes), list(v_codes),
-                      list(m_scales), list(v_scales))
-    if t is None:
-        return params
-    rc = _lib.load().kf_adam8_update_batch(
-        *t, len(params), int(kungfu_dtype(params[0])), int(np_), _lib.adam_hyper_array(hypers),
-        _stream(stream, params[0].device))
-    _lib.check(rc, "kf_adam8_update_batch", source="")
-    return params
+    return _update_batch(_adam8_update_batch,
+                         (params, grads, m_codes, v_codes, m_scales, v_scales),
+                         hypers, None, np_, stream)
 
 
 def adam8_update_batch_gated_(params, grads, m_codes, v_codes, m_scales, v_scales, hyper, gate,
@@ -583,18 +563,9 @@ def adam8_update_batch_gated_(params, grads, m_codes, v_codes, m_scales, v_scale
     """adam8_update_batch_ under a step gate (kf_adam8_update_batch_gated);
     hyper, gate, states and group as adam_update_batch_gated_ takes them. A
     skipped step leaves params, codes and scales untouched."""
-    params, grads = list(params), list(grads)
-    t = _adam8_tables("adam8_update_batch_gated_", params, grads, None, list(m_codes),
-                      list(v_codes), list(m_scales), list(v_scales))
-    if t is None:
-        return params
-    _check_gate(gate, states, int(group) + 1)
-    rc = _lib.load().kf_adam8_update_batch_gated(
-        *t, len(params), int(kungfu_dtype(params[0])), int(np_),
-        _lib.adam_hyper_array([dict(hyper, step=1)]), gate.data_ptr(), _state_ptr(states, group),
-        _stream(stream, params[0].device))
-    _lib.check(rc, "kf_adam8_update_batch_gated", source="")
-    return params
+    return _update_batch(_adam8_update_batch_gated,
+                         (params, grads, m_codes, v_codes, m_scales, v_scales), hyper,
+                         (gate, states, group), np_, stream)
 
 
 def adam8_master_update_batch_(params16, grads16, masters, m_codes, v_codes, m_scales, v_scales,
@@ -603,18 +574,9 @@ def adam8_master_update_batch_(params16, grads16, masters, m_codes, v_codes, m_s
     (kf_adam8_master_update_batch): the f32 update runs on (masters, widened
     grads16, dequantized state) and params16 = masters narrowed,
     round-to-nearest-even. params16 is written, never read."""
-    params, grads, hypers = list(params16), list(grads16), list(hypers)
-    if len(hypers) != len(params):
-        raise ValueError("adam8_master_update_batch_: one hyper per param segment")
-    t = _adam8_tables("adam8_master_update_batch_", params, grads, list(masters), list(m_codes),
-                      list(v_codes), list(m_scales), list(v_scales))
-    if t is None:
-        return params
-    rc = _lib.load().kf_adam8_master_update_batch(
-        *t, len(params), int(kungfu_dtype(params[0])), int(np_), _lib.adam_hyper_array(hypers),
-        _stream(stream, params[0].device))
-    _lib.check(rc, "kf_adam8_master_update_batch", source="")
-    return params
+    return _update_batch(_adam8_master_update_batch,
+                         (params16, grads16, masters, m_codes, v_codes, m_scales, v_scales),
+                         hypers, None, np_, stream)
 
 
 def adam8_master_update_batch_gated_(params16, grads16, masters, m_codes, v_codes, m_scales,
@@ -622,18 +584,9 @@ def adam8_master_update_batch_gated_(params16, grads16, masters, m_codes, v_code
     """adam8_master_update_batch_ under a step gate
     (kf_adam8_master_update_batch_gated). A skipped step leaves params16,
     masters, codes and scales untouched."""
-    params, grads = list(params16), list(grads16)
-    t = _adam8_tables("adam8_master_update_batch_gated_", params, grads, list(masters),
-                      list(m_codes), list(v_codes), list(m_scales), list(v_scales))
-    if t is None:
-        return params
-    _check_gate(gate, states, int(group) + 1)
-    rc = _lib.load().kf_adam8_master_update_batch_gated(
-        *t, len(params), int(kungfu_dtype(params[0])), int(np_),
-        _lib.adam_hyper_array([dict(hyper, step=1)]), gate.data_ptr(), _state_ptr(states, group),
-        _stream(stream, params[0].device))
-    _lib.check(rc, "kf_adam8_master_update_batch_gated", source="")
-    return params
+    return _update_batch(_adam8_master_update_batch_gated,
+                         (params16, grads16, masters, m_codes, v_codes, m_scales, v_scales),
+                         hyper, (gate, states, group), np_, stream)
 
 
 def adam8_quantize(x, which, codes=None, scales=None, stream=None):
@@ -686,25 +639,8 @@ def lamb_moments_batch_(params, grads, exp_avgs, exp_avg_sqs, updates, hypers, n
     updated in place, updates[b] is written, params and grads are only read.
     hypers[b] as adam_update_batch_ takes them (lr and decoupled are ignored).
     Every tensor starts 16-byte aligned."""
-    params, grads, hypers = list(params), list(grads), list(hypers)
-    ms, vs, us = list(exp_avgs), list(exp_avg_sqs), list(updates)
-    if not (len(params) == len(grads) == len(ms) == len(vs) == len(us) == len(hypers)):
-        raise ValueError("lamb_moments_batch_: one grad, exp_avg, exp_avg_sq, update and hyper "
-                         "per param segment")
-    if not params:
-        return us
-    _check_dev(params + grads + ms + vs + us)
-    for p, g, m, v, u in zip(params, grads, ms, vs, us):
-        if p.dtype != params[0].dtype or \
-                any(x.numel() != p.numel() or x.dtype != p.dtype for x in (g, m, v, u)):
-            raise ValueError("lamb_moments_batch_: shape/dtype mismatch")
-    cnt = (ctypes.c_size_t * len(params))(*[p.numel() for p in params])
-    rc = _lib.load().kf_lamb_moments_batch(
-        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (params, grads, ms, vs, us)],
-        cnt, len(params), int(kungfu_dtype(params[0])), int(np_),
-        _lib.adam_hyper_array(hypers), _stream(stream, params[0].device))
-    _lib.check(rc, "kf_lamb_moments_batch", source="")
-    return us
+    return _update_batch(_lamb_moments_batch, (params, grads, exp_avgs, exp_avg_sqs, updates),
+                         hypers, None, np_, stream)
 
 
 def lamb_master_moments_batch_(grads16, masters, exp_avgs, exp_avg_sqs, updates, hypers, np_=0,
@@ -714,27 +650,9 @@ def lamb_master_moments_batch_(grads16, masters, exp_avgs, exp_avg_sqs, updates,
     gradient is widened, the f32 arithmetic runs on (masters, g, exp_avgs,
     exp_avg_sqs) and writes the fp32 updates. masters and grads16 are only
     read; the 16-bit parameters are not touched (LambApplyPlan writes them)."""
-    grads, ws, hypers = list(grads16), list(masters), list(hypers)
-    ms, vs, us = list(exp_avgs), list(exp_avg_sqs), list(updates)
-    if not (len(grads) == len(ws) == len(ms) == len(vs) == len(us) == len(hypers)):
-        raise ValueError("lamb_master_moments_batch_: one master, exp_avg, exp_avg_sq, update and "
-                         "hyper per gradient segment")
-    if not grads:
-        return us
-    _check_dev(grads + ws + ms + vs + us)
-    if grads[0].dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError("lamb_master_moments_batch_: bf16 or f16 gradients")
-    for g, w, m, v, u in zip(grads, ws, ms, vs, us):
-        if g.dtype != grads[0].dtype or \
-                any(x.numel() != g.numel() or x.dtype != torch.float32 for x in (w, m, v, u)):
-            raise ValueError("lamb_master_moments_batch_: shape/dtype mismatch")
-    cnt = (ctypes.c_size_t * len(grads))(*[g.numel() for g in grads])
-    rc = _lib.load().kf_lamb_master_moments_batch(
-        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (grads, ws, ms, vs, us)],
-        cnt, len(grads), int(kungfu_dtype(grads[0])), int(np_),
-        _lib.adam_hyper_array(hypers), _stream(stream, grads[0].device))
-    _lib.check(rc, "kf_lamb_master_moments_batch", source="")
-    return us
+    return _update_batch(_lamb_master_moments_batch,
+                         (grads16, masters, exp_avgs, exp_avg_sqs, updates), hypers, None, np_,
+                         stream)
 
 
 def lamb_trust_update_(sq, world, group_of, groups, nlr, ratio, trust_clip=0.0, stream=None):
@@ -745,24 +663,33 @@ def lamb_trust_update_(sq, world, group_of, groups, nlr, ratio, trust_clip=0.0, 
     -> group); groups[j] a dict with lr and adapt. Writes ratio[t] =
     ||p|| / ||u|| (1 where adapt is off or a norm is not > 0), clipped from
     above by trust_clip > 0, and nlr[t] = -(lr * ratio[t]). No host sync."""
+    return _trust_update("lamb_trust_update_", sq, world, group_of, groups, nlr, ratio, None,
+                         trust_clip, stream)
+
+
+def _trust_update(name, sq, world, group_of, groups, nlr, ratio, gate, trust_clip, stream):
+    """Both trust updates: gate is None for the ungated one."""
     groups = list(groups)
     _check_dev([sq, group_of, nlr, ratio])
+    if gate is not None:
+        _check_gate(gate)
     T = group_of.numel()
     if group_of.dtype != torch.int32 or T < 1 or not groups:
-        raise ValueError("lamb_trust_update_: group_of is a non-empty int32 tensor, and at least "
-                         "one group")
+        raise ValueError("%s: group_of is a non-empty int32 tensor, and at least one group" % name)
     if sq.dtype != torch.float64 or sq.numel() != int(world) * 2 * T or int(world) < 1:
-        raise ValueError("lamb_trust_update_: sq is world * 2 * T float64 values")
+        raise ValueError("%s: sq is world * 2 * T float64 values" % name)
     for t in (nlr, ratio):
         if t.dtype != torch.float64 or t.numel() != T:
-            raise ValueError("lamb_trust_update_: nlr and ratio are T float64 values")
+            raise ValueError("%s: nlr and ratio are T float64 values" % name)
     garr = (_lib.LambGroup * len(groups))()
     for a, h in zip(garr, groups):
         a.lr, a.adapt = float(h["lr"]), int(bool(h["adapt"]))
-    rc = _lib.load().kf_lamb_trust_update(
+    entry = "kf_lamb_trust_update" if gate is None else "kf_lamb_trust_update_gated"
+    rc = getattr(_lib.load(), entry)(
         sq.data_ptr(), int(world), T, group_of.data_ptr(), garr, len(groups),
-        float(trust_clip or 0.0), nlr.data_ptr(), ratio.data_ptr(), _stream(stream, sq.device))
-    _lib.check(rc, "kf_lamb_trust_update", source="")
+        float(trust_clip or 0.0), nlr.data_ptr(), ratio.data_ptr(),
+        *([] if gate is None else [gate.data_ptr()]), _stream(stream, sq.device))
+    _lib.check(rc, entry, source="")
     return nlr
 
 
@@ -776,27 +703,9 @@ def lamb_moments_batch_gated_(params, grads, exp_avgs, exp_avg_sqs, updates, hyp
     step_gate_update_ with every group's lr = 1 left them. A skipped step
     leaves exp_avgs, exp_avg_sqs and updates untouched; otherwise g is
     multiplied by the gate's grad_mul directly after the /np_."""
-    params, grads = list(params), list(grads)
-    ms, vs, us = list(exp_avgs), list(exp_avg_sqs), list(updates)
-    if not (len(params) == len(grads) == len(ms) == len(vs) == len(us)):
-        raise ValueError("lamb_moments_batch_gated_: one grad, exp_avg, exp_avg_sq and update "
-                         "per param segment")
-    if not params:
-        return us
-    _check_dev(params + grads + ms + vs + us)
-    _check_gate(gate, states, int(group) + 1)
-    for p, g, m, v, u in zip(params, grads, ms, vs, us):
-        if p.dtype != params[0].dtype or \
-                any(x.numel() != p.numel() or x.dtype != p.dtype for x in (g, m, v, u)):
-            raise ValueError("lamb_moments_batch_gated_: shape/dtype mismatch")
-    cnt = (ctypes.c_size_t * len(params))(*[p.numel() for p in params])
-    rc = _lib.load().kf_lamb_moments_batch_gated(
-        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (params, grads, ms, vs, us)],
-        cnt, len(params), int(kungfu_dtype(params[0])), int(np_),
-        _lib.adam_hyper_array([dict(hyper, step=1)]), gate.data_ptr(), _state_ptr(states, group),
-        _stream(stream, params[0].device))
-    _lib.check(rc, "kf_lamb_moments_batch_gated", source="")
-    return us
+    return _update_batch(_lamb_moments_batch_gated,
+                         (params, grads, exp_avgs, exp_avg_sqs, updates), hyper,
+                         (gate, states, group), np_, stream)
 
 
 def lamb_master_moments_batch_gated_(grads16, masters, exp_avgs, exp_avg_sqs, updates, hyper, gate,
@@ -804,56 +713,17 @@ def lamb_master_moments_batch_gated_(grads16, masters, exp_avgs, exp_avg_sqs, up
     """lamb_master_moments_batch_ under a step gate
     (kf_lamb_master_moments_batch_gated); hyper, gate, states and group as
     lamb_moments_batch_gated_ takes them."""
-    grads, ws = list(grads16), list(masters)
-    ms, vs, us = list(exp_avgs), list(exp_avg_sqs), list(updates)
-    if not (len(grads) == len(ws) == len(ms) == len(vs) == len(us)):
-        raise ValueError("lamb_master_moments_batch_gated_: one master, exp_avg, exp_avg_sq and "
-                         "update per gradient segment")
-    if not grads:
-        return us
-    _check_dev(grads + ws + ms + vs + us)
-    _check_gate(gate, states, int(group) + 1)
-    if grads[0].dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError("lamb_master_moments_batch_gated_: bf16 or f16 gradients")
-    for g, w, m, v, u in zip(grads, ws, ms, vs, us):
-        if g.dtype != grads[0].dtype or \
-                any(x.numel() != g.numel() or x.dtype != torch.float32 for x in (w, m, v, u)):
-            raise ValueError("lamb_master_moments_batch_gated_: shape/dtype mismatch")
-    cnt = (ctypes.c_size_t * len(grads))(*[g.numel() for g in grads])
-    rc = _lib.load().kf_lamb_master_moments_batch_gated(
-        *[_lib.ptr_array([t.data_ptr() for t in ts]) for ts in (grads, ws, ms, vs, us)],
-        cnt, len(grads), int(kungfu_dtype(grads[0])), int(np_),
-        _lib.adam_hyper_array([dict(hyper, step=1)]), gate.data_ptr(), _state_ptr(states, group),
-        _stream(stream, grads[0].device))
-    _lib.check(rc, "kf_lamb_master_moments_batch_gated", source="")
-    return us
+    return _update_batch(_lamb_master_moments_batch_gated,
+                         (grads16, masters, exp_avgs, exp_avg_sqs, updates), hyper,
+                         (gate, states, group), np_, stream)
 
 
 def lamb_trust_update_gated_(sq, world, group_of, groups, nlr, ratio, gate, trust_clip=0.0,
                              stream=None):
     """lamb_trust_update_ under a step gate (kf_lamb_trust_update_gated): a
     skipped step leaves nlr and ratio as they were."""
-    groups = list(groups)
-    _check_dev([sq, group_of, nlr, ratio])
-    _check_gate(gate)
-    T = group_of.numel()
-    if group_of.dtype != torch.int32 or T < 1 or not groups:
-        raise ValueError("lamb_trust_update_gated_: group_of is a non-empty int32 tensor, and at "
-                         "least one group")
-    if sq.dtype != torch.float64 or sq.numel() != int(world) * 2 * T or int(world) < 1:
-        raise ValueError("lamb_trust_update_gated_: sq is world * 2 * T float64 values")
-    for t in (nlr, ratio):
-        if t.dtype != torch.float64 or t.numel() != T:
-            raise ValueError("lamb_trust_update_gated_: nlr and ratio are T float64 values")
-    garr = (_lib.LambGroup * len(groups))()
-    for a, h in zip(garr, groups):
-        a.lr, a.adapt = float(h["lr"]), int(bool(h["adapt"]))
-    rc = _lib.load().kf_lamb_trust_update_gated(
-        sq.data_ptr(), int(world), T, group_of.data_ptr(), garr, len(groups),
-        float(trust_clip or 0.0), nlr.data_ptr(), ratio.data_ptr(), gate.data_ptr(),
-        _stream(stream, sq.device))
-    _lib.check(rc, "kf_lamb_trust_update_gated", source="")
-    return nlr
+    return _trust_update("lamb_trust_update_gated_", sq, world, group_of, groups, nlr, ratio, gate,
+                         trust_clip, stream)
 
 
 class LambApplyPlan:

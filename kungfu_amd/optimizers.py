@@ -836,6 +836,187 @@ class _ShardedSGD(_Sharded):
             G["first"] = False
 
 
+class _AdamState:
+    """The storage variant of one Adam bucket group: where its
+    exp_avg / exp_avg_sq shards live, how they are zeroed, updated with and
+    without a gate, and presented to and restored from a checkpoint. Made once,
+    with the buckets; what a step needs of the exchange is bound then. This one
+    is the plain variant: state in the buckets' dtype, updated by the
+    exchange's fused step. o is the optimizer, G the group's dict."""
+
+    def __init__(self, o, G):
+        self.o, self.G, self.ex = o, G, o._kf_ex
+        self.pb, self.gb = G["pb"].buckets, G["gb"].buckets
+
+    def zero(self, dtype=None):
+        G = self.G
+        G["m"], G["v"] = (self.o._kf_zero_shards(G, dtype) for _ in range(2))
+
+    def step(self, j, h):
+        G = self.G
+        self.ex.adam_step_(self.pb, self.gb, G["m"], G["v"], [h] * len(self.pb))
+
+    def step_gated(self, j, h):
+        o, G = self.o, self.G
+        self.ex.adam_gated_step_(self.pb, self.gb, G["w"], G["m"], G["v"], h, G["np"], o._kf_gate,
+                                 o._kf_gstates, j, ("gated", j))
+
+    def present(self):
+        """Collective: {entry of state_buffers(): {parameter: full tensor}}."""
+        o, G = self.o, self.G
+        return {"exp_avg": o._kf_unshard(G, G["m"]), "exp_avg_sq": o._kf_unshard(G, G["v"])}
+
+    def restore(self, mapping, step):
+        """load_state_buffers' mapping into this rank's shards."""
+        o, G = self.o, self.G
+        for key, shards in (("exp_avg", G["m"]), ("exp_avg_sq", G["v"])):
+            o._kf_reshard(G, shards, lambda p, key=key: mapping[p][key] if p in mapping else None)
+
+
+class _WithMaster:
+    """Beside a variant: G["w"], the fp32 master shards, as "master"."""
+
+    def present(self):
+        out = super().present()
+        out["master"] = self.o._kf_unshard(self.G, self.G["w"])
+        return out
+
+    def restore(self, mapping, step):
+        super().restore(mapping, step)
+        self.o._kf_reshard(self.G, self.G["w"],
+                           lambda p: mapping.get(p, {}).get("master", p.data))
+
+
+class _AdamMaster(_WithMaster, _AdamState):
+    """16-bit parameters through fp32 masters and fp32 state."""
+
+    def zero(self):
+        import torch
+        super().zero(torch.float32)
+
+    def step(self, j, h):
+        G = self.G
+        self.ex.adam_master_step_(self.pb, self.gb, G["w"], G["m"], G["v"], [h] * len(self.pb))
+
+
+class _AdamOnShards(_AdamState):
+    """A variant whose update is not the exchange's own: reduce-scatter, the
+    epilogue's update(...) on this rank's shards, all-gather. `key` names the
+    exchange's workspace of the ungated step, `probe` the method by which an
+    injected epilogue is told from the HIP one, `name` the epilogue's ungated
+    update (its gated twin ends in gated_). The slices of the parameter buckets
+    that are this rank's never move, so they are made here."""
+
+    def __init__(self, o, G, key, probe, name):
+        super().__init__(o, G)
+        self.key, self.ep, self.mine = key, o._kf_ops(probe), o._kf_mine(G)
+        self.run, self.run_gated = getattr(self.ep, name), getattr(self.ep, name + "gated_")
+
+    def step(self, j, h):
+        ex = self.ex
+        np_ = ex.reduce_shards_(self.gb, (self.key, j))
+        self.update(ex.grad_shards_(self.gb, (self.key, j)), [h] * len(self.pb), np_, ())
+        ex.gather_params_(self.pb)
+
+    def step_gated(self, j, h):
+        o = self.o
+        self.update(self.ex.grad_shards_(self.gb, ("gated", j)), h, self.G["np"],
+                    (o._kf_gate, o._kf_gstates, j))
+        self.ex.gather_params_(self.pb)
+
+
+class _AdamSR(_AdamOnShards):
+    """bf16 state and stochastic rounding; "sr_draw" is the
+    host's count of draws."""
+
+    def __init__(self, o, G):
+        super().__init__(o, G, "sr", "adam_sr_update_", "adam_sr_update_")
+        self.bases = [self.ex.rank * m.numel() for m in self.mine]  # offsets in the buckets
+
+    def update(self, shards, hyper, np_, gated):
+        G = self.G
+        G["draw"] += 1  # the host's count: a step the device skips draws too
+        (self.run_gated if gated else self.run)(
+            self.mine, shards, G["m"], G["v"], hyper, *gated, np_, self.bases, G["streams"],
+            G["draw"] & 0xffffffff)
+
+    def present(self):
+        out = super().present()
+        out["sr_draw"] = {p: self.G["draw"] for p in out["exp_avg"]}
+        return out
+
+    def restore(self, mapping, step):
+        super().restore(mapping, step)
+        draws = {int(mapping[p]["sr_draw"]) for p in self.G["ps"]
+                 if p in mapping and "sr_draw" in mapping[p]}
+        if len(draws) > 1:
+            raise ValueError("load_state_buffers: the parameters of one group differ in "
+                             "sr_draw: %s" % sorted(draws))
+        self.G["draw"] = draws.pop() if draws else step
+
+
+class _Adam8(_AdamOnShards):
+    """exp_avg / exp_avg_sq as block-wise 8-bit codes G["m"], G["v"] and f32
+    scales G["ms"], G["vs"]; a checkpoint holds them
+    dequantized, a form that does not depend on world or layout."""
+
+    parts = (("exp_avg", "m", "ms"), ("exp_avg_sq", "v", "vs"))  # of table 0 and of table 1
+
+    def __init__(self, o, G, name="adam8_update_"):
+        super().__init__(o, G, "adam8", "adam8_update_", name)
+
+    def zero(self):
+        # the zero state: scale 0, exp_avg code 127, exp_avg_sq code 0
+        import torch
+        from .ops import ADAM8_BLOCK, ADAM8_ZERO_CODE
+        o, G = self.o, self.G
+        for key, code in zip(("m", "v"), ADAM8_ZERO_CODE):
+            G[key] = o._kf_zero_shards(G, torch.uint8)
+            for c in G[key]:
+                c.fill_(code)
+        for key in ("ms", "vs"):
+            G[key] = [torch.zeros(c.numel() // ADAM8_BLOCK, dtype=torch.float32, device=c.device)
+                      for c in G["m"]]
+
+    def update(self, shards, hyper, np_, gated):
+        G = self.G
+        (self.run_gated if gated else self.run)(
+            self.mine, shards, G["m"], G["v"], G["ms"], G["vs"], hyper, *gated, np_)
+
+    def present(self):
+        o, G, ep = self.o, self.G, self.ep
+        return {key: o._kf_unshard(G, [ep.adam8_dequantize(c, x, which)
+                                       for c, x in zip(G[codes], G[scales])])
+                for which, (key, codes, scales) in enumerate(self.parts)}
+
+    def restore(self, mapping, step):
+        # requantized; idempotent on what present() gave
+        import torch
+        o, G, ep = self.o, self.G, self.ep
+        for which, (key, codes, scales) in enumerate(self.parts):
+            full = [torch.zeros(c.numel(), dtype=torch.float32, device=c.device) for c in G[codes]]
+            o._kf_reshard(G, full, lambda p, key=key: mapping[p][key] if p in mapping else None)
+            for x, c, sc in zip(full, G[codes], G[scales]):
+                ep.adam8_quantize_(x, which, c, sc)
+
+
+class _Adam8Master(_WithMaster, _Adam8):
+    """8-bit state beside fp32 masters of 16-bit parameters."""
+
+    def __init__(self, o, G):
+        super().__init__(o, G, "adam8_master_update_")
+
+    def update(self, shards, hyper, np_, gated):
+        G = self.G
+        (self.run_gated if gated else self.run)(
+            self.mine, shards, G["w"], G["m"], G["v"], G["ms"], G["vs"], hyper, *gated, np_)
+
+
+# (8-bit state, master weights) -> the variant; stochastic rounding comes first
+_ADAM_STATES = {(False, False): _AdamState, (False, True): _AdamMaster,
+                (True, False): _Adam8, (True, True): _Adam8Master}
+
+
 class _ShardedAdam(_Sharded):
     """reduce-scatter(grads) -> Adam / AdamW update on the own shard ->
     all-gather(params). exp_avg and exp_avg_sq are one shard each per bucket;
@@ -871,19 +1052,21 @@ class _ShardedAdam(_Sharded):
                 G["sr"] = True
                 G["streams"] = [sr_stream_word(self._kf_sr_seed, j, i)
                                 for i in range(len(G["pb"].buckets))]
-        for G in self._kf_groups if self._kf_state_bits == 8 else []:
-            G["b8"] = True  # the dtypes were checked when the optimizer was made
+        for G in self._kf_groups:
+            # 8-bit state: the dtypes were checked when the optimizer was made
+            G["b8"] = self._kf_state_bits == 8
+            kind = _AdamSR if G["sr"] else _ADAM_STATES[G["b8"], G["w"] is not None]
+            G["var"] = kind(self, G)
         if self._kf_gated:
             self._kf_build_gated()
 
-    # -- 8-bit block-wise state ---------------------------------
-    def _kf_adam8_ops(self):
-        """Where the 8-bit updates and the quantizer run: the exchange's
-        epilogue (collective.Exchange; injectable for CPU tests) or the HIP
-        one."""
+    def _kf_ops(self, probe):
+        """Where a family of device steps runs: the exchange's epilogue if it
+        has the method `probe` (collective.Exchange; injectable for CPU
+        tests), else the HIP one."""
         from .collective import HipEpilogue
         ep = getattr(self._kf_ex, "epilogue", None)
-        return ep if hasattr(ep, "adam8_update_") else HipEpilogue()
+        return ep if hasattr(ep, probe) else HipEpilogue()
 
     def _kf_mine(self, G):
         """This rank's slices of the group's parameter buckets."""
@@ -891,66 +1074,20 @@ class _ShardedAdam(_Sharded):
         q = [b.numel() // ex.world for b in G["pb"].buckets]
         return [b[ex.rank * n:(ex.rank + 1) * n] for b, n in zip(G["pb"].buckets, q)]
 
-    def _kf_adam8_update(self, G, shards, hyper, np_, gated=None):
-        """The 8-bit update of one group on this rank's shards. hyper: one per
-        bucket, or with gated = (gate, states, group) the one hyper."""
-        ep, mine = self._kf_adam8_ops(), self._kf_mine(G)
-        state = (G["m"], G["v"], G["ms"], G["vs"])
-        if gated is None:
-            if G["w"] is not None:
-                ep.adam8_master_update_(mine, shards, G["w"], *state, hyper, np_)
-            else:
-                ep.adam8_update_(mine, shards, *state, hyper, np_)
-        elif G["w"] is not None:
-            ep.adam8_master_update_gated_(mine, shards, G["w"], *state, hyper, *gated, np_)
-        else:
-            ep.adam8_update_gated_(mine, shards, *state, hyper, *gated, np_)
-
-    def _kf_adam8_f32(self, G, which):
-        """One f32 shard per bucket: the group's exp_avg (which = 0) or
-        exp_avg_sq (1) dequantized."""
-        ep = self._kf_adam8_ops()
-        codes, scales = (G["m"], G["ms"]) if which == 0 else (G["v"], G["vs"])
-        return [ep.adam8_dequantize(c, s, which) for c, s in zip(codes, scales)]
-
-    # -- stochastic rounding (DESIGN.md §18) -----------------------------------
-    def _kf_sr_ops(self):
-        """Where the stochastic-rounding updates run: the exchange's epilogue
-        (collective.Exchange; injectable for CPU tests) or the HIP one."""
-        from .collective import HipEpilogue
-        ep = getattr(self._kf_ex, "epilogue", None)
-        return ep if hasattr(ep, "adam_sr_update_") else HipEpilogue()
-
-    def _kf_sr_tables(self, G):
-        """(this rank's slices of the group's parameter buckets, their element
-        offsets in the buckets, the call's key) of a stochastic-rounding group."""
-        ex = self._kf_ex
-        q = [b.numel() // ex.world for b in G["pb"].buckets]
-        mine = [b[ex.rank * n:(ex.rank + 1) * n] for b, n in zip(G["pb"].buckets, q)]
-        return mine, [ex.rank * n for n in q], G["draw"] & 0xffffffff
-
     def _kf_states(self, G):
-        """The group's zeroed exp_avg / exp_avg_sq shards, allocated on the
-        first step (fp32 where the group has master weights)."""
-        if G["m"] is None and G["b8"]:
-            # the zero state: scale 0, exp_avg code 127, exp_avg_sq code 0
-            from .ops import ADAM8_BLOCK, ADAM8_ZERO_CODE
-            import torch
-            G["m"] = self._kf_zero_shards(G, torch.uint8)
-            G["v"] = self._kf_zero_shards(G, torch.uint8)
-            for c in G["m"]:
-                c.fill_(ADAM8_ZERO_CODE[0])
-            for c in G["v"]:
-                c.fill_(ADAM8_ZERO_CODE[1])
-            world = self._kf_ex.world
-            for key in ("ms", "vs"):
-                G[key] = [torch.zeros(b.numel() // world // ADAM8_BLOCK, dtype=torch.float32,
-                                      device=b.device) for b in G["pb"].buckets]
+        """The group's exp_avg / exp_avg_sq shards, zeroed by its variant on
+        the first step."""
         if G["m"] is None:
-            import torch
-            dtype = torch.float32 if G["w"] is not None else None
-            G["m"], G["v"] = self._kf_zero_shards(G, dtype), self._kf_zero_shards(G, dtype)
+            G["var"].zero()
         return G["m"], G["v"]
+
+    def _kf_hyper(self, G, **more):
+        """The group's hyper, read at every step (schedulers change them), with
+        what the caller adds: step, adapt."""
+        pg = self.param_groups[G["gi"]]
+        return dict(lr=float(pg["lr"]), betas=tuple(float(b) for b in pg["betas"]),
+                    eps=float(pg["eps"]), weight_decay=float(pg["weight_decay"]),
+                    decoupled=self._kf_decoupled, **more)
 
     # -- the gated step (DESIGN.md §16) ---------------------------------------
     _kf_gated = False
@@ -958,14 +1095,6 @@ class _ShardedAdam(_Sharded):
     _kf_rule = None     # init_scale, growth_factor, backoff_factor, growth_interval
     _kf_gate = None     # kf_step_gate on the device, a uint8 tensor
     _kf_gstates = None  # kf_step_state per bucket group
-
-    def _kf_gate_ops(self):
-        """Where the norm pass, the verdict and the gated updates run: the
-        exchange's epilogue (collective.Exchange; injectable for CPU tests)
-        or the HIP one."""
-        from .collective import HipEpilogue
-        ep = getattr(self._kf_ex, "epilogue", None)
-        return ep if hasattr(ep, "step_gate_update_") else HipEpilogue()
 
     def _kf_gate_tensor(self):
         """The gate, created when first needed (scale_loss comes before the
@@ -985,7 +1114,7 @@ class _ShardedAdam(_Sharded):
         buffers of the plans' sums of squares."""
         import torch
         from . import ops
-        gate, ex, ep = self._kf_gate_tensor(), self._kf_ex, self._kf_gate_ops()
+        gate, ex, ep = self._kf_gate_tensor(), self._kf_ex, self._kf_ops("step_gate_update_")
         self._kf_gstates = ops.new_step_states(gate.device, len(self._kf_groups))
         by = {}
         for j, G in enumerate(self._kf_groups):
@@ -1006,7 +1135,7 @@ class _ShardedAdam(_Sharded):
         the plans' sums), D (the verdict): queued, nothing waits. Returns
         every group's hyper. gate_lr: the lr the step states are advanced
         with in place of the groups' own (LAMB: 1.0)."""
-        ex, ep, groups = self._kf_ex, self._kf_gate_ops(), self._kf_groups
+        ex, ep, groups = self._kf_ex, self._kf_ops("step_gate_update_"), self._kf_groups
         for j, G in enumerate(groups):
             self._kf_states(G)
             G["np"] = ex.reduce_shards_(G["gb"].buckets, ("gated", j))
@@ -1019,12 +1148,7 @@ class _ShardedAdam(_Sharded):
             plan.run("sq", out=out)
             self._kf_sq[k:k + 1].copy_(out[-1:])
         ex.gather_doubles_(self._kf_sq, self._kf_sq_all)
-        hs = []
-        for G in groups:
-            pg = self.param_groups[G["gi"]]  # read at every step: schedulers change them
-            hs.append({"lr": float(pg["lr"]), "betas": tuple(float(b) for b in pg["betas"]),
-                       "eps": float(pg["eps"]), "weight_decay": float(pg["weight_decay"]),
-                       "decoupled": self._kf_decoupled})
+        hs = [self._kf_hyper(G) for G in groups]
         r = self._kf_rule
         ghs = hs if gate_lr is None else [dict(h, lr=float(gate_lr)) for h in hs]
         ep.step_gate_update_(self._kf_sq_all, ex.world, nps, ghs, self._kf_gstates, self._kf_gate,
@@ -1036,24 +1160,8 @@ class _ShardedAdam(_Sharded):
     def _kf_step_gated(self):
         """A to D (_kf_gate_verdict), E (every group's gated update and the
         parameters' all-gather): queued, nothing waits for the verdict."""
-        ex, groups = self._kf_ex, self._kf_groups
-        hs = self._kf_gate_verdict()
-        for j, (G, h) in enumerate(zip(groups, hs)):
-            if G["sr"]:
-                G["draw"] += 1  # the host's count: a step the device skips draws too
-                mine, bases, key = self._kf_sr_tables(G)
-                self._kf_sr_ops().adam_sr_update_gated_(
-                    mine, ex.grad_shards_(G["gb"].buckets, ("gated", j)), G["m"], G["v"], h,
-                    self._kf_gate, self._kf_gstates, j, G["np"], bases, G["streams"], key)
-                ex.gather_params_(G["pb"].buckets)
-                continue
-            if G["b8"]:
-                self._kf_adam8_update(G, ex.grad_shards_(G["gb"].buckets, ("gated", j)), h,
-                                      G["np"], (self._kf_gate, self._kf_gstates, j))
-                ex.gather_params_(G["pb"].buckets)
-                continue
-            ex.adam_gated_step_(G["pb"].buckets, G["gb"].buckets, G["w"], G["m"], G["v"], h,
-                                G["np"], self._kf_gate, self._kf_gstates, j, ("gated", j))
+        for j, (G, h) in enumerate(zip(self._kf_groups, self._kf_gate_verdict())):
+            G["var"].step_gated(j, h)
 
     _kf_gate_words = "max_grad_norm or loss_scale"  # what turns the gate on
 
@@ -1127,33 +1235,10 @@ class _ShardedAdam(_Sharded):
             _finish(self._kf_ex)
             return loss
         for j, G in enumerate(self._kf_groups):
-            pg = self.param_groups[G["gi"]]  # read at every step: schedulers change them
-            ms, vs = self._kf_states(G)
+            if G["m"] is None:
+                G["var"].zero()
             G["step"] += 1
-            h = {"lr": float(pg["lr"]), "betas": tuple(float(b) for b in pg["betas"]),
-                 "eps": float(pg["eps"]), "weight_decay": float(pg["weight_decay"]),
-                 "decoupled": self._kf_decoupled, "step": G["step"]}
-            nb = len(G["pb"].buckets)
-            if G["sr"]:
-                ex = self._kf_ex
-                G["draw"] += 1
-                np_ = ex.reduce_shards_(G["gb"].buckets, ("sr", j))
-                mine, bases, key = self._kf_sr_tables(G)
-                self._kf_sr_ops().adam_sr_update_(
-                    mine, ex.grad_shards_(G["gb"].buckets, ("sr", j)), ms, vs, [h] * nb, np_,
-                    bases, G["streams"], key)
-                ex.gather_params_(G["pb"].buckets)
-            elif G["b8"]:
-                ex = self._kf_ex
-                np_ = ex.reduce_shards_(G["gb"].buckets, ("adam8", j))
-                self._kf_adam8_update(G, ex.grad_shards_(G["gb"].buckets, ("adam8", j)),
-                                      [h] * nb, np_)
-                ex.gather_params_(G["pb"].buckets)
-            elif G["w"] is not None:
-                self._kf_ex.adam_master_step_(G["pb"].buckets, G["gb"].buckets, G["w"], ms, vs,
-                                              [h] * nb)
-            else:
-                self._kf_ex.adam_step_(G["pb"].buckets, G["gb"].buckets, ms, vs, [h] * nb)
+            G["var"].step(j, self._kf_hyper(G, step=G["step"]))
         _finish(self._kf_ex)
         return loss
 
@@ -1170,19 +1255,9 @@ class _ShardedAdam(_Sharded):
         for G, step in zip(self._kf_groups or [], self._kf_steps()):
             if G["m"] is None or step == 0:
                 continue
-            if G["b8"]:  # dequantized: a form that does not depend on world or layout
-                m = self._kf_unshard(G, self._kf_adam8_f32(G, 0))
-                v = self._kf_unshard(G, self._kf_adam8_f32(G, 1))
-            else:
-                m, v = self._kf_unshard(G, G["m"]), self._kf_unshard(G, G["v"])
-            for p in m:
-                out[p] = {"step": step, "exp_avg": m[p], "exp_avg_sq": v[p]}
-            if G["w"] is not None:
-                for p, w in self._kf_unshard(G, G["w"]).items():
-                    out[p]["master"] = w
-            if G["sr"]:
-                for p in m:
-                    out[p]["sr_draw"] = G["draw"]
+            for key, full in G["var"].present().items():
+                for p, t in full.items():
+                    out.setdefault(p, {"step": step})[key] = t
         _finish(self._kf_ex)
         return out
 
@@ -1208,32 +1283,9 @@ class _ShardedAdam(_Sharded):
             if len(steps) > 1:
                 raise ValueError("load_state_buffers: the parameters of one group differ in "
                                  "step: %s" % sorted(steps))
-            ms, vs = self._kf_states(G)
-            if G["b8"]:  # requantized; idempotent on what state_buffers() gave
-                import torch
-                ep = self._kf_adam8_ops()
-                for which, key, codes, scales in ((0, "exp_avg", ms, G["ms"]),
-                                                  (1, "exp_avg_sq", vs, G["vs"])):
-                    full = [torch.zeros(c.numel(), dtype=torch.float32, device=c.device)
-                            for c in codes]
-                    self._kf_reshard(G, full,
-                                     lambda p, key=key: mapping[p][key] if p in mapping else None)
-                    for x, c, s in zip(full, codes, scales):
-                        ep.adam8_quantize_(x, which, c, s)
-            else:
-                self._kf_reshard(G, ms, lambda p: mapping[p]["exp_avg"] if p in mapping else None)
-                self._kf_reshard(G, vs,
-                                 lambda p: mapping[p]["exp_avg_sq"] if p in mapping else None)
-            if G["w"] is not None:
-                self._kf_reshard(G, G["w"], lambda p: mapping.get(p, {}).get("master", p.data))
+            self._kf_states(G)
             G["step"] = steps.pop()
-            if G["sr"]:
-                draws = {int(mapping[p]["sr_draw"]) for p in G["ps"]
-                         if p in mapping and "sr_draw" in mapping[p]}
-                if len(draws) > 1:
-                    raise ValueError("load_state_buffers: the parameters of one group differ in "
-                                     "sr_draw: %s" % sorted(draws))
-                G["draw"] = draws.pop() if draws else G["step"]
+            G["var"].restore(mapping, G["step"])
             if self._kf_gated:
                 self._kf_seed_state(j, G["step"], self.param_groups[G["gi"]]["betas"])
 
@@ -1311,14 +1363,6 @@ class _ShardedLAMB(_ShardedAdam):
     def _kf_new_group(self):
         return dict(super()._kf_new_group(), u=None)
 
-    def _kf_lamb_ops(self):
-        """Where the moments, the norms, the trust ratios and the apply pass
-        run: the exchange's epilogue (collective.Exchange; injectable for CPU
-        tests) or the HIP one."""
-        from .collective import HipEpilogue
-        ep = getattr(self._kf_ex, "epilogue", None)
-        return ep if hasattr(ep, "lamb_moments_") else HipEpilogue()
-
     def _kf_build_sharded(self):
         """Once, with the buckets: the state and update shards (fixed
         addresses), the piece list of every bucket group, and per (dtype,
@@ -1326,7 +1370,7 @@ class _ShardedLAMB(_ShardedAdam):
         the ratios' buffers and the apply plan."""
         import torch
         super()._kf_build_sharded()
-        ex, ep = self._kf_ex, self._kf_lamb_ops()
+        ex, ep = self._kf_ex, self._kf_ops("lamb_moments_")
         by = {}
         for j, G in enumerate(self._kf_groups):
             self._kf_states(G)
@@ -1367,7 +1411,7 @@ class _ShardedLAMB(_ShardedAdam):
         loss = self._kf_closure(closure)
         if self._kf_groups is None:
             self._kf_build_sharded()
-        ex, ep, groups = self._kf_ex, self._kf_lamb_ops(), self._kf_groups
+        ex, ep, groups = self._kf_ex, self._kf_ops("lamb_moments_"), self._kf_groups
         for G in groups:
             _SyncSGD._kf_place(G["ps"], G["gb"])
         if self._kf_gated:
@@ -1377,20 +1421,16 @@ class _ShardedLAMB(_ShardedAdam):
         for j, G in enumerate(groups):
             G["np"] = ex.reduce_shards_(G["gb"].buckets, ("lamb", j))
         for j, G in enumerate(groups):
-            pg = self.param_groups[G["gi"]]  # read at every step: schedulers change them
             G["step"] += 1
-            wd = float(pg["weight_decay"])
-            G["h"] = {"lr": float(pg["lr"]), "betas": tuple(float(b) for b in pg["betas"]),
-                      "eps": float(pg["eps"]), "weight_decay": wd, "decoupled": False,
-                      "step": G["step"], "adapt": wd != 0 or self._kf_always_adapt}
+            h = G["h"] = self._kf_hyper(G, step=G["step"])
+            h["decoupled"] = False
+            h["adapt"] = h["weight_decay"] != 0 or self._kf_always_adapt
             shards = ex.grad_shards_(G["gb"].buckets, ("lamb", j))
             hs = [G["h"]] * len(shards)
             if G["w"] is not None:
                 ep.lamb_master_moments_(shards, G["w"], G["m"], G["v"], G["u"], hs, G["np"])
             else:
-                q = [b.numel() // ex.world for b in G["pb"].buckets]
-                mine = [b[ex.rank * n:(ex.rank + 1) * n] for b, n in zip(G["pb"].buckets, q)]
-                ep.lamb_moments_(mine, shards, G["m"], G["v"], G["u"], hs, G["np"])
+                ep.lamb_moments_(self._kf_mine(G), shards, G["m"], G["v"], G["u"], hs, G["np"])
         for L in self._kf_lamb:
             L["norm"].run("sq", out=L["out"])
             ex.gather_doubles_(L["out"][:2 * L["T"]], L["sq"])
@@ -1409,7 +1449,7 @@ class _ShardedLAMB(_ShardedAdam):
         for the step states, E the gated moments, F the norms of (p, u), G the
         gated trust ratios and apply pass, H the parameters' all-gather.
         Queued; nothing waits for the verdict."""
-        ex, ep, groups = self._kf_ex, self._kf_lamb_ops(), self._kf_groups
+        ex, ep, groups = self._kf_ex, self._kf_ops("lamb_moments_"), self._kf_groups
         gate, states = self._kf_gate, self._kf_gstates
         hs = self._kf_gate_verdict(gate_lr=1.0)
         for j, (G, h) in enumerate(zip(groups, hs)):
@@ -1420,10 +1460,8 @@ class _ShardedLAMB(_ShardedAdam):
                 ep.lamb_master_moments_gated_(shards, G["w"], G["m"], G["v"], G["u"], G["h"], gate,
                                               states, j, G["np"])
             else:
-                q = [b.numel() // ex.world for b in G["pb"].buckets]
-                mine = [b[ex.rank * n:(ex.rank + 1) * n] for b, n in zip(G["pb"].buckets, q)]
-                ep.lamb_moments_gated_(mine, shards, G["m"], G["v"], G["u"], G["h"], gate, states,
-                                       j, G["np"])
+                ep.lamb_moments_gated_(self._kf_mine(G), shards, G["m"], G["v"], G["u"], G["h"],
+                                       gate, states, j, G["np"])
         for L in self._kf_lamb:
             L["norm"].run("sq", out=L["out"])  # unconditional: read-only
             ex.gather_doubles_(L["out"][:2 * L["T"]], L["sq"])
