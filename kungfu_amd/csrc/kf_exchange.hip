@@ -57,6 +57,8 @@
 #include <thread>
 #include <vector>
 
+#include "kf_exchange_plan.hpp"
+#include "kf_update_batch.hpp"
 #include "kungfu_amd.h"
 
 // kf_session.hip (library-internal)
@@ -223,7 +225,8 @@ ncclRedOp_t nccl_op(KungFu_Op op)
     }
 }
 
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+using kf::align_up;
+using kf::off16;
 
 // ---------------------------------------------------------------------------
 // the built-in transport: librccl
@@ -345,28 +348,18 @@ struct NamedTask {
     void *arg        = nullptr;
 };
 
-// The optimizer update on the shards (kf_exchange_sgd_batch,
-// kf_exchange_adam_batch, kf_exchange_adam_master_batch): the tables, one
-// entry per bucket, and the batched kernel that takes them. Exactly one of
-// sgd / adam is set.
+// The optimizer update on the shards (kf_exchange_sgd_batch, _adam_batch,
+// _adam_master_batch, _adam_gated_batch): the tables, one entry per bucket,
+// the hypers (exactly one of sgd / adam), the gate of a gated step (adam is
+// then ONE hyper for every bucket) and the batched kernel that takes them.
 struct ShardUpdate {
     void *const *params;
     void *const *state;   // this rank's momentum (SGD) or exp_avg (Adam) shards
     void *const *state2;  // Adam: this rank's exp_avg_sq shards
     const kf_sgd_hyper *sgd;
     const kf_adam_hyper *adam;
-    void *const *master = nullptr;  // Adam on 16-bit buckets: this rank's fp32 master shards
-    // The gated step (kf_exchange_reduce_shards_batch, kf_exchange_adam_gated_batch)
-    // runs the schedule in two calls with the verdict between them:
-    //   kReduceOnly  phase 1 and the rank-order folds, no update; *np_out = what
-    //                the update must still divide by
-    //   kUpdateOnly  the gated update with np = np_in, then phase 3; adam is ONE
-    //                hyper for every bucket
-    enum { kWhole = 0, kReduceOnly = 1, kUpdateOnly = 2 };
-    int part                   = kWhole;
-    int *np_out                = nullptr;
-    int np_in                  = 0;
-    const kf_step_gate *gate   = nullptr;
+    void *const *master         = nullptr;  // Adam on 16-bit buckets: this rank's fp32 master shards
+    const kf_step_gate *gate    = nullptr;
     const kf_step_state *gstate = nullptr;
 
     const char *kernel() const
@@ -379,23 +372,22 @@ struct ShardUpdate {
     int run(void *const *ps, const void *const *gs, const size_t *cnts, int b0, int n,
             KungFu_Datatype dt, int np, hipStream_t s) const
     {
+        auto at        = [&](void *const *tab) { return tab ? tab + b0 : nullptr; };
+        void *const *m = at(state), *const *v = at(state2), *const *w = at(master);
+        int rc;
         if (gate && master) {
-            return kf_adam_master_update_batch_gated(ps, gs, master + b0, state + b0, state2 + b0,
-                                                     cnts, n, dt, np, adam, gate, gstate, s);
+            rc = kf_adam_master_update_batch_gated(ps, gs, w, m, v, cnts, n, dt, np, adam, gate,
+                                                   gstate, s);
+        } else if (gate) {
+            rc = kf_adam_update_batch_gated(ps, gs, m, v, cnts, n, dt, np, adam, gate, gstate, s);
+        } else if (sgd) {
+            rc = kf_sgd_update_batch(ps, gs, m, cnts, n, dt, np, sgd + b0, s);
+        } else if (master) {
+            rc = kf_adam_master_update_batch(ps, gs, w, m, v, cnts, n, dt, np, adam + b0, s);
+        } else {
+            rc = kf_adam_update_batch(ps, gs, m, v, cnts, n, dt, np, adam + b0, s);
         }
-        if (gate) {
-            return kf_adam_update_batch_gated(ps, gs, state + b0, state2 + b0, cnts, n, dt, np, adam,
-                                              gate, gstate, s);
-        }
-        if (sgd) {
-            return kf_sgd_update_batch(ps, gs, state ? state + b0 : nullptr, cnts, n, dt, np,
-                                       sgd + b0, s);
-        }
-        if (master) {
-            return kf_adam_master_update_batch(ps, gs, master + b0, state + b0, state2 + b0, cnts,
-                                               n, dt, np, adam + b0, s);
-        }
-        return kf_adam_update_batch(ps, gs, state + b0, state2 + b0, cnts, n, dt, np, adam + b0, s);
+        return rc == KF_OK ? KF_OK : fail(rc, std::string(kernel()) + ": " + kf_last_error());
     }
 };
 
@@ -477,19 +469,7 @@ struct kf_exchange {
                                      std::to_string(code) + ")");
     }
     int ensure_ws(size_t bytes, hipStream_t s);
-    void release_ws(hipStream_t s);
-    // sma_alpha != nullptr: SMA, sends = the variables, recvs = the sum workspaces,
-    // each variable blended once its sum is gathered
-    // phases: which of the three to run (kAll; the hierarchical all-reduce
-    // runs 1+2, its cross-host step, then 3)
-    // upd != nullptr: the sharded optimizer step (kf_exchange_sgd_batch,
-    // kf_exchange_adam_batch), sends == recvs = the gradient buckets, average
-    // set; the update runs on the shards in phase 2 and phase 3 gathers the
-    // parameter buckets
-    int batch(const void *const *sends, void *const *recvs, const size_t *counts, int nb,
-              KungFu_Datatype dt, KungFu_Op op, int average, int algo, hipStream_t s,
-              const double *sma_alpha = nullptr, int phases = 7,
-              const ShardUpdate *upd = nullptr);
+    void release_ws(hipStream_t s);  // the batch calls themselves: Schedule and its drivers, below
     int hier(kf_session_t *cross, const void *send, void *recv, size_t count, KungFu_Datatype dt,
              KungFu_Op op, int average, int algo, const std::string &name, hipStream_t s);
     kf_exchange *split(int color, int key, int *status);  // caller holds mu
@@ -550,24 +530,26 @@ void kf_exchange::release_ws(hipStream_t s)
     }
 }
 
+static int check_algo(int algo)
+{
+    const bool known = algo >= KF_ALGO_AUTO && algo <= KF_ALGO_REDUCE_SCATTER_AVG;
+    return known ? KF_OK : fail(KF_ERR_ARG, "unknown algo");
+}
+
 // Resolve KF_ALGO_AUTO; KF_ERR_* for a combination that cannot run.
 static int resolve_algo(int algo, KungFu_Datatype dt, KungFu_Op op, int world, int *out)
 {
+    if (check_algo(algo) != KF_OK) return KF_ERR_ARG;
     ncclDataType_t t;
     const bool rs_ok = nccl_type(dt, &t);
+    *out = algo;
     if (algo == KF_ALGO_REDUCE_SCATTER || algo == KF_ALGO_REDUCE_SCATTER_AVG) {
-        if (!rs_ok) return fail(KF_ERR_DTYPE, "no reduce-scatter type for this dtype");
-        *out = algo;
-        return KF_OK;
+        return rs_ok ? KF_OK : fail(KF_ERR_DTYPE, "no reduce-scatter type for this dtype");
     }
     if (algo == KF_ALGO_ALL_TO_ALL) {
-        if (world > KF_MAX_INPUTS) {
-            return fail(KF_ERR_ARG, "all-to-all fold supports at most 16 ranks");
-        }
-        *out = algo;
-        return KF_OK;
+        if (world <= KF_MAX_INPUTS) return KF_OK;
+        return fail(KF_ERR_ARG, "all-to-all fold supports at most 16 ranks");
     }
-    if (algo != KF_ALGO_AUTO) return fail(KF_ERR_ARG, "unknown algo");
     (void)op;  // MIN/MAX through RCCL differ from std::min/max only on NaN inputs
     const bool own_semantics = dt == KungFu_FLOAT16 || dt == KungFu_BFLOAT16;
     if (world <= KF_MAX_INPUTS && (own_semantics || !rs_ok)) {
@@ -580,209 +562,216 @@ static int resolve_algo(int algo, KungFu_Datatype dt, KungFu_Op op, int world, i
     return KF_OK;
 }
 
-int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_t *counts,
-                       int nb, KungFu_Datatype dt, KungFu_Op op, int average, int algo,
-                       hipStream_t s, const double *sma_alpha, int phases, const ShardUpdate *upd)
+// One group of collectives: each(b), for b in [b0, b1), is a transport status;
+// `what` names a failure.
+template <class F>
+static int grouped(const kf_exchange &x, int b0, int b1, const char *what, F each)
 {
-    const int sz = tsize(dt);
-    const int W = world, r = rank;
-    const bool sma = sma_alpha != nullptr;
-    const bool reduce_only = upd && upd->part == ShardUpdate::kReduceOnly;
-    const bool update_only = upd && upd->part == ShardUpdate::kUpdateOnly;
-    if (W == 1 && builtin && reduce_only) {  // a single peer: the buckets are the sums
-        *upd->np_out = 1;
-        return KF_OK;
+    const int e0 = x.T->group_start(x.comm);
+    if (e0 != 0) return x.tfail(e0, "group_start");
+    int rc = KF_OK;
+    for (int b = b0; b < b1 && rc == KF_OK; ++b) {
+        const int e = each(b);
+        if (e != 0) rc = x.tfail(e, what);
     }
-    if (W == 1 && builtin && upd) {  // a single peer: the update over the whole buckets
-        const int rc = upd->run(upd->params, sends, counts, 0, nb, dt, update_only ? upd->np_in : 1, s);
-        if (rc != KF_OK) return fail(rc, std::string(upd->kernel()) + ": " + kf_last_error());
-        return KF_OK;
-    }
-    if (W == 1 && builtin) {  // a single peer: the sum is the bucket, x / 1 == x
-        for (int b = 0; b < nb && (phases & 1); ++b) {
-            if (counts[b] && sends[b] != recvs[b]) {
-                KF_HIP(hipMemcpyAsync(recvs[b], sends[b], counts[b] * sz, hipMemcpyDeviceToDevice, s));
-            }
-        }
-        if (sma) {
-            std::vector<void *> vv(nb);
-            for (int b = 0; b < nb; ++b) vv[b] = const_cast<void *>(sends[b]);
-            const int rc = kf_sma_blend_batch(vv.data(), const_cast<const void *const *>(recvs),
-                                              counts, nb, dt, W, *sma_alpha, s);
-            if (rc != KF_OK) return fail(rc, "kf_sma_blend_batch");
-        }
-        return KF_OK;
-    }
-    int a  = 0;
-    int rc = resolve_algo(algo, dt, op, W, &a);
-    if (rc != KF_OK) return rc;
-    if (a == KF_ALGO_REDUCE_SCATTER_AVG && !average) a = KF_ALGO_REDUCE_SCATTER;
-    // the /np inside the collective (ncclAvg): no shard epilogue
-    const KungFu_Op rs_op =
-        a == KF_ALGO_REDUCE_SCATTER_AVG ? static_cast<KungFu_Op>(KF_TRANSPORT_OP_AVG) : op;
-    if (reduce_only) *upd->np_out = a == KF_ALGO_REDUCE_SCATTER ? W : 0;
+    const int e1 = x.T->group_end(x.comm);
+    return rc != KF_OK ? rc : (e1 != 0 ? x.tfail(e1, "group_end") : KF_OK);
+}
 
-    // workspace: received shards (all-to-all) and gathered tails
-    std::vector<size_t> wsoff(nb, 0), toff(nb, 0);
-    size_t need = 0;
-    for (int b = 0; b < nb && (phases & 3) && !update_only; ++b) {
-        const size_t q = counts[b] / W, t = counts[b] % W;
-        if (a == KF_ALGO_ALL_TO_ALL && q) {
-            wsoff[b] = need;
-            need += align_up(q * W * sz, 256);
-        }
-        if (t) {
-            toff[b] = need;
-            need += align_up(t * W * sz, 256);
-        }
-    }
-    if (need) {
-        rc = ensure_ws(need, s);
+// One batch call's schedule: what is resolved once, and the three phases over
+// the buckets [b0, b1). Collectives go on the caller's stream s, the
+// element-wise work on the stream it is given.
+struct Schedule {
+    kf_exchange &x;
+    const size_t *counts;
+    const int nb;
+    const KungFu_Datatype dt;
+    const KungFu_Op op;
+    const hipStream_t s;
+    const size_t W = x.world, r = x.rank, sz = tsize(dt);
+    int a           = KF_ALGO_AUTO;  // resolve()
+    KungFu_Op rs_op = op;  // the reduce-scatter's: AVG under KF_ALGO_REDUCE_SCATTER_AVG
+    kf::Workspace ws;      // reserve(): received shards (all-to-all) and gathered tails
+    char *wsp = nullptr;
+    std::vector<const void *> ins;  // the tables of a batched launch
+    std::vector<void *> outs;
+    std::vector<size_t> cnts;
+
+    bool alone() const { return W == 1 && x.builtin; }  // the built-in transport's single peer
+    size_t q(int b) const { return counts[b] / W; }
+    size_t t(int b) const { return counts[b] % W; }
+    // this rank's shard of bucket b, which starts at `bucket`, and the bucket's tail
+    template <class C> C *shard(C *bucket, int b) const { return bucket + r * q(b) * sz; }
+    template <class C> C *tail(C *bucket, int b) const { return bucket + q(b) * W * sz; }
+    // what an update of the shards must still divide by: a plain reduce-scatter
+    // leaves the sum, the fold and ncclAvg have divided
+    int np() const { return a == KF_ALGO_REDUCE_SCATTER ? x.world : 0; }
+
+    int resolve(int algo, int average)
+    {
+        const int rc = resolve_algo(algo, dt, op, x.world, &a);
         if (rc != KF_OK) return rc;
+        if (a == KF_ALGO_REDUCE_SCATTER_AVG && !average) a = KF_ALGO_REDUCE_SCATTER;
+        if (a == KF_ALGO_REDUCE_SCATTER_AVG) rs_op = static_cast<KungFu_Op>(KF_TRANSPORT_OP_AVG);
+        return KF_OK;
     }
-    char *wsp = static_cast<char *>(ws);
-
-    auto group_end = [&](int status) -> int {
-        const int e = T->group_end(comm);
-        if (status != KF_OK) return status;
-        if (e != 0) return tfail(e, "group_end");
-        return KF_OK;
-    };
-
-    // phase 1: every bucket's reduce-scatter (or all-to-all) and tail gather
-    auto phase1 = [&](int b0, int b1) -> int {
-        const int e0 = T->group_start(comm);
-        if (e0 != 0) return tfail(e0, "group_start");
-        int rc1 = KF_OK;
-        for (int b = b0; b < b1 && rc1 == KF_OK; ++b) {
-            const size_t q = counts[b] / W, t = counts[b] % W;
-            const char *snd = static_cast<const char *>(sends[b]);
-            char *rcv       = static_cast<char *>(recvs[b]);
-            int e           = 0;
-            if (q && (a == KF_ALGO_REDUCE_SCATTER || a == KF_ALGO_REDUCE_SCATTER_AVG)) {
-                e = T->reduce_scatter(snd, rcv + r * q * sz, q, dt, rs_op, comm, s);
-            } else if (q) {
-                e = T->all_to_all(snd, wsp + wsoff[b], q * sz, comm, s);
-            }
-            if (e == 0 && t) {
-                e = T->all_gather(snd + q * W * sz, wsp + toff[b], t * sz, comm, s);
-            }
-            if (e != 0) rc1 = tfail(e, "phase-1 collective");
-        }
-        return group_end(rc1);
-    };
-
-    // phase 2: the element-wise work, batched over the buckets
-    auto phase2 = [&](int b0, int b1, hipStream_t cs) -> int {
-        std::vector<const void *> ins;
-        std::vector<void *> outs;
-        std::vector<size_t> cnts;
-        if (a == KF_ALGO_REDUCE_SCATTER && average && !upd) {
-            for (int b = b0; b < b1; ++b) {
-                const size_t q = counts[b] / W;
-                if (!q) continue;
-                char *sh = static_cast<char *>(recvs[b]) + r * q * sz;
-                ins.push_back(sh);
-                outs.push_back(sh);
-                cnts.push_back(q);
-            }
-            if (!outs.empty()) {
-                const int e = kf_bucket_reduce_batch(ins.data(), 1, outs.data(), cnts.data(),
-                                                     static_cast<int>(outs.size()), dt, KungFu_SUM,
-                                                     W, cs);
-                if (e != KF_OK) return fail(e, "shard /np epilogue");
-            }
-            ins.clear();
-            outs.clear();
-            cnts.clear();
-        }
-        for (int b = b0; b < b1 && !update_only; ++b) {  // rank-order folds: shards and tails
-            const size_t q = counts[b] / W, t = counts[b] % W;
-            char *rcv      = static_cast<char *>(recvs[b]);
-            if (q && a == KF_ALGO_ALL_TO_ALL) {
-                for (int j = 0; j < W; ++j) ins.push_back(wsp + wsoff[b] + j * q * sz);
-                outs.push_back(rcv + r * q * sz);
-                cnts.push_back(q);
-            }
-            if (t) {
-                for (int j = 0; j < W; ++j) ins.push_back(wsp + toff[b] + j * t * sz);
-                outs.push_back(rcv + q * W * sz);
-                cnts.push_back(t);
-            }
-        }
-        if (!outs.empty()) {
-            const int e = kf_bucket_reduce_batch(ins.data(), W, outs.data(), cnts.data(),
-                                                 static_cast<int>(outs.size()), dt, op,
-                                                 average ? W : 0, cs);
-            if (e != KF_OK) return fail(e, "rank-order fold of the received shards");
-        }
-        if (upd && !reduce_only) {
-            // the update on this rank's shard of every bucket; after a plain
-            // reduce-scatter the shard holds the sum and the kernel divides
-            // (the shard is read once, no /np pass); the fold and ncclAvg
-            // have divided already (a gated update is told which)
-            std::vector<void *> ps;
-            std::vector<const void *> gs;
-            cnts.clear();
-            for (int b = b0; b < b1; ++b) {
-                const size_t q = counts[b] / W;
-                ps.push_back(static_cast<char *>(upd->params[b]) + r * q * sz);
-                gs.push_back(static_cast<const char *>(recvs[b]) + r * q * sz);
-                cnts.push_back(q);
-            }
-            const int np = update_only ? upd->np_in : (a == KF_ALGO_REDUCE_SCATTER ? W : 0);
-            const int e  = upd->run(ps.data(), gs.data(), cnts.data(), b0, b1 - b0, dt, np, cs);
-            if (e != KF_OK) return fail(e, std::string(upd->kernel()) + ": " + kf_last_error());
-        }
-        return KF_OK;
-    };
-
-    // phase 3: in-place all-gather of every reduced shard
-    auto phase3 = [&](int b0, int b1) -> int {
-        const int e0 = T->group_start(comm);
-        if (e0 != 0) return tfail(e0, "group_start");
-        int rc3 = KF_OK;
-        for (int b = b0; b < b1 && rc3 == KF_OK; ++b) {
-            const size_t q = counts[b] / W;
-            if (!q) continue;
-            char *rcv   = static_cast<char *>(upd ? upd->params[b] : recvs[b]);
-            const int e = T->all_gather(rcv + r * q * sz, rcv, q * sz, comm, s);
-            if (e != 0) rc3 = tfail(e, "all_gather");
-        }
-        return group_end(rc3);
-    };
-
-    // SMA: v = (1 - alpha) v + alpha (sum / world), once the sum is gathered;
-    // the buckets' blends in one batched launch
-    auto blend = [&](int b0, int b1, hipStream_t cs) -> int {
-        if (!sma || b1 <= b0) return KF_OK;
-        std::vector<void *> vv(b1 - b0);
-        for (int b = b0; b < b1; ++b) vv[b - b0] = const_cast<void *>(sends[b]);
-        const int e = kf_sma_blend_batch(vv.data(), const_cast<const void *const *>(recvs + b0),
-                                         counts + b0, b1 - b0, dt, W, *sma_alpha, cs);
-        if (e != KF_OK) return fail(e, "kf_sma_blend_batch");
-        return KF_OK;
-    };
-
-    const int G = phases == 7 && !upd ? std::min(groups, nb) : 1;
-    if (G <= 1) {
-        Marks *mk = timing ? take_marks() : nullptr;
-        auto mark = [&](int k) {
-            if (mk) (void)hipEventRecord(mk->e[k], s);
-        };
-        mark(0);
-        if (phases & 1) rc = phase1(0, nb);
-        mark(1);
-        if (rc == KF_OK && (phases & 2)) rc = phase2(0, nb, s);
-        mark(2);
-        if (rc == KF_OK && (phases & 4)) rc = phase3(0, nb);
-        mark(3);
-        if (rc == KF_OK && phases == 7) rc = blend(0, nb, s);
-        mark(4);
-        if (need) release_ws(s);  // whatever ran reads the workspace in stream order
+    int reserve()
+    {
+        ws = kf::plan_workspace(counts, nb, W, sz, a == KF_ALGO_ALL_TO_ALL);
+        const int rc = ws.bytes ? x.ensure_ws(ws.bytes, s) : KF_OK;
+        wsp          = static_cast<char *>(x.ws);
         return rc;
     }
-    if (timing) ++untimed_calls;
+    // phase 1: every bucket's reduce-scatter (or all-to-all) and tail gather
+    int scatter(const void *const *sends, void *const *recvs, int b0, int b1)
+    {
+        return grouped(x, b0, b1, "phase-1 collective", [&](int b) {
+            const char *snd = static_cast<const char *>(sends[b]);
+            char *mine      = shard(static_cast<char *>(recvs[b]), b);
+            int e           = 0;
+            if (q(b) && a == KF_ALGO_ALL_TO_ALL) {
+                e = x.T->all_to_all(snd, wsp + ws.shards[b], q(b) * sz, x.comm, s);
+            } else if (q(b)) {
+                e = x.T->reduce_scatter(snd, mine, q(b), dt, rs_op, x.comm, s);
+            }
+            if (e != 0 || !t(b)) return e;
+            return x.T->all_gather(tail(snd, b), wsp + ws.tails[b], t(b) * sz, x.comm, s);
+        });
+    }
+    // phase 2: the element-wise work, each kind batched over the buckets
+    int launch(int k, KungFu_Op o, int div, hipStream_t cs, const char *what)
+    {
+        const int n = static_cast<int>(outs.size());
+        int e       = KF_OK;
+        if (n) {
+            e = kf_bucket_reduce_batch(ins.data(), k, outs.data(), cnts.data(), n, dt, o, div, cs);
+        }
+        ins.clear(), outs.clear(), cnts.clear();
+        return e == KF_OK ? KF_OK : fail(e, what);
+    }
+    // after a plain reduce-scatter: the shards' /np
+    int divide_shards(void *const *recvs, int b0, int b1, hipStream_t cs)
+    {
+        for (int b = b0; b < b1; ++b) {
+            if (!q(b)) continue;
+            outs.push_back(shard(static_cast<char *>(recvs[b]), b));
+            ins.push_back(outs.back());
+            cnts.push_back(q(b));
+        }
+        return launch(1, KungFu_SUM, x.world, cs, "shard /np epilogue");
+    }
+    // the rank-order folds of the received shards and of the tails; div: the
+    // /np fused into them
+    int fold(void *const *recvs, int div, int b0, int b1, hipStream_t cs)
+    {
+        for (int b = b0; b < b1; ++b) {
+            char *rcv = static_cast<char *>(recvs[b]);
+            if (q(b) && a == KF_ALGO_ALL_TO_ALL) {
+                for (size_t j = 0; j < W; ++j) ins.push_back(wsp + ws.shards[b] + j * q(b) * sz);
+                outs.push_back(shard(rcv, b));
+                cnts.push_back(q(b));
+            }
+            if (t(b)) {
+                for (size_t j = 0; j < W; ++j) ins.push_back(wsp + ws.tails[b] + j * t(b) * sz);
+                outs.push_back(tail(rcv, b));
+                cnts.push_back(t(b));
+            }
+        }
+        return launch(x.world, op, div, cs, "rank-order fold of the received shards");
+    }
+    // the optimizer update on this rank's shard of every bucket: the shard is
+    // read once, so after a plain reduce-scatter the kernel divides by np and
+    // there is no /np pass
+    int update(const ShardUpdate &u, void *const *grads, int np, int b0, int b1, hipStream_t cs)
+    {
+        for (int b = b0; b < b1; ++b) {
+            outs.push_back(shard(static_cast<char *>(u.params[b]), b));
+            ins.push_back(shard(static_cast<const char *>(grads[b]), b));
+            cnts.push_back(q(b));
+        }
+        const int rc = u.run(outs.data(), ins.data(), cnts.data(), b0, b1 - b0, dt, np, cs);
+        ins.clear(), outs.clear(), cnts.clear();
+        return rc;
+    }
+    // phase 3: in-place all-gather of every reduced shard
+    int gather(void *const *bufs, int b0, int b1)
+    {
+        return grouped(x, b0, b1, "all_gather", [&](int b) {
+            char *buf = static_cast<char *>(bufs[b]);
+            return q(b) ? x.T->all_gather(shard(buf, b), buf, q(b) * sz, x.comm, s) : 0;
+        });
+    }
+    // An un-pipelined call: its four steps (`nothing` where it has none) in
+    // order until one fails, the five timing marks at their boundaries (all
+    // five: kf_exchange_phase_times waits for the last), and the workspace
+    // released after whatever ran (it is read in stream order).
+    template <class... P> int serial(P... step)
+    {
+        static_assert(sizeof...(P) == 4, "phase 1, phase 2, phase 3, the blend: five marks");
+        kf_exchange::Marks *mk = x.timing ? x.take_marks() : nullptr;
+        int k = 0, rc = KF_OK;
+        auto mark = [&] {
+            if (mk) (void)hipEventRecord(mk->e[k++], s);
+        };
+        mark();
+        ((rc = rc == KF_OK ? step() : rc, mark()), ...);
+        if (ws.bytes) x.release_ws(s);
+        return rc;
+    }
+};
+
+static int nothing() { return KF_OK; }
+static int hip_ok(hipError_t e, const char *what)
+{
+    return e == hipSuccess ? KF_OK : hip_fail(e, what);
+}
+
+// SMA: the variables (they are the sends) blended with the gathered sums,
+// v = (1 - alpha) v + alpha (sum / world); the buckets' blends in one batched
+// launch
+struct Sma {
+    void *const *vars;
+    double alpha;
+};
+static int sma_blend(const Schedule &sc, const Sma *sma, void *const *sums, int b0, int b1,
+                     hipStream_t cs)
+{
+    if (!sma || b1 <= b0) return KF_OK;
+    const int e = kf_sma_blend_batch(sma->vars + b0, sums + b0, sc.counts + b0, b1 - b0, sc.dt,
+                                     sc.x.world, sma->alpha, cs);
+    return e == KF_OK ? KF_OK : fail(e, "kf_sma_blend_batch");
+}
+
+// The drivers, one per use of the phases; the caller holds x.mu.
+//
+// The all-reduce, with the SMA blend where asked: the only one that pipelines.
+static int all_reduce(kf_exchange &x, const void *const *sends, void *const *recvs,
+                      const size_t *counts, int nb, KungFu_Datatype dt, KungFu_Op op, int average,
+                      int algo, hipStream_t s, const Sma *sma = nullptr)
+{
+    Schedule sc{x, counts, nb, dt, op, s};
+    if (sc.alone()) {  // the sum is the bucket, x / 1 == x
+        for (int b = 0; b < nb; ++b) {
+            if (!counts[b] || sends[b] == recvs[b]) continue;
+            KF_HIP(hipMemcpyAsync(recvs[b], sends[b], counts[b] * sc.sz, hipMemcpyDeviceToDevice, s));
+        }
+        return sma_blend(sc, sma, recvs, 0, nb, s);
+    }
+    int rc = sc.resolve(algo, average);
+    if (rc == KF_OK) rc = sc.reserve();
+    if (rc != KF_OK) return rc;
+    const bool divide = sc.a == KF_ALGO_REDUCE_SCATTER && average;
+    auto reduce = [&](int b0, int b1, hipStream_t cs) {
+        const int e = divide ? sc.divide_shards(recvs, b0, b1, cs) : KF_OK;
+        return e == KF_OK ? sc.fold(recvs, average ? x.world : 0, b0, b1, cs) : e;
+    };
+    if (std::min(x.groups, nb) <= 1) {
+        return sc.serial([&] { return sc.scatter(sends, recvs, 0, nb); },
+                         [&] { return reduce(0, nb, s); },
+                         [&] { return sc.gather(recvs, 0, nb); },
+                         [&] { return sma_blend(sc, sma, recvs, 0, nb, s); });
+    }
+    if (x.timing) ++x.untimed_calls;
 
     // pipelined: groups of consecutive buckets with about equal bytes;
     //   caller stream s: p1(0) p1(1) [wait p2(0)] p3(0) p1(2) [wait p2(1)] p3(1) ...
@@ -790,51 +779,37 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
     // every wait is on an event recorded earlier on the other stream, so
     // neither stream can wait on the other in a cycle; the collectives keep
     // the same order on every rank
-    std::vector<int> gb(1, 0);  // group g = buckets [gb[g], gb[g+1])
-    {
-        size_t total = 0, acc = 0;
-        for (int b = 0; b < nb; ++b) total += counts[b];
-        for (int b = 0; b < nb; ++b) {
-            acc += counts[b];
-            const int left = nb - b - 1, want = G - static_cast<int>(gb.size());
-            if (want > 0 && left >= want && acc * G >= total * gb.size()) gb.push_back(b + 1);
-        }
-        gb.push_back(nb);
-    }
-    const int ng = static_cast<int>(gb.size()) - 1;
-    if (!comp) KF_HIP(hipStreamCreateWithFlags(&comp, hipStreamNonBlocking));
-    while (pev.size() < static_cast<size_t>(3 * ng + 1)) {
+    const std::vector<int> gb = kf::split_groups(counts, nb, x.groups);
+    const int ng              = static_cast<int>(gb.size()) - 1;
+    if (!x.comp) KF_HIP(hipStreamCreateWithFlags(&x.comp, hipStreamNonBlocking));
+    while (x.pev.size() < static_cast<size_t>(3 * ng + 1)) {
         hipEvent_t e;
         KF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        pev.push_back(e);
+        x.pev.push_back(e);
     }
-    auto e1 = [&](int g) { return pev[3 * g]; };
-    auto e2 = [&](int g) { return pev[3 * g + 1]; };
-    auto e3 = [&](int g) { return pev[3 * g + 2]; };
-    hipEvent_t e_end = pev[3 * ng];
+    hipStream_t comp = x.comp;
+    auto ev = [&](int g, int phase) { return x.pev[3 * g + phase - 1]; };  // group g's p1, p2, p3
+    hipEvent_t e_end = x.pev[3 * ng];
     bool comp_used   = false;
     // every failure below leaves through the same exit (no early return), so
     // the folds already queued on comp are joined and the workspace released
-    auto hip_ok = [&](hipError_t e, const char *what) -> int {
-        return e == hipSuccess ? KF_OK : hip_fail(e, what);
-    };
     auto finish = [&](int g) -> int {  // gather group g, then blend it
-        int f = hip_ok(hipStreamWaitEvent(s, e2(g), 0), "hipStreamWaitEvent(p2)");
-        if (f == KF_OK) f = phase3(gb[g], gb[g + 1]);
+        int f = hip_ok(hipStreamWaitEvent(s, ev(g, 2), 0), "hipStreamWaitEvent(p2)");
+        if (f == KF_OK) f = sc.gather(recvs, gb[g], gb[g + 1]);
         if (f != KF_OK || !sma) return f;
-        f = hip_ok(hipEventRecord(e3(g), s), "hipEventRecord(p3)");
-        if (f == KF_OK) f = hip_ok(hipStreamWaitEvent(comp, e3(g), 0), "hipStreamWaitEvent(p3)");
-        if (f == KF_OK) f = blend(gb[g], gb[g + 1], comp);
+        f = hip_ok(hipEventRecord(ev(g, 3), s), "hipEventRecord(p3)");
+        if (f == KF_OK) f = hip_ok(hipStreamWaitEvent(comp, ev(g, 3), 0), "hipStreamWaitEvent(p3)");
+        if (f == KF_OK) f = sma_blend(sc, sma, recvs, gb[g], gb[g + 1], comp);
         return f;
     };
     for (int g = 0; g < ng && rc == KF_OK; ++g) {
-        rc = phase1(gb[g], gb[g + 1]);
-        if (rc == KF_OK) rc = hip_ok(hipEventRecord(e1(g), s), "hipEventRecord(p1)");
-        if (rc == KF_OK) rc = hip_ok(hipStreamWaitEvent(comp, e1(g), 0), "hipStreamWaitEvent(p1)");
+        rc = sc.scatter(sends, recvs, gb[g], gb[g + 1]);
+        if (rc == KF_OK) rc = hip_ok(hipEventRecord(ev(g, 1), s), "hipEventRecord(p1)");
+        if (rc == KF_OK) rc = hip_ok(hipStreamWaitEvent(comp, ev(g, 1), 0), "hipStreamWaitEvent(p1)");
         if (rc != KF_OK) break;
         comp_used = true;
-        rc = phase2(gb[g], gb[g + 1], comp);
-        if (rc == KF_OK) rc = hip_ok(hipEventRecord(e2(g), comp), "hipEventRecord(p2)");
+        rc = reduce(gb[g], gb[g + 1], comp);
+        if (rc == KF_OK) rc = hip_ok(hipEventRecord(ev(g, 2), comp), "hipEventRecord(p2)");
         if (rc == KF_OK && g > 0) rc = finish(g - 1);
     }
     if (rc == KF_OK) rc = finish(ng - 1);
@@ -843,12 +818,83 @@ int kf_exchange::batch(const void *const *sends, void *const *recvs, const size_
     // workspace nor the buckets are reused under them; if even that join
     // cannot be queued, wait for comp here
     if (comp_used && (sma || rc != KF_OK)) {
-        if (hipEventRecord(e_end, comp) != hipSuccess || hipStreamWaitEvent(s, e_end, 0) != hipSuccess) {
+        if (hipEventRecord(e_end, comp) != hipSuccess ||
+            hipStreamWaitEvent(s, e_end, 0) != hipSuccess) {
             (void)hipStreamSynchronize(comp);
         }
     }
-    if (need) release_ws(s);
+    if (sc.ws.bytes) x.release_ws(s);
     return rc;
+}
+
+// Phases 1 and 2: this rank's shard of every recv, and every tail, holds the
+// sum. fused_average: the division by the world is done where the fold or
+// ncclAvg can fuse it, and only there; a plain reduce-scatter's shard stays
+// the sum. np is what the caller must still divide by (-1 where the call is
+// refused before that is known). An empty call queues nothing and reports a
+// non-empty one's np.
+struct Reduced {
+    int rc, np;
+};
+static Reduced reduce_to_shards(kf_exchange &x, const void *const *sends, void *const *recvs,
+                                const size_t *counts, int nb, KungFu_Datatype dt, KungFu_Op op,
+                                int fused_average, int algo, hipStream_t s)
+{
+    Schedule sc{x, counts, nb, dt, op, s};
+    if (sc.alone()) {  // a single peer: the buckets are the sums
+        return {all_reduce(x, sends, recvs, counts, nb, dt, op, 0, algo, s), 1};
+    }
+    int rc = sc.resolve(algo, fused_average);
+    if (rc != KF_OK) return {rc, -1};
+    if (nb > 0) rc = sc.reserve();
+    if (nb > 0 && rc == KF_OK) {
+        const int div = fused_average ? x.world : 0;
+        rc = sc.serial([&] { return sc.scatter(sends, recvs, 0, nb); },
+                       [&] { return sc.fold(recvs, div, 0, nb, s); }, nothing, nothing);
+    }
+    return {rc, sc.np()};
+}
+
+// Phase 3 alone: every rank's shard of every bucket to all ranks, in place.
+static int gather_shards(kf_exchange &x, void *const *bufs, const size_t *counts, int nb,
+                         KungFu_Datatype dt, hipStream_t s)
+{
+    Schedule sc{x, counts, nb, dt, KungFu_SUM, s};
+    if (sc.alone()) return KF_OK;  // it holds every shard
+    return sc.serial(nothing, nothing, [&] { return sc.gather(bufs, 0, nb); }, nothing);
+}
+
+// The whole sharded step: the gradient buckets reduced to shards and averaged,
+// the update on the parameter shards, the parameter buckets gathered.
+static int sharded_step(kf_exchange &x, void *const *grads, const size_t *counts, int nb,
+                        KungFu_Datatype dt, int algo, hipStream_t s, const ShardUpdate &upd)
+{
+    Schedule sc{x, counts, nb, dt, KungFu_SUM, s};
+    if (sc.alone()) {  // a single peer: the update over the whole buckets
+        return upd.run(upd.params, grads, counts, 0, nb, dt, 1, s);
+    }
+    int rc = sc.resolve(algo, 1);
+    if (rc == KF_OK) rc = sc.reserve();
+    if (rc != KF_OK) return rc;
+    auto fold_update = [&] {
+        const int e = sc.fold(grads, x.world, 0, nb, s);
+        return e == KF_OK ? sc.update(upd, grads, sc.np(), 0, nb, s) : e;
+    };
+    return sc.serial([&] { return sc.scatter(grads, grads, 0, nb); }, fold_update,
+                     [&] { return sc.gather(upd.params, 0, nb); }, nothing);
+}
+
+// The gated step's second half, after reduce_to_shards and the verdict: the
+// gated update with the first half's np, then the gather.
+static int gated_update_gather(kf_exchange &x, void *const *grads, const size_t *counts, int nb,
+                               KungFu_Datatype dt, int np, hipStream_t s, const ShardUpdate &upd)
+{
+    Schedule sc{x, counts, nb, dt, KungFu_SUM, s};
+    if (sc.alone()) {  // a single peer: the update over the whole buckets
+        return upd.run(upd.params, grads, counts, 0, nb, dt, np, s);
+    }
+    return sc.serial(nothing, [&] { return sc.update(upd, grads, np, 0, nb, s); },
+                     [&] { return sc.gather(upd.params, 0, nb); }, nothing);
 }
 
 kf_exchange::Marks *kf_exchange::take_marks()
@@ -991,7 +1037,7 @@ int kf_exchange::hier(kf_session_t *cross, const void *send, void *recv, size_t 
         // at host 0's (graph.go:46-62's forest array)
         for (int g = 0; g < gsize; ++g) forest[g] = members[0][lrank[g]];
         const size_t q = count / W, t = count % W;
-        rc = batch(&send, &recv, &count, 1, dt, op, 0, algo, s, nullptr, 3);
+        rc = reduce_to_shards(*this, &send, &recv, &count, 1, dt, op, 0, algo, s).rc;
         if (rc == KF_OK && q) {
             char *sh = out + rank * q * sz;
             rc = kf_session_subset_all_reduce(cross, sh, sh, q, dt, op, forest.data(),
@@ -1008,13 +1054,13 @@ int kf_exchange::hier(kf_session_t *cross, const void *send, void *recv, size_t 
                                                kf_session_last_error());
             if (rc == KF_OK) rc = scale(tl, t);
         }
-        if (rc == KF_OK) rc = batch(&recv, &recv, &count, 1, dt, op, 0, algo, s, nullptr, 4);
+        if (rc == KF_OK) rc = gather_shards(*this, &recv, &count, 1, dt, s);
         return rc;
     }
     // hosts of different sizes: the reference's structure (collective.cpp:
     // 144-160) — host all-reduce, the hosts' first ranks across, host broadcast
     for (int g = 0; g < gsize; ++g) forest[g] = lrank[g] == 0 ? members[0][0] : g;
-    rc = batch(&send, &recv, &count, 1, dt, op, 0, algo, s);
+    rc = all_reduce(*this, &send, &recv, &count, 1, dt, op, 0, algo, s);
     if (rc == KF_OK) {
         rc = kf_session_subset_all_reduce(cross, recv, recv, count, dt, op, forest.data(),
                                           name.c_str(), s);
@@ -1046,7 +1092,7 @@ void kf_exchange::issue_loop()
             std::lock_guard<std::mutex> g(mu);
             const void *sp = t.send;
             void *rp       = t.recv;
-            rc = batch(&sp, &rp, &t.count, 1, t.dt, t.op, t.average, t.algo, t.stream);
+            rc = all_reduce(*this, &sp, &rp, &t.count, 1, t.dt, t.op, t.average, t.algo, t.stream);
         }
         const std::string why = rc == KF_OK ? std::string() : t_ex_error;
         hipEvent_t ev = nullptr;
@@ -1305,8 +1351,8 @@ void kf_exchange::negotiate_loop()
             }
             if (rc == KF_OK) {
                 std::lock_guard<std::mutex> g(mu);
-                rc = batch(snd.data(), rcv.data(), cnt.data(), static_cast<int>(j - i), ts[i].dt,
-                           ts[i].op, ts[i].average, ts[i].algo, nstream);
+                rc = all_reduce(*this, snd.data(), rcv.data(), cnt.data(), static_cast<int>(j - i),
+                                ts[i].dt, ts[i].op, ts[i].average, ts[i].algo, nstream);
             }
             const std::string why = rc == KF_OK ? std::string() : t_ex_error;
             std::lock_guard<std::mutex> lk(nmu);
@@ -1558,7 +1604,22 @@ kf_exchange_t *kf_exchange_split(kf_exchange_t *ex, int color, int key, int *sta
 
 static int check_bucket_args(kf_exchange_t *ex, const void *const *sends, void *const *recvs,
                              const size_t *counts, int nb, KungFu_Datatype dt, KungFu_Op op,
-                             int average);
+                             int average)
+{
+    if (!ex || nb < 0 || (nb > 0 && (!sends || !recvs || !counts))) {
+        return fail(KF_ERR_ARG, "bad arguments");
+    }
+    if (tsize(dt) == 0) return fail(KF_ERR_DTYPE, "unsupported dtype");
+    if (static_cast<unsigned>(op) > KungFu_PROD) return fail(KF_ERR_OP, "unsupported op");
+    if (dt == KungFu_FLOAT16 && op != KungFu_SUM) return fail(KF_ERR_OP, "fp16 supports SUM only");
+    if (average && (op != KungFu_SUM || !is_float(dt))) {
+        return fail(KF_ERR_OP, "average needs SUM on a float dtype");
+    }
+    for (int b = 0; b < nb; ++b) {
+        if (counts[b] && (!sends[b] || !recvs[b])) return fail(KF_ERR_ARG, "null bucket");
+    }
+    return KF_OK;
+}
 
 kf_exchange_t *kf_exchange_create_local(kf_session_t *s, int device)
 {
@@ -1634,23 +1695,34 @@ int kf_hier_all_reduce(kf_exchange_t *local, kf_session_t *cross, const void *se
                        static_cast<hipStream_t>(stream));
 }
 
-static int check_bucket_args(kf_exchange_t *ex, const void *const *sends, void *const *recvs,
-                             const size_t *counts, int nb, KungFu_Datatype dt, KungFu_Op op,
-                             int average)
+// The ladder of the entries that work on shards, for bucket b of `count`
+// elements (an empty one is not looked at): a null pointer in `buckets`, a
+// count that is no multiple of the world, a null pointer in a `shards` table
+// (a pair of the table and its text; a null table is one the entry does not
+// have), then the 16-byte alignment of all of them and of the shard's size.
+// fn: "<the entry's name>: ". Every rank reaches the same verdict before any
+// collective is queued.
+constexpr const char *kNotWorldMultiple =
+    "counts must be multiples of the world (padded buckets, no tails)";
+constexpr const char *kShardOff16 = "buckets and their shards must start 16-byte aligned";
+using ShardTab                    = std::pair<void *const *, const char *>;
+static int check_shard_bucket(const std::string &fn, std::initializer_list<void *const *> buckets,
+                              std::initializer_list<ShardTab> shards, int b, size_t count,
+                              int world, int sz)
 {
-    if (!ex || nb < 0 || (nb > 0 && (!sends || !recvs || !counts))) {
-        return fail(KF_ERR_ARG, "bad arguments");
+    if (count == 0) return KF_OK;
+    const size_t W = static_cast<size_t>(world);
+    bool off       = W > 1 && (count / W * sz) % 16;
+    for (void *const *t : buckets) {
+        if (!t[b]) return fail(KF_ERR_ARG, fn + "null bucket");
+        off = off || off16(t[b]);
     }
-    if (tsize(dt) == 0) return fail(KF_ERR_DTYPE, "unsupported dtype");
-    if (static_cast<unsigned>(op) > KungFu_PROD) return fail(KF_ERR_OP, "unsupported op");
-    if (dt == KungFu_FLOAT16 && op != KungFu_SUM) return fail(KF_ERR_OP, "fp16 supports SUM only");
-    if (average && (op != KungFu_SUM || !is_float(dt))) {
-        return fail(KF_ERR_OP, "average needs SUM on a float dtype");
+    if (count % W) return fail(KF_ERR_ARG, fn + kNotWorldMultiple);
+    for (const ShardTab &t : shards) {
+        if (t.first && !t.first[b]) return fail(KF_ERR_ARG, fn + t.second);
+        off = off || (t.first && off16(t.first[b]));
     }
-    for (int b = 0; b < nb; ++b) {
-        if (counts[b] && (!sends[b] || !recvs[b])) return fail(KF_ERR_ARG, "null bucket");
-    }
-    return KF_OK;
+    return off ? fail(KF_ERR_ARG, fn + kShardOff16) : KF_OK;
 }
 
 int kf_exchange_all_reduce_batch(kf_exchange_t *ex, const void *const *sends, void *const *recvs,
@@ -1661,8 +1733,8 @@ int kf_exchange_all_reduce_batch(kf_exchange_t *ex, const void *const *sends, vo
     if (rc != KF_OK || nb == 0) return rc;
     DeviceGuard g(ex->device);
     std::lock_guard<std::mutex> lk(ex->mu);
-    return ex->batch(sends, recvs, counts, nb, dt, op, average, algo,
-                     static_cast<hipStream_t>(stream));
+    return all_reduce(*ex, sends, recvs, counts, nb, dt, op, average, algo,
+                      static_cast<hipStream_t>(stream));
 }
 
 int kf_exchange_all_reduce(kf_exchange_t *ex, const void *send, void *recv, size_t count,
@@ -1680,119 +1752,91 @@ int kf_exchange_sma_batch(kf_exchange_t *ex, void *const *vs, void *const *sums,
     if (!is_float(dt)) return fail(KF_ERR_DTYPE, "SMA needs a float dtype");
     DeviceGuard g(ex->device);
     std::lock_guard<std::mutex> lk(ex->mu);
+    const Sma sma{vs, alpha};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    std::vector<const void *> snd(vs, vs + nb);
-    return ex->batch(snd.data(), sums, counts, nb, dt, KungFu_SUM, 0, algo, s, &alpha);
+    return all_reduce(*ex, vs, sums, counts, nb, dt, KungFu_SUM, 0, algo, s, &sma);
 }
 
 int kf_exchange_sgd_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
                           void *const *mom_shards, const size_t *counts, int nb,
                           KungFu_Datatype dt, const kf_sgd_hyper *hyper, int algo, void *stream)
 {
-    if (!ex || nb < 0) return fail(KF_ERR_ARG, "kf_exchange_sgd_batch: bad arguments");
-    if (!is_float(dt)) return fail(KF_ERR_DTYPE, "kf_exchange_sgd_batch: f32, f16, bf16 and f64 only");
+    const std::string fn = "kf_exchange_sgd_batch: ";
+    if (!ex || nb < 0) return fail(KF_ERR_ARG, fn + "bad arguments");
+    if (!is_float(dt)) return fail(KF_ERR_DTYPE, fn + "f32, f16, bf16 and f64 only");
     if (nb == 0) return KF_OK;
-    if (!params || !grads || !counts || !hyper) {
-        return fail(KF_ERR_ARG, "kf_exchange_sgd_batch: null table");
-    }
+    if (!params || !grads || !counts || !hyper) return fail(KF_ERR_ARG, fn + "null table");
+    // check_shard_bucket's ladder written out: here every bucket's pointers
+    // come before the algo, and the momentum check sits between the
+    // divisibility and the alignment check
     for (int b = 0; b < nb; ++b) {
-        if (counts[b] && (!params[b] || !grads[b])) {
-            return fail(KF_ERR_ARG, "kf_exchange_sgd_batch: null bucket");
-        }
+        if (counts[b] && (!params[b] || !grads[b])) return fail(KF_ERR_ARG, fn + "null bucket");
     }
-    if (algo < KF_ALGO_AUTO || algo > KF_ALGO_REDUCE_SCATTER_AVG) return fail(KF_ERR_ARG, "unknown algo");
-    // every rank must reach the same verdict before any collective is queued
+    if (check_algo(algo) != KF_OK) return KF_ERR_ARG;
     const size_t W = static_cast<size_t>(ex->world), sz = static_cast<size_t>(tsize(dt));
     for (int b = 0; b < nb; ++b) {
         if (counts[b] == 0) continue;
-        if (counts[b] % W) {
-            return fail(KF_ERR_ARG, "kf_exchange_sgd_batch: counts must be multiples of the world "
-                                    "(padded buckets, no tails)");
-        }
+        if (counts[b] % W) return fail(KF_ERR_ARG, fn + kNotWorldMultiple);
         void *m = mom_shards ? mom_shards[b] : nullptr;
         if (hyper[b].momentum != 0 && !m) {
-            return fail(KF_ERR_ARG, "kf_exchange_sgd_batch: momentum != 0 needs a momentum shard");
+            return fail(KF_ERR_ARG, fn + "momentum != 0 needs a momentum shard");
         }
-        if ((reinterpret_cast<uintptr_t>(params[b]) % 16) || (reinterpret_cast<uintptr_t>(grads[b]) % 16) ||
-            (reinterpret_cast<uintptr_t>(m) % 16) || (W > 1 && (counts[b] / W * sz) % 16)) {
-            return fail(KF_ERR_ARG, "kf_exchange_sgd_batch: buckets and their shards must start "
-                                    "16-byte aligned");
+        const bool shard_off = W > 1 && (counts[b] / W * sz) % 16;
+        if (off16(params[b]) || off16(grads[b]) || off16(m) || shard_off) {
+            return fail(KF_ERR_ARG, fn + kShardOff16);
         }
     }
     DeviceGuard g(ex->device);
     std::lock_guard<std::mutex> lk(ex->mu);
-    const ShardUpdate step{params, mom_shards, nullptr, hyper, nullptr};
-    return ex->batch(grads, grads, counts, nb, dt, KungFu_SUM, 1, algo,
-                     static_cast<hipStream_t>(stream), nullptr, 7, &step);
+    return sharded_step(*ex, grads, counts, nb, dt, algo, static_cast<hipStream_t>(stream),
+                        ShardUpdate{params, mom_shards, nullptr, hyper, nullptr});
 }
 
-// kf_exchange_adam_batch and kf_exchange_adam_master_batch: the checks every
-// rank makes before any collective is queued, then the three phases.
-// with_master: 16-bit buckets with fp32 master and state shards; otherwise the
-// state has the buckets' dtype and master_shards is not looked at.
+// kf_exchange_adam_batch, _adam_master_batch and _adam_gated_batch: the checks
+// every rank makes before any collective is queued, then the sharded step, or
+// with a gate the gated update (one hyper, its bias corrections ignored) and
+// the gather. with_master: 16-bit buckets with fp32 master and state shards;
+// otherwise the state has the buckets' dtype and master_shards is not looked at.
 static int exchange_adam(const char *name, kf_exchange_t *ex, void *const *params,
                          void *const *grads, void *const *master_shards, bool with_master,
                          void *const *exp_avg_shards, void *const *exp_avg_sq_shards,
                          const size_t *counts, int nb, KungFu_Datatype dt,
                          const kf_adam_hyper *hyper, int algo, void *stream,
                          const kf_step_gate *gate = nullptr, const kf_step_state *gstate = nullptr,
-                         int np_in = 0)
+                         int np = 0)
 {
-    // gate != nullptr: kf_exchange_adam_gated_batch, the gated update (one
-    // hyper, its bias corrections ignored) and phase 3
     const std::string fn = std::string(name) + ": ";
     if (!ex || nb < 0) return fail(KF_ERR_ARG, fn + "bad arguments");
-    if (gate && (!gstate || np_in < 0)) return fail(KF_ERR_ARG, fn + "no step state, or np < 0");
-    if (with_master) {
-        if (dt != KungFu_BFLOAT16 && dt != KungFu_FLOAT16) {
-            return fail(KF_ERR_DTYPE, fn + "bf16 and f16 only");
-        }
-    } else if (dt != KungFu_FLOAT && dt != KungFu_DOUBLE && dt != KungFu_BFLOAT16) {
+    if (gate && (!gstate || np < 0)) return fail(KF_ERR_ARG, fn + "no step state, or np < 0");
+    if (with_master && dt != KungFu_BFLOAT16 && dt != KungFu_FLOAT16) {
+        return fail(KF_ERR_DTYPE, fn + "bf16 and f16 only");
+    }
+    if (!with_master && dt != KungFu_FLOAT && dt != KungFu_DOUBLE && dt != KungFu_BFLOAT16) {
         return fail(KF_ERR_DTYPE, fn + "f32, bf16 and f64 only");
     }
     if (nb == 0) return KF_OK;
-    if (!params || !grads || !exp_avg_shards || !exp_avg_sq_shards || !counts || !hyper ||
-        (with_master && !master_shards)) {
-        return fail(KF_ERR_ARG, fn + "null table");
-    }
-    if (algo < KF_ALGO_AUTO || algo > KF_ALGO_REDUCE_SCATTER_AVG) return fail(KF_ERR_ARG, "unknown algo");
-    // every rank must reach the same verdict before any collective is queued
-    const size_t W = static_cast<size_t>(ex->world), sz = static_cast<size_t>(tsize(dt));
-    auto off16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) % 16) != 0; };
+    const bool tables = params && grads && exp_avg_shards && exp_avg_sq_shards && counts && hyper;
+    if (!tables || (with_master && !master_shards)) return fail(KF_ERR_ARG, fn + "null table");
+    if (check_algo(algo) != KF_OK) return KF_ERR_ARG;
+    if (!with_master) master_shards = nullptr;
+    const ShardTab m{exp_avg_shards, "every non-empty bucket needs both state shards"};
+    const ShardTab v{exp_avg_sq_shards, m.second};
+    const ShardTab w{master_shards, "every non-empty bucket needs its master shard"};
     for (int b = 0; b < nb; ++b) {
-        if (counts[b] == 0) continue;
-        if (!params[b] || !grads[b]) return fail(KF_ERR_ARG, fn + "null bucket");
-        if (counts[b] % W) {
-            return fail(KF_ERR_ARG, fn + "counts must be multiples of the world "
-                                         "(padded buckets, no tails)");
-        }
-        if (!exp_avg_shards[b] || !exp_avg_sq_shards[b]) {
-            return fail(KF_ERR_ARG, fn + "every non-empty bucket needs both state shards");
-        }
-        if (with_master && !master_shards[b]) {
-            return fail(KF_ERR_ARG, fn + "every non-empty bucket needs its master shard");
-        }
-        if (off16(params[b]) || off16(grads[b]) || off16(exp_avg_shards[b]) ||
-            off16(exp_avg_sq_shards[b]) || (with_master && off16(master_shards[b])) ||
-            (W > 1 && (counts[b] / W * sz) % 16)) {
-            return fail(KF_ERR_ARG, fn + "buckets and their shards must start 16-byte aligned");
-        }
-        if (!gate && (!(hyper[b].bias_correction1 > 0) || !(hyper[b].bias_correction2 > 0))) {
+        const int rc = check_shard_bucket(fn, {params, grads}, {m, v, w}, b, counts[b], ex->world,
+                                          tsize(dt));
+        if (rc != KF_OK) return rc;
+        if (counts[b] && !gate &&
+            (!(hyper[b].bias_correction1 > 0) || !(hyper[b].bias_correction2 > 0))) {
             return fail(KF_ERR_ARG, fn + "bias corrections must be > 0");
         }
     }
     DeviceGuard g(ex->device);
     std::lock_guard<std::mutex> lk(ex->mu);
-    ShardUpdate step{params, exp_avg_shards, exp_avg_sq_shards, nullptr, hyper,
-                     with_master ? master_shards : nullptr};
-    if (gate) {
-        step.part   = ShardUpdate::kUpdateOnly;
-        step.np_in  = np_in;
-        step.gate   = gate;
-        step.gstate = gstate;
-    }
-    return ex->batch(grads, grads, counts, nb, dt, KungFu_SUM, 1, algo,
-                     static_cast<hipStream_t>(stream), nullptr, gate ? 6 : 7, &step);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const ShardUpdate step{params, m.first, v.first, nullptr, hyper, master_shards, gate, gstate};
+    return gate ? gated_update_gather(*ex, grads, counts, nb, dt, np, s, step)
+                : sharded_step(*ex, grads, counts, nb, dt, algo, s, step);
 }
 
 int kf_exchange_reduce_shards_batch(kf_exchange_t *ex, void *const *grads, const size_t *counts,
@@ -1801,35 +1845,18 @@ int kf_exchange_reduce_shards_batch(kf_exchange_t *ex, void *const *grads, const
     const std::string fn = "kf_exchange_reduce_shards_batch: ";
     if (!ex || nb < 0 || !np) return fail(KF_ERR_ARG, fn + "bad arguments");
     if (!is_float(dt)) return fail(KF_ERR_DTYPE, fn + "f32, f16, bf16 and f64 only");
-    if (algo < KF_ALGO_AUTO || algo > KF_ALGO_REDUCE_SCATTER_AVG) return fail(KF_ERR_ARG, "unknown algo");
+    if (check_algo(algo) != KF_OK) return KF_ERR_ARG;
     if (nb > 0 && (!grads || !counts)) return fail(KF_ERR_ARG, fn + "null table");
-    // every rank must reach the same verdict before any collective is queued
-    const size_t W = static_cast<size_t>(ex->world), sz = static_cast<size_t>(tsize(dt));
     for (int b = 0; b < nb; ++b) {
-        if (counts[b] == 0) continue;
-        if (!grads[b]) return fail(KF_ERR_ARG, fn + "null bucket");
-        if (counts[b] % W) {
-            return fail(KF_ERR_ARG, fn + "counts must be multiples of the world "
-                                         "(padded buckets, no tails)");
-        }
-        if ((reinterpret_cast<uintptr_t>(grads[b]) % 16) || (W > 1 && (counts[b] / W * sz) % 16)) {
-            return fail(KF_ERR_ARG, fn + "buckets and their shards must start 16-byte aligned");
-        }
+        const int rc = check_shard_bucket(fn, {grads}, {}, b, counts[b], ex->world, tsize(dt));
+        if (rc != KF_OK) return rc;
     }
     DeviceGuard g(ex->device);
     std::lock_guard<std::mutex> lk(ex->mu);
-    if (nb == 0) {  // nothing to reduce: what a non-empty call would report
-        int a = 0;
-        const int rc = ex->world == 1 && ex->builtin ? KF_OK : resolve_algo(algo, dt, KungFu_SUM, ex->world, &a);
-        if (rc != KF_OK) return rc;
-        *np = ex->world == 1 && ex->builtin ? 1 : (a == KF_ALGO_REDUCE_SCATTER ? ex->world : 0);
-        return KF_OK;
-    }
-    ShardUpdate step{nullptr, nullptr, nullptr, nullptr, nullptr};
-    step.part   = ShardUpdate::kReduceOnly;
-    step.np_out = np;
-    return ex->batch(grads, grads, counts, nb, dt, KungFu_SUM, 1, algo,
-                     static_cast<hipStream_t>(stream), nullptr, 3, &step);
+    hipStream_t s     = static_cast<hipStream_t>(stream);
+    const Reduced red = reduce_to_shards(*ex, grads, grads, counts, nb, dt, KungFu_SUM, 1, algo, s);
+    if (red.np >= 0) *np = red.np;
+    return red.rc;
 }
 
 int kf_exchange_adam_gated_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
@@ -1859,13 +1886,8 @@ int kf_exchange_all_gather_doubles(kf_exchange_t *ex, const double *send, double
         if (send != recv) KF_HIP(hipMemcpyAsync(recv, send, bytes, hipMemcpyDeviceToDevice, s));
         return KF_OK;
     }
-    const int e0 = ex->T->group_start(ex->comm);
-    if (e0 != 0) return ex->tfail(e0, "group_start");
-    const int e  = ex->T->all_gather(send, recv, bytes, ex->comm, s);
-    const int e1 = ex->T->group_end(ex->comm);
-    if (e != 0) return ex->tfail(e, "all_gather of the plans' sums of squares");
-    if (e1 != 0) return ex->tfail(e1, "group_end");
-    return KF_OK;
+    return grouped(*ex, 0, 1, "all_gather of the plans' sums of squares",
+                   [&](int) { return ex->T->all_gather(send, recv, bytes, ex->comm, s); });
 }
 
 int kf_exchange_gather_params_batch(kf_exchange_t *ex, void *const *params, const size_t *counts,
@@ -1876,26 +1898,13 @@ int kf_exchange_gather_params_batch(kf_exchange_t *ex, void *const *params, cons
     if (!is_float(dt)) return fail(KF_ERR_DTYPE, fn + "f32, f16, bf16 and f64 only");
     if (nb == 0) return KF_OK;
     if (!params || !counts) return fail(KF_ERR_ARG, fn + "null table");
-    // every rank must reach the same verdict before any collective is queued
-    const size_t W = static_cast<size_t>(ex->world), sz = static_cast<size_t>(tsize(dt));
     for (int b = 0; b < nb; ++b) {
-        if (counts[b] == 0) continue;
-        if (!params[b]) return fail(KF_ERR_ARG, fn + "null bucket");
-        if (counts[b] % W) {
-            return fail(KF_ERR_ARG, fn + "counts must be multiples of the world "
-                                         "(padded buckets, no tails)");
-        }
-        if ((reinterpret_cast<uintptr_t>(params[b]) % 16) || (W > 1 && (counts[b] / W * sz) % 16)) {
-            return fail(KF_ERR_ARG, fn + "buckets and their shards must start 16-byte aligned");
-        }
+        const int rc = check_shard_bucket(fn, {params}, {}, b, counts[b], ex->world, tsize(dt));
+        if (rc != KF_OK) return rc;
     }
     DeviceGuard g(ex->device);
     std::lock_guard<std::mutex> lk(ex->mu);
-    if (ex->world == 1 && ex->builtin) return KF_OK;
-    // phase 3 of a plain batch call whose buckets are the parameters
-    std::vector<const void *> snd(params, params + nb);
-    return ex->batch(snd.data(), params, counts, nb, dt, KungFu_SUM, 0, KF_ALGO_AUTO,
-                     static_cast<hipStream_t>(stream), nullptr, 4);
+    return gather_shards(*ex, params, counts, nb, dt, static_cast<hipStream_t>(stream));
 }
 
 int kf_exchange_adam_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
@@ -2047,7 +2056,7 @@ int kf_exchange_all_reduce_named(kf_exchange_t *ex, const char *name, const void
     size_t c = count;
     int rc   = check_bucket_args(ex, &send, &recv, &c, 1, dt, op, average);
     if (rc != KF_OK) return rc;
-    if (algo < KF_ALGO_AUTO || algo > KF_ALGO_REDUCE_SCATTER_AVG) return fail(KF_ERR_ARG, "unknown algo");
+    if (check_algo(algo) != KF_OK) return KF_ERR_ARG;
     DeviceGuard g(ex->device);
     {
         std::lock_guard<std::mutex> lk(ex->mu);
