@@ -739,7 +739,10 @@ int kf_bucket_reduce_peers(const void *const *inputs, int k, void *out, size_t n
  * kf_transform2_host can DMA it directly (e.g. a receive-buffer pool the
  * transport reuses, srcs/go/rchannel/connection/byte_slice_pool.go:28-60).
  * The library remembers the range (a chunk inside it needs no pointer
- * queries); release it with kf_host_unregister(p), p the registered base. */
+ * queries); release it with kf_host_unregister(p), p the registered base.
+ * Where the platform cannot page-lock memory a process already has (some
+ * virtual machines) this returns KF_ERR_HIP and the range stays pageable:
+ * calls on it still work, through the staging path. */
 int kf_host_register(void *p, size_t bytes);
 int kf_host_unregister(void *p);
 

@@ -78,6 +78,10 @@ thread_local std::string t_last_error;
 int hip_fail(hipError_t e, const char *what)
 {
     t_last_error = std::string(what) + ": " + hipGetErrorString(e);
+    // reported here, so not left in HIP's last-error slot: a refused
+    // hipHostRegister otherwise fails the launch check of the next reduce
+    // kernel (this file's failures only; the other sources keep their own)
+    (void)hipGetLastError();
     return KF_ERR_HIP;
 }
 
