@@ -649,6 +649,96 @@ int kf_lamb_trust_update_gated(const double *sq, int world, int ntensor, const i
 int kf_lamb_apply_run_gated(kf_lamb_apply_t *p, const double *nlr, const kf_step_gate *gate,
                             void *stream);
 
+/* ---- LARS: layer-wise rates on the sharded SGD step ------------------------
+ *
+ * LARS (kungfu_amd/csrc/kf_lars.hip) as a per-tensor scaling of
+ * the gradient in front of kf_sgd_update_batch's arithmetic, where the reduced
+ * gradient and the momentum only exist as one rank's shard. Every parenthesis
+ * is one IEEE operation in the compute type C, no FMA contraction; scalars are
+ * computed in double and cast once to C, as kf_sgd_update_batch does. C is f32
+ * for f32 parameters and f64 for f64; for bf16 / f16 parameters C is f32 on
+ * the fp32 master copy, and the momentum is fp32 too.
+ *
+ * Norms: kf_segnorm KF_NORM_SQ on every rank, T the number of tensors:
+ * segment t is the piece of tensor t's parameters (of its master copy, on the
+ * master path) that lies in this rank's shard, count 0 where the rank holds
+ * none; segment T + t is the same piece of the reduced gradient shard, raw,
+ * before the / np. On the master path the halves differ in dtype: two plans
+ * that write into one send vector of kf_exchange_all_gather_doubles.
+ *
+ * Trust, one lane per tensor, fp64:
+ *   P = 0; for r in rank order: P = P + sq[r][t]      G likewise from sq[r][T + t]
+ *   wn = sqrt(P);  gn = np > 0 ? sqrt(G) / np : sqrt(G)
+ *   ratio = (adapt_g && wn > 0 && gn > 0) ? (tc_g * wn) / ((gn + (wd_g * wn)) + eps_g) : 1
+ *   coef[t] = { ratio, wd_g, mu_g, c_g = 1 - dampening_g, nlr_g = -lr_g, flags_g }
+ * g = group_of[t]. flags_g: 1 = momentum != 0, 2 = nesterov, 4 = first.
+ *
+ * Apply, per element of a piece, the scalars those of the tensor's row cast to C:
+ *   g = np > 0 ? g / np : g                    (kf_bucket_div's rounding in C)
+ *   wd != 0:        g = g + (wd * p)
+ *   g = ratio * g
+ *   momentum != 0:  m = first ? g : (mu * m) + (c * g)
+ *                   g = nesterov ? g + (mu * m) : m
+ *   p = p + (nlr * g)
+ * On the master path g is widened from 16 bits, p is the fp32 master and
+ * params16 = narrow(master), round-to-nearest-even. Where momentum == 0 the
+ * piece's momentum is neither read nor written; on `first` it is written and
+ * not read. Elements outside every piece (bucket padding) are not touched; the
+ * gradients are only read. 5 accesses per element: 20 bytes for f32, 18 + 2 on
+ * the master path. Non-finite gradients are NOT skipped; there is no gate on
+ * this path. */
+
+/* A parameter group's hyperparameters, read on the host before the call
+ * returns. first: the group's momentum holds nothing yet. adapt: the group
+ * uses the trust ratio; otherwise its ratio is 1. */
+typedef struct {
+    double lr, momentum, dampening, weight_decay, trust_coefficient, eps;
+    int nesterov, first, adapt;
+} kf_lars_group;
+
+/* coef: KF_LARS_COEF_DOUBLES doubles per tensor, row t at coef + 6 * t:
+ * { ratio, weight_decay, momentum, 1 - dampening, -lr, flags (0 .. 7, as a
+ * double) }; ntensor * 48 bytes of device memory. */
+#define KF_LARS_COEF_DOUBLES 6
+
+/* The coefficient rows of ntensor tensors. sq is a device array of world * 2 *
+ * ntensor doubles, sq[r * 2 * ntensor + k]; group_of (device, ntensor ints)
+ * maps a tensor to its group; groups (host, ngroup entries) come with every
+ * call because schedulers change them. ratio (device, ntensor doubles) gets
+ * ratio[t] once more on its own. A tensor whose group index is outside
+ * [0, ngroup) is not written. Any ntensor >= 1, world >= 1, ngroup >= 1 and
+ * np >= 0: one launch per 16 groups, on the same stream. No atomics, no host
+ * sync, no allocation. */
+int kf_lars_trust_update(const double *sq, int world, int ntensor, const int *group_of,
+                         const kf_lars_group *groups, int ngroup, int np, double *coef,
+                         double *ratio, void *stream);
+
+/* The apply pass as a plan (kf_lamb_apply's shape and contract):
+ * kf_lars_apply_create uploads the piece table to HBM once; kf_lars_apply_run
+ * is one launch whatever the number of pieces, and only queues it (no
+ * allocation, no host sync). Piece i is counts[i] elements at params[i],
+ * grads[i] and moms[i] of dt (f32 or f64, params16 == NULL), or, with dt =
+ * bf16 / f16, fp32 elements at params[i] (the master) and moms[i] and 16-bit
+ * ones at grads[i] and params16[i]; any other combination: KF_ERR_DTYPE.
+ * tensors[i] in [0, ntensor) is the piece's row of coef. Pointers are aligned
+ * to the element only, but a piece's arrays must share their element offset
+ * from a 16-byte boundary (KF_ERR_ARG otherwise; pieces cut from shards that
+ * start 16-byte aligned do). A count may be 0 and npiece may be 0. Returns
+ * NULL on failure with kf_last_error() set. Every argument check comes before
+ * any HIP call. coef is kf_lars_trust_update's; np >= 0 is what the gradient
+ * is still to be divided by. kf_lars_apply_tile: the elements of one block's
+ * tile of 16-byte units for dt (a piece of up to that many elements, plus its
+ * unaligned head and tail, is one block's). */
+typedef struct kf_lars_apply kf_lars_apply_t; /* opaque plan */
+kf_lars_apply_t *kf_lars_apply_create(void *const *params, const void *const *grads,
+                                      void *const *moms,
+                                      void *const *params16 /* NULL: f32, f64 */,
+                                      const size_t *counts, const int *tensors, int npiece,
+                                      int ntensor, KungFu_Datatype dt);
+int kf_lars_apply_run(kf_lars_apply_t *p, const double *coef, int np, void *stream);
+void kf_lars_apply_destroy(kf_lars_apply_t *p);
+size_t kf_lars_apply_tile(KungFu_Datatype dt);
+
 /* ---- gradient monitors: segmented squared norms ------------------------- */
 
 /* What MonitorGradientNoiseScaleOptimizer and MonitorGradientVarianceOptimizer

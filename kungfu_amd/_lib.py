@@ -150,6 +150,11 @@ EXPORTED = (
     "kf_adam8_master_update_batch_gated",
     "kf_adam8_quantize",
     "kf_adam8_dequantize",
+    "kf_lars_trust_update",
+    "kf_lars_apply_create",
+    "kf_lars_apply_run",
+    "kf_lars_apply_destroy",
+    "kf_lars_apply_tile",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -218,6 +223,31 @@ def adam_hyper_array(hypers):
 class LambGroup(ctypes.Structure):
     """kf_lamb_group (include/kungfu_amd.h): what the trust ratios need of a group."""
     _fields_ = [("lr", ctypes.c_double), ("adapt", ctypes.c_int)]
+
+
+class LarsGroup(ctypes.Structure):
+    """kf_lars_group (include/kungfu_amd.h): a parameter group's LARS scalars."""
+    _fields_ = [("lr", ctypes.c_double), ("momentum", ctypes.c_double),
+                ("dampening", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("trust_coefficient", ctypes.c_double), ("eps", ctypes.c_double),
+                ("nesterov", ctypes.c_int), ("first", ctypes.c_int), ("adapt", ctypes.c_int)]
+
+
+LARS_COEF_DOUBLES = 6  # KF_LARS_COEF_DOUBLES: a tensor's row of kf_lars_trust_update's coef
+
+
+def lars_group_array(groups):
+    """A kf_lars_group[] from dicts with torch.optim.SGD's param-group keys
+    (lr, momentum, dampening, weight_decay, nesterov) and trust_coefficient,
+    eps, first, adapt."""
+    arr = (LarsGroup * max(1, len(groups)))()
+    for a, h in zip(arr, groups):
+        a.lr, a.momentum = float(h["lr"]), float(h.get("momentum", 0.0))
+        a.dampening, a.weight_decay = float(h.get("dampening", 0.0)), float(h.get("weight_decay", 0.0))
+        a.trust_coefficient, a.eps = float(h["trust_coefficient"]), float(h["eps"])
+        a.nesterov, a.first = int(bool(h.get("nesterov", False))), int(bool(h.get("first", False)))
+        a.adapt = int(bool(h["adapt"]))
+    return arr
 
 
 class StepGate(ctypes.Structure):
@@ -597,6 +627,18 @@ def load():
     lib.kf_lamb_apply_run_gated.restype = c_int
     lib.kf_lamb_apply_destroy.argtypes = [c_void_p]
     lib.kf_lamb_apply_destroy.restype = None
+    lib.kf_lars_trust_update.argtypes = [c_void_p, c_int, c_int, c_void_p, P(LarsGroup), c_int,
+                                         c_int, c_void_p, c_void_p, c_void_p]
+    lib.kf_lars_trust_update.restype = c_int
+    lib.kf_lars_apply_create.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_void_p),
+                                         P(c_size_t), P(c_int), c_int, c_int, c_int]
+    lib.kf_lars_apply_create.restype = c_void_p
+    lib.kf_lars_apply_run.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
+    lib.kf_lars_apply_run.restype = c_int
+    lib.kf_lars_apply_destroy.argtypes = [c_void_p]
+    lib.kf_lars_apply_destroy.restype = None
+    lib.kf_lars_apply_tile.argtypes = [c_int]
+    lib.kf_lars_apply_tile.restype = c_size_t
     lib.kf_exchange_gather_params_batch.argtypes = [c_void_p, P(c_void_p), P(c_size_t), c_int,
                                                     c_int, c_void_p]
     lib.kf_exchange_gather_params_batch.restype = c_int

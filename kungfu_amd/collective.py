@@ -176,6 +176,17 @@ class HipEpilogue:
                                             trust_clip)
 
 
+    # -- LARS --
+    def lars_trust_update_(self, sq, world, group_of, groups, coef, ratio, np_=0):
+        """The tensors' coefficient rows (ops.lars_trust_update_), one launch per 16 groups."""
+        return ops.lars_trust_update_(sq, world, group_of, groups, coef, ratio, np_)
+
+    def lars_apply_plan(self, params, grads, moms, tensors, ntensor, params16=None):
+        """A plan whose run(coef, np_) is the fused LARS momentum update of
+        the pieces (ops.LarsApplyPlan), built once over fixed views."""
+        return ops.lars_apply_plan(params, grads, moms, tensors, ntensor, params16)
+
+
 def coalesce_runs(buckets):
     """Maximal runs of buckets that are consecutive in one storage, each as
     one flat view."""

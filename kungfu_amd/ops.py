@@ -811,6 +811,140 @@ class LambApplyPlan:
             pass
 
 
+# -- LARS (include/kungfu_amd.h "LARS") --
+
+LARS_COEF = _lib.LARS_COEF_DOUBLES
+
+
+def lars_trust_update_(sq, world, group_of, groups, coef, ratio, np_=0, stream=None):
+    """The coefficient rows of T = group_of.numel() tensors on the device
+    (kf_lars_trust_update): sq is world * 2 * T float64 sums of squares,
+    sq[r * 2T + t] of rank r's piece of tensor t's parameters and
+    sq[r * 2T + T + t] of its reduced gradient before the / np_; group_of an
+    int32 device tensor (tensor -> group); groups[j] a dict with lr, momentum,
+    dampening, weight_decay, nesterov, trust_coefficient, eps, first and
+    adapt. Writes coef[6t:6t + 6] = (ratio, weight_decay, momentum,
+    1 - dampening, -lr, flags) and ratio[t], where ratio =
+    tc * ||p|| / (||g|| / np_ + wd * ||p|| + eps), or 1 where adapt is off or
+    a norm is not > 0. No host sync."""
+    groups = list(groups)
+    _check_dev([sq, group_of, coef, ratio])
+    T = group_of.numel()
+    if group_of.dtype != torch.int32 or T < 1 or not groups:
+        raise ValueError("lars_trust_update_: group_of is a non-empty int32 tensor, and at least "
+                         "one group")
+    if sq.dtype != torch.float64 or sq.numel() != int(world) * 2 * T or int(world) < 1:
+        raise ValueError("lars_trust_update_: sq is world * 2 * T float64 values")
+    if coef.dtype != torch.float64 or coef.numel() != LARS_COEF * T or \
+            ratio.dtype != torch.float64 or ratio.numel() != T:
+        raise ValueError("lars_trust_update_: coef is %d * T and ratio T float64 values"
+                         % LARS_COEF)
+    rc = _lib.load().kf_lars_trust_update(
+        sq.data_ptr(), int(world), T, group_of.data_ptr(), _lib.lars_group_array(groups),
+        len(groups), int(np_), coef.data_ptr(), ratio.data_ptr(), _stream(stream, sq.device))
+    _lib.check(rc, "kf_lars_trust_update", source="")
+    return coef
+
+
+class LarsApplyPlan:
+    """LARS's fused momentum update over "tensor ∩ own shard" pieces
+    (kf_lars_apply_*): built once over views that never move, run(coef, np_)
+    is one launch whatever the number of pieces. Per element of piece i, with
+    the scalars of row tensors[i] of coef (lars_trust_update_'s):
+
+      g = grads[i] / np_;  wd != 0: g += wd * p;  g *= ratio
+      momentum != 0: m = first ? g : mu * m + (1 - dampening) * g
+                     g = nesterov ? g + mu * m : m
+      params[i] += -lr * g
+
+    in the pieces' f32 / f64. With params16 (bf16 or f16 views of the same
+    lengths) params are the fp32 master pieces, moms fp32, grads of the 16-bit
+    type, and params16[i] = params[i] narrowed, round-to-nearest-even. Pieces
+    are aligned to the element only; a piece's tensors must share their
+    element offset from a 16-byte boundary. A piece may be empty. The
+    gradients are only read; a piece whose row has momentum 0 leaves its moms
+    alone. The plan keeps the tensors alive."""
+
+    def __init__(self, params, grads, moms, tensors, ntensor, params16=None):
+        ps, gs, ms, ts = list(params), list(grads), list(moms), [int(t) for t in tensors]
+        p16 = None if params16 is None else list(params16)
+        if not (len(ps) == len(gs) == len(ms) == len(ts)) or \
+                (p16 is not None and len(p16) != len(ps)):
+            raise ValueError("LarsApplyPlan: one gradient, momentum and tensor index per piece")
+        _check_dev(ps + gs + ms + (p16 or []))
+        for i, (p, g, m) in enumerate(zip(ps, gs, ms)):
+            if p.dtype != ps[0].dtype or m.dtype != p.dtype or g.dtype != gs[0].dtype or \
+                    g.numel() != p.numel() or m.numel() != p.numel():
+                raise ValueError("LarsApplyPlan: shape/dtype mismatch")
+            if p16 is not None and (p16[i].numel() != p.numel() or p16[i].dtype != gs[0].dtype):
+                raise ValueError("LarsApplyPlan: shape/dtype mismatch")
+        if ps:
+            if p16 is not None:
+                if ps[0].dtype != torch.float32 or \
+                        gs[0].dtype not in (torch.bfloat16, torch.float16):
+                    raise ValueError("LarsApplyPlan: fp32 masters and momentum, bf16 or f16 "
+                                     "gradients and parameters")
+            elif ps[0].dtype not in (torch.float32, torch.float64) or gs[0].dtype != ps[0].dtype:
+                raise ValueError("LarsApplyPlan: f32 or f64 parameters (bf16 and f16 through "
+                                 "their masters)")
+        self._keep = (ps, gs, ms, p16)
+        self.npiece, self.ntensor = len(ps), int(ntensor)
+        self.device = ps[0].device if ps else None
+        self._plan = None
+        if not ps:
+            return
+        lib = _lib.load()
+        dt = int(kungfu_dtype(gs[0]))
+        with torch.cuda.device(self.device):
+            self._plan = lib.kf_lars_apply_create(
+                _lib.ptr_array([t.data_ptr() for t in ps]),
+                _lib.ptr_array([t.data_ptr() for t in gs]),
+                _lib.ptr_array([t.data_ptr() for t in ms]),
+                None if p16 is None else _lib.ptr_array([t.data_ptr() for t in p16]),
+                (ctypes.c_size_t * len(ps))(*[t.numel() for t in ps]),
+                (ctypes.c_int * len(ps))(*ts), len(ps), self.ntensor, dt)
+        if not self._plan:
+            raise _lib.KungFuAMDError("kf_lars_apply_create failed: %s"
+                                      % lib.kf_last_error().decode())
+
+    def run(self, coef, np_=0, stream=None):
+        if not self.npiece:
+            return
+        if self._plan is None:
+            raise ValueError("LarsApplyPlan: closed")
+        _check_dev([coef])
+        if coef.dtype != torch.float64 or coef.numel() != LARS_COEF * self.ntensor or \
+                coef.device != self.device:
+            raise ValueError("LarsApplyPlan.run: coef must be %d float64 values on %s"
+                             % (LARS_COEF * self.ntensor, self.device))
+        rc = _lib.load().kf_lars_apply_run(self._plan, coef.data_ptr(), int(np_),
+                                           _stream(stream, self.device))
+        _lib.check(rc, "kf_lars_apply_run", source="")
+
+    def close(self):
+        if self._plan is not None:
+            _lib.load().kf_lars_apply_destroy(self._plan)
+            self._plan = None
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def lars_apply_plan(params, grads, moms, tensors, ntensor, params16=None):
+    """A LarsApplyPlan: run(coef, np_) is the one apply launch."""
+    return LarsApplyPlan(params, grads, moms, tensors, ntensor, params16)
+
+
+def lars_apply_tile(dtype):
+    """Elements of one block's tile in the apply launch for parameters of
+    `dtype` (kf_lars_apply_tile)."""
+    return int(_lib.load().kf_lars_apply_tile(int(kungfu_dtype(torch.empty(0, dtype=dtype)))))
+
+
 _NORM_DTYPES = (torch.float32, torch.float16, torch.bfloat16, torch.float64)
 
 

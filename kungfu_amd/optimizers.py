@@ -30,6 +30,9 @@ Operator surface kept from the reference:
   for torch.optim.Adam / AdamW: exp_avg and exp_avg_sq sharded over the ranks.
 * ``ShardedLAMBOptimizer(optimizer, named_parameters=None, ...)`` — LAMB on
   the same shards: per-tensor trust ratios from norms taken across the ranks.
+* ``ShardedLARSOptimizer(optimizer, named_parameters=None, ...)`` — LARS on
+  the sharded SGD step: a per-tensor rate in front of the momentum update,
+  with fp32 master weights and momentum for bf16 / f16 models.
 
 Buckets: parameters are grouped (in registration order, per dtype/device) into
 flat padded device buckets (``collective.GradBuckets``); ``p.grad`` (S-SGD) or
@@ -1483,6 +1486,171 @@ class _ShardedLAMB(_ShardedAdam):
         return out
 
 
+class _ShardedLARS(_Sharded):
+    """reduce-scatter(grads) -> segmented norms of the (parameter, gradient)
+    pieces -> all-gather of the sums -> coefficient rows -> fused LARS momentum
+    update on the own pieces -> all-gather(params). The
+    momentum is one shard per bucket, in fp32 beside an fp32 master shard for
+    bf16 / f16 groups; both are allocated with the buckets, so the plans'
+    addresses never change."""
+
+    _kf_name = "ShardedLARSOptimizer"
+    _kf_dtypes = ("float32", "float64")
+    _kf_dtype_words = "f32 and f64 (bf16 and f16 with master_weights=True)"
+    _kf_trust = 0.001
+    _kf_eps = 1e-8
+    _kf_always_adapt = False
+    _kf_lars = None  # the plans, one per (dtype, device)
+    _kf_ops = _ShardedAdam._kf_ops
+
+    def _kf_new_group(self):
+        return {"moms": None, "w": None, "first": True, "np": 0}
+
+    def _kf_build_sharded(self):
+        """Once, with the buckets: master and momentum shards, and per (dtype,
+        device) the norm plan (two on the master path, whose halves differ in
+        dtype) over the 2T pieces of parameters and reduced gradients, the
+        tensor -> group table, the coefficient rows and the apply plan."""
+        import torch
+        from ._lib import LARS_COEF_DOUBLES
+        super()._kf_build_sharded()
+        ex, ep = self._kf_ex, self._kf_ops("lars_apply_plan")
+        by = {}
+        for j, G in enumerate(self._kf_groups):
+            b = G["pb"].buckets[0]
+            if b.element_size() == 2:
+                G["w"] = self._kf_zero_shards(G, torch.float32)
+                for bucket, w in zip(G["pb"].buckets, G["w"]):  # the widening is exact
+                    q = w.numel()
+                    w.copy_(bucket[ex.rank * q:(ex.rank + 1) * q])
+            G["moms"] = self._kf_zero_shards(G, torch.float32 if G["w"] is not None else None)
+            by.setdefault((b.dtype, b.device), []).append(j)
+        self._kf_lars = []
+        for (dtype, device), js in by.items():
+            pp, gg, mm, p16, tensors, group_of, owners = [], [], [], [], [], [], []
+            for k, j in enumerate(js):
+                G = self._kf_groups[j]
+                shards = ex.grad_shards_(G["gb"].buckets, ("lars", j))
+                pieces = {t: (b, off, n) for t, b, off, n in
+                          lamb_pieces(G["pb"], ex.world, ex.rank)}
+                for t, p in enumerate(G["ps"]):
+                    b, off, n = pieces.get(t, (0, 0, 0))
+                    bucket = G["pb"].buckets[b]
+                    q = bucket.numel() // ex.world
+                    mine = bucket[ex.rank * q:(ex.rank + 1) * q]
+                    pp.append((G["w"][b] if G["w"] is not None else mine)[off:off + n])
+                    gg.append(shards[b][off:off + n])  # a shard is the q reduced elements
+                    mm.append(G["moms"][b][off:off + n])
+                    if G["w"] is not None:
+                        p16.append(mine[off:off + n])
+                    tensors.append(len(owners))
+                    group_of.append(k)
+                    owners.append(p)
+            T = len(owners)
+            f64 = dict(dtype=torch.float64, device=device)
+            out = torch.zeros(2 * T + 1, **f64)
+            if p16:  # fp32 masters, 16-bit gradients: the second plan's sums start at out[T]
+                norms = [(ep.sq_norm_plan(pp), out[:T + 1]), (ep.sq_norm_plan(gg), out[T:])]
+            else:
+                norms = [(ep.sq_norm_plan(pp + gg), out)]
+            self._kf_lars.append({
+                "js": js, "owners": owners, "T": T, "norms": norms, "out": out,
+                "sq": torch.zeros(2 * T * ex.world, **f64),
+                "group_of": torch.tensor(group_of, dtype=torch.int32, device=device),
+                "coef": torch.zeros(LARS_COEF_DOUBLES * T, **f64), "ratio": torch.ones(T, **f64),
+                "apply": ep.lars_apply_plan(pp, gg, mm, tensors, T, p16 if p16 else None)})
+
+    def _kf_hyper(self, G):
+        """The group's hyper, read at every step (schedulers change them)."""
+        pg = self.param_groups[G["gi"]]
+        wd = float(pg["weight_decay"])
+        return {"lr": float(pg["lr"]), "momentum": float(pg["momentum"]),
+                "dampening": float(pg["dampening"]), "weight_decay": wd,
+                "nesterov": bool(pg["nesterov"]), "first": G["first"],
+                "trust_coefficient": self._kf_trust, "eps": self._kf_eps,
+                "adapt": wd != 0 or self._kf_always_adapt}
+
+    def step(self, closure=None):
+        loss = self._kf_closure(closure)
+        if self._kf_groups is None:
+            self._kf_build_sharded()
+        ex, ep, groups = self._kf_ex, self._kf_ops("lars_apply_plan"), self._kf_groups
+        for G in groups:
+            _SyncSGD._kf_place(G["ps"], G["gb"])
+        for j, G in enumerate(groups):
+            G["np"] = ex.reduce_shards_(G["gb"].buckets, ("lars", j))
+        for L in self._kf_lars:
+            nps = {groups[j]["np"] for j in L["js"]}
+            if len(nps) != 1:
+                raise ValueError("%s: the exchange left the groups of one dtype with different "
+                                 "divisors %s" % (self._kf_name, sorted(nps)))
+            np_ = nps.pop()
+            for plan, out in L["norms"]:  # the gradients' sums last: they own out[T:]
+                plan.run("sq", out=out)
+            ex.gather_doubles_(L["out"][:2 * L["T"]], L["sq"])
+            hs = [self._kf_hyper(groups[j]) for j in L["js"]]
+            ep.lars_trust_update_(L["sq"], ex.world, L["group_of"], hs, L["coef"], L["ratio"], np_)
+            L["apply"].run(L["coef"], np_)
+            for j, h in zip(L["js"], hs):
+                if h["momentum"] != 0:
+                    groups[j]["first"] = False
+        for G in groups:
+            ex.gather_params_(G["pb"].buckets)
+        _finish(ex)
+        return loss
+
+    def momentum_buffers(self):
+        """Collective: {parameter: its full momentum buffer} (fp32 for bf16 /
+        f16 parameters), gathered from the ranks' shards; empty for a group
+        that has not yet stepped with momentum. ShardedSGDOptimizer's
+        checkpoint path."""
+        out = {}
+        for G in self._kf_groups or []:
+            if not G["first"]:
+                out.update(self._kf_unshard(G, G["moms"]))
+        _finish(self._kf_ex)
+        return out
+
+    def load_momentum_buffers(self, mapping):
+        """ShardedSGDOptimizer.load_momentum_buffers: each rank keeps its
+        slice, and the next step is no longer a loaded group's first."""
+        if self._kf_groups is None:
+            self._kf_build_sharded()
+        for G in self._kf_groups:
+            if any(p in mapping for p in G["ps"]):
+                self._kf_reshard(G, G["moms"], mapping.get)
+                G["first"] = False
+
+    def master_buffers(self):
+        """Collective: {parameter: its full fp32 master copy} of the bf16 /
+        f16 groups (master_weights=True); the checkpoint's "master"."""
+        out = {}
+        for G in self._kf_groups or []:
+            if G["w"] is not None:
+                out.update(self._kf_unshard(G, G["w"]))
+        _finish(self._kf_ex)
+        return out
+
+    def load_master_buffers(self, mapping):
+        """{parameter: full fp32 master} (master_buffers' result, on every
+        rank) into this rank's master shards; a parameter missing from
+        `mapping` keeps the widening of its 16-bit value."""
+        if self._kf_groups is None:
+            self._kf_build_sharded()
+        for G in self._kf_groups:
+            if G["w"] is not None:
+                self._kf_reshard(G, G["w"], lambda p: mapping.get(p, p.data))
+
+    def last_trust_ratios(self):
+        """{parameter: the trust ratio its last step used}; empty before the
+        first step. Synchronises with the device."""
+        out = {}
+        for L in self._kf_lars or []:
+            for p, r in zip(L["owners"], L["ratio"].cpu().tolist()):
+                out[p] = float(r)
+        return out
+
+
 def ShardedSGDOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20):
     """Synchronous SGD with the optimizer update sharded over the ranks
     (sharded optimizer state): every step is
@@ -1929,4 +2097,87 @@ def ShardedLAMBOptimizer(optimizer, named_parameters=None, exchange=None, bucket
         opt._kf_max_norm, opt._kf_rule = _gate_rule(gate.get("max_grad_norm"),
                                                     gate.get("loss_scale"), opt._kf_name)
         opt._kf_gated = True
+    return opt
+
+
+def ShardedLARSOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20,
+                         master_weights=False, trust_coefficient=0.001, eps=1e-8,
+                         always_adapt=False):
+    """LARS (layer-wise adaptive rate scaling, the large-batch method of
+    SGD with momentum) with the update and its state sharded over the ranks as
+    ShardedSGDOptimizer's are. Every step is
+
+      reduce-scatter(grads)
+        -> norms of every tensor's piece of p and of the reduced gradient on
+           this rank (ops.SegNorm, fp64) -> all-gather of 16 bytes per tensor
+           and rank
+        -> per tensor: ratio = trust_coefficient * ||p|| /
+           (||g|| + weight_decay * ||p|| + eps), and the tensor's row of
+           coefficients in device memory (ops.lars_trust_update_)
+        -> [own pieces, one launch: g / np, g += weight_decay * p, g *= ratio,
+            momentum, p -= lr * g] (ops.LarsApplyPlan) -> all-gather(params)
+
+    all queued on the current stream: the host never waits for a norm. The
+    sums are added in rank order, so every rank computes the same ratios bit
+    for bit. LARS here is a scaling of the gradient per tensor, not a clip,
+    in front of torch.optim.SGD's single-tensor arithmetic, rounded as
+    include/kungfu_amd.h ("LARS") states.
+
+    `optimizer` must be a torch.optim.SGD (TypeError otherwise); it only lends
+    its class and its param_groups: lr, momentum, dampening, weight_decay and
+    nesterov are read from them at every step, so LR schedulers work. A
+    parameter group adapts (uses the ratio) when its weight_decay != 0 or
+    always_adapt=True, ShardedLAMBOptimizer's rule: a batch-norm or bias group
+    with weight_decay=0 takes plain SGD steps. A tensor whose parameter norm
+    or gradient norm is not > 0 (a zero-element tensor among them) has ratio 1.
+
+      * master_weights=True: bf16 and f16 groups keep an fp32 master copy of
+        this rank's slice and an fp32 momentum; the update runs in fp32 on
+        them and the 16-bit parameters are the master narrowed
+        (round-to-nearest-even). Without it bf16 and f16 parameters are
+        refused: f32 and f64 only.
+      * trust_coefficient > 0 and eps >= 0 are LARS's eta and the
+        denominator's epsilon.
+      * Non-finite gradients are not skipped: they reach the norms, the
+        momentum and the parameters.
+      * A parameter without a gradient is updated as with a zero gradient,
+        and p.grad does not hold the averaged gradient after step().
+
+    momentum_buffers() / load_momentum_buffers() are ShardedSGDOptimizer's
+    checkpoint path (fp32 buffers for 16-bit parameters); with master weights
+    master_buffers() / load_master_buffers() carry the checkpoint's master
+    copies. last_trust_ratios() returns {parameter: float} of the last step
+    and synchronises.
+
+    Not offered: a gate (gradient clipping, loss scaling, step skipping),
+    overlap=True, the hierarchical (multi-host) path, a clip mode
+    (min(ratio, 1)), maximize, differentiable, and any optimizer other than
+    SGD."""
+    import torch
+    name = "ShardedLARSOptimizer"
+    if not isinstance(optimizer, torch.optim.SGD):
+        raise TypeError("%s wraps a torch.optim.SGD, not %s" % (name, type(optimizer).__name__))
+    for g in optimizer.param_groups:
+        for option in ("maximize", "differentiable"):
+            if g.get(option, False):
+                raise ValueError("%s: %s=True is not supported" % (name, option))
+        if not master_weights and any(p.dtype in (torch.bfloat16, torch.float16)
+                                      for p in g["params"]):
+            raise TypeError("%s: bf16 and f16 parameters need master_weights=True" % name)
+    for what, v, ok in (("trust_coefficient", trust_coefficient, lambda x: 0 < x < float("inf")),
+                        ("eps", eps, lambda x: 0 <= x < float("inf"))):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not ok(v):
+            raise ValueError("%s: %s must be a finite number %s 0, not %r"
+                             % (name, what, ">" if what == "trust_coefficient" else ">=", v))
+    opt = _wrap(optimizer, _ShardedLARS)
+    opt._kf_setup(named_parameters, exchange, bucket_bytes)
+    for method in ("reduce_shards_", "grad_shards_", "gather_doubles_", "gather_params_"):
+        if not hasattr(opt._kf_ex, method):
+            raise ValueError("%s needs an exchange with %s() (collective.Exchange or "
+                             "exchange.NativeExchange)" % (name, method))
+    opt._kf_trust, opt._kf_eps = float(trust_coefficient), float(eps)
+    opt._kf_always_adapt = bool(always_adapt)
+    if master_weights:
+        opt._kf_dtypes = ("float32", "float16", "bfloat16", "float64")
+        opt._kf_dtype_words = "f32, f16, bf16 and f64"
     return opt

@@ -25,7 +25,8 @@ takes ``named_parameters`` positionally.
 momentum sharded over the ranks) likewise takes ``named_parameters``
 positionally, and so does ``ShardedAdamOptimizer`` (the same for
 torch.optim.Adam / AdamW and their two state tensors) and
-``ShardedLAMBOptimizer`` (LAMB's layer-wise trust ratios on the same shards).
+``ShardedLAMBOptimizer`` (LAMB's layer-wise trust ratios on the same shards)
+and ``ShardedLARSOptimizer`` (LARS's layer-wise rates on the sharded SGD step).
 """
 from .. import optimizers as _opt
 from ..optimizers import SynchronousAveragingOptimizer
@@ -33,7 +34,7 @@ from ..optimizers import SynchronousAveragingOptimizer
 __all__ = ["SynchronousSGDOptimizer", "SynchronousAveragingOptimizer",
            "MonitorGradientNoiseScaleOptimizer", "MonitorGradientVarianceOptimizer",
            "PairAveragingOptimizer", "ShardedSGDOptimizer", "ShardedAdamOptimizer",
-           "ShardedLAMBOptimizer"]
+           "ShardedLAMBOptimizer", "ShardedLARSOptimizer"]
 
 
 def SynchronousSGDOptimizer(optimizer, named_parameters, op=None, **kwargs):
@@ -88,3 +89,10 @@ def ShardedLAMBOptimizer(optimizer, named_parameters, **kwargs):
     `master_weights`, `trust_clip`, `always_adapt` and `gate` (a dict with
     `max_grad_norm` and / or `loss_scale`: the step under the device-side gate)."""
     return _opt.ShardedLAMBOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
+
+
+def ShardedLARSOptimizer(optimizer, named_parameters, **kwargs):
+    """kungfu_amd.optimizers.ShardedLARSOptimizer with `named_parameters`
+    positional. Keywords pass through: `exchange`, `bucket_bytes`,
+    `master_weights`, `trust_coefficient`, `eps` and `always_adapt`."""
+    return _opt.ShardedLARSOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
