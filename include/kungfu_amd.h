@@ -739,6 +739,56 @@ int kf_lars_apply_run(kf_lars_apply_t *p, const double *coef, int np, void *stre
 void kf_lars_apply_destroy(kf_lars_apply_t *p);
 size_t kf_lars_apply_tile(KungFu_Datatype dt);
 
+/* ---- MXFP8 gradient wire ----------------------------------------------------
+ *
+ * What phase 1 of a sharded step carries under kf_exchange_reduce_shards_mx8_
+ * batch (kungfu_amd/csrc/kf_mx8.hip; tests/mx8_ref.py restates
+ * it in numpy): one OCP E4M3 code per gradient element and one E8M0 scale byte
+ * per block of 32 consecutive elements, counted from the bucket's start:
+ * 1.03125 bytes per element.
+ *
+ * Pack, per block; bf16 and f16 inputs are widened to f32 first (exactly):
+ *   mag   = the unsigned integer maximum of bits(x) & 0x7fffffff over the
+ *           block (a NaN or inf wins it);
+ *   mag >= 0x7f800000: scale byte 0xFF, codes 0;
+ *   else  e = clamp(((mag + 0x00200000) >> 23) - 135, -127, 127), scale byte
+ *           e + 127: the smallest power of two X = 2^e with mag / X < 448 (a
+ *           mantissa fraction of 0.75 or more takes the next exponent), so the
+ *           largest element lands in [224, 448) and nothing saturates or
+ *           meets E4M3's NaN code;
+ *   code  = E4M3FN(RNE(x * 2^-e)); the product is exact and the sign is kept
+ *           (-0 is 0x80). An all-zero block has scale byte 0.
+ * Unpack: value = f32(E4M3(code)) * 2^(scale - 127), exact in f32 for every
+ * code and scale, subnormal results included; scale 0xFF makes every element
+ * of the block the NaN 0x7fc00000, so a gradient that was not finite stays
+ * not finite.
+ * |unpack(pack(x)) - x| <= max(|x| * 2^-4, X * 2^-10).
+ * Fold, for element i of a shard over the world's pieces in rank order:
+ *   s = ((v_0 + v_1) + v_2) + ... + v_{world-1} in f32, then s / np (np > 0:
+ *   a correctly rounded f32 division), then one RNE narrowing for bf16 and
+ *   f16; f32 stores the quotient.
+ *
+ * The packed form of one bucket of `count` elements over `world` ranks is
+ * `world` pieces, piece j what rank j receives: q = count / world code bytes,
+ * q / 32 scale bytes, zero bytes up to the next multiple of 16; pieces lie
+ * kf_mx8_piece_bytes(q) apart. The count % world tail is not packed.
+ *
+ * kf_mx8_pack_batch: grads[b] (dt: f32, bf16 or f16; only read) -> packed[b],
+ * world * kf_mx8_piece_bytes(counts[b] / world) bytes, every bucket and piece
+ * in one launch per 32 pieces. kf_mx8_fold_batch: packed[b], the world pieces
+ * received for this rank's shard of q[b] elements -> out_shards[b] in dt, one
+ * launch per 32 buckets. A bucket with q == 0 is not looked at. Checks, in
+ * this order and before any HIP call: nb < 0; (nb == 0: KF_OK;) a null table;
+ * dt (KF_ERR_DTYPE: f64 and the integers are refused); world outside
+ * [1, KF_MAX_INPUTS]; np < 0 (fold); then per non-empty bucket a null
+ * pointer, q % 32 != 0, a pointer off a 16-byte boundary. All KF_ERR_ARG but
+ * the dtype's, each with its kf_last_error() text. */
+size_t kf_mx8_piece_bytes(size_t q);
+int kf_mx8_pack_batch(const void *const *grads, void *const *packed, const size_t *counts, int nb,
+                      int world, KungFu_Datatype dt, void *stream);
+int kf_mx8_fold_batch(const void *const *packed, void *const *out_shards, const size_t *q, int nb,
+                      int world, KungFu_Datatype dt, int np, void *stream);
+
 /* ---- gradient monitors: segmented squared norms ------------------------- */
 
 /* What MonitorGradientNoiseScaleOptimizer and MonitorGradientVarianceOptimizer
@@ -1322,6 +1372,23 @@ int kf_exchange_adam_gated_batch(kf_exchange_t *ex, void *const *params, void *c
                                  void *const *exp_avg_sq_shards, const size_t *counts, int nb,
                                  KungFu_Datatype dt, int np, const kf_adam_hyper *hyper,
                                  const kf_step_gate *gate, const kf_step_state *state, void *stream);
+/* kf_exchange_reduce_shards_batch over the MXFP8 gradient wire (above): every
+ * bucket's world pieces packed in one launch, ONE grouped phase 1 (the
+ * all-to-all of kf_mx8_piece_bytes(q) bytes per rank and bucket, and today's
+ * all-gather of a count % world tail, unquantized), then kf_mx8_fold_batch
+ * with / world fused, into grads[b] + rank * q, and the tails' rank-order
+ * fold. *np = 0: nothing is left to divide by. Every rank's contribution, the
+ * owner's too, goes through pack and unpack, so the result does not depend on
+ * which rank owns a shard. dt is f32, bf16 or f16 (KF_ERR_DTYPE otherwise);
+ * q must be a multiple of 32 and the world at most KF_MAX_INPUTS, buckets
+ * start 16-byte aligned (KF_ERR_ARG), checked on every rank before any
+ * collective. World 1 on the built-in transport still packs and folds; only
+ * the transport call is skipped. No algo; un-pipelined; follows
+ * kf_exchange_set_timing (pack and the collectives under phase 1, the folds
+ * under phase 2). */
+int kf_exchange_reduce_shards_mx8_batch(kf_exchange_t *ex, void *const *grads,
+                                        const size_t *counts, int nb, KungFu_Datatype dt, int *np,
+                                        void *stream);
 /* recv[r * n + k] = rank r's send[k], k < n: the transport's byte all_gather
  * of n doubles per rank (device pointers; send may be recv + rank * n). World
  * 1 on the built-in transport is a copy. */

@@ -155,6 +155,10 @@ EXPORTED = (
     "kf_lars_apply_run",
     "kf_lars_apply_destroy",
     "kf_lars_apply_tile",
+    "kf_mx8_piece_bytes",
+    "kf_mx8_pack_batch",
+    "kf_mx8_fold_batch",
+    "kf_exchange_reduce_shards_mx8_batch",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -671,6 +675,17 @@ def load():
     lib.kf_adam8_quantize.restype = c_int
     lib.kf_adam8_dequantize.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
     lib.kf_adam8_dequantize.restype = c_int
+    lib.kf_mx8_piece_bytes.argtypes = [c_size_t]
+    lib.kf_mx8_piece_bytes.restype = c_size_t
+    lib.kf_mx8_pack_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_size_t), c_int, c_int, c_int,
+                                      c_void_p]
+    lib.kf_mx8_pack_batch.restype = c_int
+    lib.kf_mx8_fold_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_size_t), c_int, c_int, c_int,
+                                      c_int, c_void_p]
+    lib.kf_mx8_fold_batch.restype = c_int
+    lib.kf_exchange_reduce_shards_mx8_batch.argtypes = [c_void_p, P(c_void_p), P(c_size_t), c_int,
+                                                        c_int, P(c_int), c_void_p]
+    lib.kf_exchange_reduce_shards_mx8_batch.restype = c_int
     _lib = lib
     # HIP resources go back while the runtime is alive, before the C exit
     # handlers run (include/kungfu_amd.h kf_shutdown)

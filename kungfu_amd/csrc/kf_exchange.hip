@@ -855,6 +855,72 @@ static Reduced reduce_to_shards(kf_exchange &x, const void *const *sends, void *
     return {rc, sc.np()};
 }
 
+// reduce_to_shards over the MXFP8 gradient wire (kf_mx8.hip):
+// the buckets' pieces packed into the workspace, one grouped phase 1 (the
+// packed pieces' all-to-all and the tails' all-gather), the received pieces
+// folded into this rank's shards with / world fused, then the tails' fold.
+// A single peer on the built-in transport packs and folds too (its one piece
+// is folded where it was packed); only the transport call is skipped.
+static int reduce_to_shards_mx8(kf_exchange &x, void *const *grads, const size_t *counts, int nb,
+                                KungFu_Datatype dt, hipStream_t s)
+{
+    Schedule sc{x, counts, nb, dt, KungFu_SUM, s};
+    sc.a = KF_ALGO_REDUCE_SCATTER;  // Schedule's own all-to-all is off: fold() takes the tails only
+    const bool alone = sc.alone();
+    const size_t W   = sc.W;
+    // the workspace: per bucket the packed pieces to send, the received ones, the gathered tails
+    std::vector<size_t> send(nb, 0), qs(nb, 0);
+    sc.ws     = kf::Workspace{std::vector<size_t>(nb, 0), std::vector<size_t>(nb, 0)};
+    auto take = [&](size_t &off, size_t bytes) {
+        off = sc.ws.bytes;
+        sc.ws.bytes += align_up(bytes, 256);
+    };
+    for (int b = 0; b < nb; ++b) {
+        qs[b]              = sc.q(b);
+        const size_t bytes = W * kf_mx8_piece_bytes(qs[b]);
+        if (qs[b]) take(send[b], bytes);
+        if (qs[b] && !alone) take(sc.ws.shards[b], bytes);
+        if (alone) sc.ws.shards[b] = send[b];
+        if (sc.t(b)) take(sc.ws.tails[b], sc.t(b) * W * sc.sz);
+    }
+    if (sc.ws.bytes == 0) return KF_OK;
+    const int rc = x.ensure_ws(sc.ws.bytes, s);
+    if (rc != KF_OK) return rc;
+    sc.wsp = static_cast<char *>(x.ws);
+    std::vector<void *> packed(nb), shards(nb);
+    std::vector<const void *> recvd(nb);
+    for (int b = 0; b < nb; ++b) {
+        packed[b] = sc.wsp + send[b];
+        recvd[b]  = sc.wsp + sc.ws.shards[b];
+        shards[b] = sc.shard(static_cast<char *>(grads[b]), b);
+    }
+    auto mx8 = [](int e, const char *what) {
+        return e == KF_OK ? KF_OK : fail(e, std::string(what) + ": " + kf_last_error());
+    };
+    auto phase1 = [&] {
+        const int e = mx8(kf_mx8_pack_batch(grads, packed.data(), counts, nb, x.world, dt, s),
+                          "kf_mx8_pack_batch");
+        if (e != KF_OK || alone) return e;
+        return grouped(x, 0, nb, "phase-1 collective (MXFP8 wire)", [&](int b) {
+            int t = 0;
+            if (qs[b]) {
+                t = x.T->all_to_all(packed[b], sc.wsp + sc.ws.shards[b], kf_mx8_piece_bytes(qs[b]),
+                                    x.comm, s);
+            }
+            if (t != 0 || !sc.t(b)) return t;
+            const char *tail = sc.tail(static_cast<const char *>(grads[b]), b);
+            return x.T->all_gather(tail, sc.wsp + sc.ws.tails[b], sc.t(b) * sc.sz, x.comm, s);
+        });
+    };
+    auto folds = [&] {
+        const int e = mx8(kf_mx8_fold_batch(recvd.data(), shards.data(), qs.data(), nb, x.world, dt,
+                                            x.world, s),
+                          "kf_mx8_fold_batch");
+        return e == KF_OK ? sc.fold(grads, x.world, 0, nb, s) : e;
+    };
+    return sc.serial(phase1, folds, nothing, nothing);
+}
+
 // Phase 3 alone: every rank's shard of every bucket to all ranks, in place.
 static int gather_shards(kf_exchange &x, void *const *bufs, const size_t *counts, int nb,
                          KungFu_Datatype dt, hipStream_t s)
@@ -1857,6 +1923,33 @@ int kf_exchange_reduce_shards_batch(kf_exchange_t *ex, void *const *grads, const
     const Reduced red = reduce_to_shards(*ex, grads, grads, counts, nb, dt, KungFu_SUM, 1, algo, s);
     if (red.np >= 0) *np = red.np;
     return red.rc;
+}
+
+int kf_exchange_reduce_shards_mx8_batch(kf_exchange_t *ex, void *const *grads,
+                                        const size_t *counts, int nb, KungFu_Datatype dt, int *np,
+                                        void *stream)
+{
+    const std::string fn = "kf_exchange_reduce_shards_mx8_batch: ";
+    if (!ex || nb < 0 || !np) return fail(KF_ERR_ARG, fn + "bad arguments");
+    if (dt != KungFu_FLOAT && dt != KungFu_BFLOAT16 && dt != KungFu_FLOAT16) {
+        return fail(KF_ERR_DTYPE, fn + "f32, bf16 and f16 only");
+    }
+    if (nb > 0 && (!grads || !counts)) return fail(KF_ERR_ARG, fn + "null table");
+    if (ex->world > KF_MAX_INPUTS) return fail(KF_ERR_ARG, fn + "at most 16 ranks");
+    const size_t W = static_cast<size_t>(ex->world);
+    for (int b = 0; b < nb; ++b) {  // a count % world tail is allowed: it travels unquantized
+        if (counts[b] == 0) continue;
+        if (!grads[b]) return fail(KF_ERR_ARG, fn + "null bucket");
+        if ((counts[b] / W) % 32) {
+            return fail(KF_ERR_ARG, fn + "shard lengths (count / world) must be multiples of 32");
+        }
+        if (off16(grads[b])) return fail(KF_ERR_ARG, fn + kShardOff16);
+    }
+    DeviceGuard g(ex->device);
+    std::lock_guard<std::mutex> lk(ex->mu);
+    const int rc = reduce_to_shards_mx8(*ex, grads, counts, nb, dt, static_cast<hipStream_t>(stream));
+    if (rc == KF_OK) *np = 0;
+    return rc;
 }
 
 int kf_exchange_adam_gated_batch(kf_exchange_t *ex, void *const *params, void *const *grads,

@@ -32,6 +32,7 @@ from .base import OP, OP_NAMES
 from .ops import kungfu_dtype
 
 ALGOS = {"auto": 0, "rs": 1, "a2a": 2, "rs_avg": 3}
+GRAD_WIRES = (None, "mx8")  # NativeExchange.set_grad_wire
 # kf_exchange_phase_times' order: phase 1 (reduce-scatter, or all-to-all for
 # the rank-order fold), phase 2 (/np epilogue or the fold), phase 3
 # (all-gather), the SMA blend
@@ -133,6 +134,24 @@ class NativeExchange:
         _lib.check(self.lib.kf_exchange_set_pipeline(self._h, int(groups)),
                    "kf_exchange_set_pipeline")
         self.groups = int(groups)
+        return self
+
+    def set_grad_wire(self, wire):
+        """What phase 1 of the sharded steps carries: None (the default), the
+        gradient buckets in their own dtype, or "mx8", block-scaled MXFP8 (one
+        E4M3 code per element and one E8M0 scale byte per 32: 1.03125 bytes per
+        element). With "mx8", reduce_shards_ packs every
+        bucket's pieces, exchanges them and folds the received ones in f32 in
+        rank order with / world fused (kf_exchange_reduce_shards_mx8_batch) and
+        returns 0; sgd_step_, adam_step_ and adam_master_step_ are then
+        reduce_shards_, the update kernel on the shards and gather_params_.
+        Shard lengths must be multiples of 32 (the optimizers' are). A lossy
+        wire: |error| <= 2^-4 |x| per element and rank. all_reduce_, start_,
+        start_into_, sma_ and all_reduce_named ignore the setting: variables
+        and SMA sums are not gradients."""
+        if wire not in GRAD_WIRES:
+            raise ValueError("grad_wire must be None or 'mx8' (got %r)" % (wire,))
+        self._wire = wire
         return self
 
     def set_timing(self, on):
@@ -259,6 +278,10 @@ class NativeExchange:
         they hold nothing defined afterwards."""
         params = list(param_buckets)
         moms = [None] * len(params) if mom_shards is None else mom_shards
+        if getattr(self, "_wire", None):
+            from . import ops
+            return self._wired_step("sgd_step_", ops.sgd_update_batch_, params, grad_buckets,
+                                    (moms,), hypers)
         return self._shard_call("sgd_step_", self.lib.kf_exchange_sgd_batch,
                                 "kf_exchange_sgd_batch", _lib.sgd_hyper_array, params,
                                 grad_buckets, (moms,), hypers)
@@ -272,6 +295,10 @@ class NativeExchange:
         numel // world elements of the parameters' dtype (f32, bf16 or f64).
         The gradient buckets are scratch: they hold nothing defined
         afterwards."""
+        if getattr(self, "_wire", None):
+            from . import ops
+            return self._wired_step("adam_step_", ops.adam_update_batch_, param_buckets,
+                                    grad_buckets, (exp_avg_shards, exp_avg_sq_shards), hypers)
         return self._shard_call("adam_step_", self.lib.kf_exchange_adam_batch,
                                 "kf_exchange_adam_batch", _lib.adam_hyper_array, param_buckets,
                                 grad_buckets, (exp_avg_shards, exp_avg_sq_shards), hypers)
@@ -284,6 +311,11 @@ class NativeExchange:
         on this rank's shard of every bucket with its fp32 master, exp_avg and
         exp_avg_sq shards of numel // world elements each. The gradient
         buckets are scratch."""
+        if getattr(self, "_wire", None):
+            from . import ops
+            return self._wired_step("adam_master_step_", ops.adam_master_update_batch_,
+                                    param_buckets, grad_buckets,
+                                    (master_shards, exp_avg_shards, exp_avg_sq_shards), hypers)
         return self._shard_call("adam_master_step_", self.lib.kf_exchange_adam_master_batch,
                                 "kf_exchange_adam_master_batch", _lib.adam_hyper_array,
                                 param_buckets, grad_buckets,
@@ -311,6 +343,23 @@ class NativeExchange:
                 torch.cuda.current_stream(self.device).cuda_stream)
         _lib.check(rc, cname)
         return params
+
+    def _wired_step(self, name, update, param_buckets, grad_buckets, state_shards, hypers):
+        """sgd_step_, adam_step_ and adam_master_step_ under set_grad_wire:
+        reduce_shards_ over the wire, `update` (the ops.*_update_batch_ whose
+        kernel the fused call runs) on this rank's shards with nothing left to
+        divide by, gather_params_."""
+        params, grads, hypers = list(param_buckets), list(grad_buckets), list(hypers)
+        states = [list(s) for s in state_shards]
+        if not all(len(x) == len(params) for x in [grads, hypers] + states):
+            raise ValueError("%s: one grad bucket, %d state shards and a hyper per bucket"
+                             % (name, len(states)))
+        if not params:
+            return params
+        self._shard_tables(name, params, grads, states)
+        np_ = self.reduce_shards_(grads)
+        update(self.grad_shards_(params), self.grad_shards_(grads), *states, hypers, np_=np_)
+        return self.gather_params_(params)
 
     def _shard_tables(self, name, params, grads, states):
         """The checks of a sharded step's tables (_shard_call and the gated
@@ -344,12 +393,20 @@ class NativeExchange:
         """Half one (kf_exchange_reduce_shards_batch): phase 1 and the
         rank-order folds, queued on the current stream. Returns what the
         update must still divide by: the world after a reduce-scatter, 0 after
-        the fold or under rs_avg, 1 at world 1 on the built-in transport."""
+        the fold or under rs_avg, 1 at world 1 on the built-in transport.
+        Under set_grad_wire("mx8"): kf_exchange_reduce_shards_mx8_batch, and 0."""
         grads = list(grad_buckets)
         if grads:
             self._check(grads)
         np_ = ctypes.c_int(0)
         dt = int(kungfu_dtype(grads[0])) if grads else 0x20408
+        if getattr(self, "_wire", None):  # "mx8": the only wire
+            rc = self.lib.kf_exchange_reduce_shards_mx8_batch(
+                self._h, _lib.ptr_array([g.data_ptr() for g in grads]),
+                _arr(ctypes.c_size_t, [g.numel() for g in grads]), len(grads), dt,
+                ctypes.byref(np_), torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(rc, "kf_exchange_reduce_shards_mx8_batch")
+            return np_.value
         rc = self.lib.kf_exchange_reduce_shards_batch(
             self._h, _lib.ptr_array([g.data_ptr() for g in grads]),
             _arr(ctypes.c_size_t, [g.numel() for g in grads]), len(grads), dt, ALGOS[self.algo],

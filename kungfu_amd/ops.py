@@ -625,6 +625,71 @@ def adam8_dequantize(codes, scales, which, out=None, stream=None):
     return out
 
 
+# -- the MXFP8 gradient wire (include/kungfu_amd.h) -------------
+
+MX8_BLOCK = 32                   # elements per scale byte
+
+
+def mx8_piece_bytes(q):
+    """The bytes of one packed piece of q elements (kf_mx8_piece_bytes): q
+    codes, q // 32 scale bytes, rounded up to 16."""
+    return int(_lib.load().kf_mx8_piece_bytes(int(q)))
+
+
+def mx8_pack_batch_(grads, world, packed=None, stream=None):
+    """Every flat f32, bf16 or f16 bucket of `grads` as `world` packed MXFP8
+    pieces (kf_mx8_pack_batch), all buckets in one launch: packed[b] is a uint8
+    tensor of world * mx8_piece_bytes(numel // world) bytes, new unless given;
+    piece j is what rank j receives. numel // world must be a multiple of 32;
+    the numel % world tail is not packed. grads are only read."""
+    grads, world = list(grads), int(world)
+    if world < 1:
+        raise ValueError("mx8_pack_batch_: world >= 1")
+    need = [world * mx8_piece_bytes(g.numel() // world) for g in grads]
+    if packed is None:
+        packed = [torch.empty(n, dtype=torch.uint8, device=g.device) for n, g in zip(need, grads)]
+    packed = list(packed)
+    if len(packed) != len(grads):
+        raise ValueError("mx8_pack_batch_: one packed tensor per bucket")
+    if not grads:
+        return packed
+    _check_dev(grads + packed)
+    for g, p, n in zip(grads, packed, need):
+        if g.dtype != grads[0].dtype or p.dtype != torch.uint8 or p.numel() != n:
+            raise ValueError("mx8_pack_batch_: one dtype, and uint8 tensors of world pieces")
+    cnt = (ctypes.c_size_t * len(grads))(*[g.numel() for g in grads])
+    rc = _lib.load().kf_mx8_pack_batch(_lib.ptr_array([g.data_ptr() for g in grads]),
+                                       _lib.ptr_array([p.data_ptr() for p in packed]), cnt,
+                                       len(grads), world, int(kungfu_dtype(grads[0])),
+                                       _stream(stream, grads[0].device))
+    _lib.check(rc, "kf_mx8_pack_batch", source="")
+    return packed
+
+
+def mx8_fold_batch_(packed, out_shards, world, np_=0, stream=None):
+    """out_shards[b] = (the `world` pieces of packed[b], unpacked and added in
+    f32 in rank order) / np_ (np_ > 0), narrowed once to the shard's dtype
+    (kf_mx8_fold_batch), all buckets in one launch. packed[b]: uint8, world *
+    mx8_piece_bytes(q) bytes for a shard of q elements (a multiple of 32)."""
+    packed, outs, world = list(packed), list(out_shards), int(world)
+    if len(packed) != len(outs):
+        raise ValueError("mx8_fold_batch_: one shard per packed tensor")
+    if not outs:
+        return outs
+    _check_dev(packed + outs)
+    for p, o in zip(packed, outs):
+        if o.dtype != outs[0].dtype or p.dtype != torch.uint8 or \
+                p.numel() != world * mx8_piece_bytes(o.numel()):
+            raise ValueError("mx8_fold_batch_: one dtype, and uint8 tensors of world pieces")
+    q = (ctypes.c_size_t * len(outs))(*[o.numel() for o in outs])
+    rc = _lib.load().kf_mx8_fold_batch(_lib.ptr_array([p.data_ptr() for p in packed]),
+                                       _lib.ptr_array([o.data_ptr() for o in outs]), q, len(outs),
+                                       world, int(kungfu_dtype(outs[0])), int(np_),
+                                       _stream(stream, outs[0].device))
+    _lib.check(rc, "kf_mx8_fold_batch", source="")
+    return outs
+
+
 # -- LAMB (include/kungfu_amd.h "LAMB", DESIGN.md §17) -------------------------
 
 def lamb_moments_batch_(params, grads, exp_avgs, exp_avg_sqs, updates, hypers, np_=0, stream=None):
