@@ -789,6 +789,46 @@ int kf_mx8_pack_batch(const void *const *grads, void *const *packed, const size_
 int kf_mx8_fold_batch(const void *const *packed, void *const *out_shards, const size_t *q, int nb,
                       int world, KungFu_Datatype dt, int np, void *stream);
 
+/* Two more packs for the same format, fold and piece layout (DESIGN.md §25;
+ * tests/mx8_ef_sr_ref.py restates them): round-to-nearest packs the same
+ * input the same way at every step, so what it drops is dropped for good.
+ *
+ * kf_mx8_pack_ef_batch, error feedback. residuals[b] holds counts[b] f32
+ * values, one per element of grads[b]. Per element of a piece:
+ *   s  = widen(g) + r            one f32 add
+ *   scale byte and code from s as kf_mx8_pack_batch makes them from g
+ *   r' = s - unpack(code, scale) one f32 subtract, stored over r
+ * so that what this call drops the next one sends. A block whose scale byte
+ * is 0xFF (some s is not finite) has codes 0 and its 32 residuals +0.0. The
+ * gradients are only read; the count % world tail's residuals are neither
+ * read nor written.
+ *
+ * kf_mx8_pack_sr_batch, stochastic rounding. The scale byte is kf_mx8_pack_
+ * batch's. With y = x * 2^-e (exact, or below every code), t = |y| and a
+ * 16-bit draw r16:
+ *   t >= 2^-6: code_mag = ((bits(t) + (r16 << 4)) >> 20) - 960
+ *   t <  2^-6: code_mag = (trunc_u32(t * 2^29) + (r16 << 4)) >> 20
+ *   code = sign(x) << 7 | code_mag
+ * E[unpack] = x; a value that is an E4M3 value at its scale is returned
+ * whatever the draw; the largest code reached is 448 (0x7e). A 0xFF block is
+ * as above. The draws are a pure function of (seed, step, rank, bucket index
+ * bucket0 + b, element index i in the bucket) and of nothing else:
+ *   w = splitmix64(splitmix64(splitmix64(seed) ^ step) ^ (rank << 32 | bucket))
+ *   (a, b) = philox2x32_10(c0 = i >> 2, c1 = high32(w), key = low32(w))
+ *   r16 = (a >> 16, a & 0xffff, b >> 16, b & 0xffff)[i & 3]
+ * with splitmix64 and Philox2x32-10 as under "Adam, stochastic rounding".
+ * Ranks, steps and buckets round independently; the same five inputs give
+ * the same bits whatever the launch geometry.
+ *
+ * Both make kf_mx8_pack_batch's checks in its order, then: a null residual
+ * table, and per non-empty bucket a null residual, a residual off a 16-byte
+ * boundary (ef); rank outside [0, world), bucket0 < 0 (sr). KF_ERR_ARG. */
+int kf_mx8_pack_ef_batch(const void *const *grads, void *const *residuals, void *const *packed,
+                         const size_t *counts, int nb, int world, KungFu_Datatype dt, void *stream);
+int kf_mx8_pack_sr_batch(const void *const *grads, void *const *packed, const size_t *counts, int nb,
+                         int world, KungFu_Datatype dt, uint64_t seed, uint64_t step, int rank,
+                         int bucket0, void *stream);
+
 /* ---- gradient monitors: segmented squared norms ------------------------- */
 
 /* What MonitorGradientNoiseScaleOptimizer and MonitorGradientVarianceOptimizer
@@ -1389,6 +1429,20 @@ int kf_exchange_adam_gated_batch(kf_exchange_t *ex, void *const *params, void *c
 int kf_exchange_reduce_shards_mx8_batch(kf_exchange_t *ex, void *const *grads,
                                         const size_t *counts, int nb, KungFu_Datatype dt, int *np,
                                         void *stream);
+/* kf_exchange_reduce_shards_mx8_batch with kf_mx8_pack_ef_batch or kf_mx8_
+ * pack_sr_batch as its pack; workspace, grouped phase 1, fold, tails, timing
+ * and the world-1 built-in transport are the same. _ef: residuals[b] is a
+ * device buffer of counts[b] f32 values, 16-byte aligned, that the caller
+ * keeps from step to step (zeros before the first); a null table or entry is
+ * KF_ERR_ARG. _sr: the draws are kf_mx8_pack_sr_batch's at the exchange's own
+ * rank and bucket0 = 0; `step` is a host-side argument, so a captured graph
+ * replays the draws of the step it was captured at. */
+int kf_exchange_reduce_shards_mx8_ef_batch(kf_exchange_t *ex, void *const *grads,
+                                           void *const *residuals, const size_t *counts, int nb,
+                                           KungFu_Datatype dt, int *np, void *stream);
+int kf_exchange_reduce_shards_mx8_sr_batch(kf_exchange_t *ex, void *const *grads,
+                                           const size_t *counts, int nb, KungFu_Datatype dt,
+                                           uint64_t seed, uint64_t step, int *np, void *stream);
 /* recv[r * n + k] = rank r's send[k], k < n: the transport's byte all_gather
  * of n doubles per rank (device pointers; send may be recv + rank * n). World
  * 1 on the built-in transport is a copy. */

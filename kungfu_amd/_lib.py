@@ -159,6 +159,10 @@ EXPORTED = (
     "kf_mx8_pack_batch",
     "kf_mx8_fold_batch",
     "kf_exchange_reduce_shards_mx8_batch",
+    "kf_mx8_pack_ef_batch",
+    "kf_mx8_pack_sr_batch",
+    "kf_exchange_reduce_shards_mx8_ef_batch",
+    "kf_exchange_reduce_shards_mx8_sr_batch",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -686,6 +690,19 @@ def load():
     lib.kf_exchange_reduce_shards_mx8_batch.argtypes = [c_void_p, P(c_void_p), P(c_size_t), c_int,
                                                         c_int, P(c_int), c_void_p]
     lib.kf_exchange_reduce_shards_mx8_batch.restype = c_int
+    c_u64 = ctypes.c_uint64
+    lib.kf_mx8_pack_ef_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_size_t), c_int,
+                                         c_int, c_int, c_void_p]
+    lib.kf_mx8_pack_ef_batch.restype = c_int
+    lib.kf_mx8_pack_sr_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_size_t), c_int, c_int, c_int,
+                                         c_u64, c_u64, c_int, c_int, c_void_p]
+    lib.kf_mx8_pack_sr_batch.restype = c_int
+    lib.kf_exchange_reduce_shards_mx8_ef_batch.argtypes = [
+        c_void_p, P(c_void_p), P(c_void_p), P(c_size_t), c_int, c_int, P(c_int), c_void_p]
+    lib.kf_exchange_reduce_shards_mx8_ef_batch.restype = c_int
+    lib.kf_exchange_reduce_shards_mx8_sr_batch.argtypes = [
+        c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_u64, c_u64, P(c_int), c_void_p]
+    lib.kf_exchange_reduce_shards_mx8_sr_batch.restype = c_int
     _lib = lib
     # HIP resources go back while the runtime is alive, before the C exit
     # handlers run (include/kungfu_amd.h kf_shutdown)

@@ -38,6 +38,7 @@
 #include <string>
 
 #include "kf_adam_math.hpp"
+#include "kf_philox.hpp"
 #include "kf_update_batch.hpp"
 
 // Load / store policy of the streams, 1 = non-temporal: kf_adam.hip's. g is
@@ -86,34 +87,7 @@ static_assert(sizeof(AdamSrArgs) + sizeof(Div) + sizeof(uint32_t) <= 3072, "kern
 static_assert(sizeof(AdamSrArgs) + sizeof(AdamSrSeg) + 4 + sizeof(Div) + sizeof(uint32_t) > 3072,
               "kAdamSrSeg is the most the budget holds");
 
-// Philox2x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2,
-// 3"): ten rounds of {hi(M * c0) ^ key ^ c1, lo(M * c0)}, the key bumped by
-// the golden ratio between rounds. The key sequence is wave-uniform.
-struct Philox2 {
-    uint32_t a, b;
-};
-// hi ^ key ^ c1 as one three-input bit operation where the target has one
-// (truth table 0x96); key is wave-uniform.
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
-{
-#if __has_builtin(__builtin_amdgcn_bitop3_b32)
-    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-#else
-    return a ^ b ^ c;
-#endif
-}
-__device__ __forceinline__ Philox2 philox2x32_10(uint32_t c0, uint32_t c1, uint32_t key)
-{
-    constexpr uint32_t M = 0xD256D193u, W = 0x9E3779B9u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t prod = static_cast<uint64_t>(M) * c0;
-        c0 = xor3(static_cast<uint32_t>(prod >> 32), key, c1);
-        c1 = static_cast<uint32_t>(prod);
-        key += W;
-    }
-    return Philox2{c0, c1};
-}
+// philox2x32_10 (Philox2x32-10, Salmon et al.) is kf_philox.hpp's.
 
 // sr(x, rx) in the low half and sr(y, ry) in the high half of one word,
 // rx, ry < 2^16: the header comment's narrowing, without a branch. A finite

@@ -50,6 +50,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <numeric>
@@ -861,8 +862,14 @@ static Reduced reduce_to_shards(kf_exchange &x, const void *const *sends, void *
 // folded into this rank's shards with / world fused, then the tails' fold.
 // A single peer on the built-in transport packs and folds too (its one piece
 // is folded where it was packed); only the transport call is skipped.
+// `pack` is the entry that fills the pieces: kf_mx8_pack_batch, or its
+// error-feedback or stochastic-rounding variant.
+struct Mx8Pack {
+    const char *name;
+    std::function<int(void *const *packed, hipStream_t s)> run;
+};
 static int reduce_to_shards_mx8(kf_exchange &x, void *const *grads, const size_t *counts, int nb,
-                                KungFu_Datatype dt, hipStream_t s)
+                                KungFu_Datatype dt, hipStream_t s, const Mx8Pack &pack)
 {
     Schedule sc{x, counts, nb, dt, KungFu_SUM, s};
     sc.a = KF_ALGO_REDUCE_SCATTER;  // Schedule's own all-to-all is off: fold() takes the tails only
@@ -898,8 +905,7 @@ static int reduce_to_shards_mx8(kf_exchange &x, void *const *grads, const size_t
         return e == KF_OK ? KF_OK : fail(e, std::string(what) + ": " + kf_last_error());
     };
     auto phase1 = [&] {
-        const int e = mx8(kf_mx8_pack_batch(grads, packed.data(), counts, nb, x.world, dt, s),
-                          "kf_mx8_pack_batch");
+        const int e = mx8(pack.run(packed.data(), s), pack.name);
         if (e != KF_OK || alone) return e;
         return grouped(x, 0, nb, "phase-1 collective (MXFP8 wire)", [&](int b) {
             int t = 0;
@@ -1925,16 +1931,18 @@ int kf_exchange_reduce_shards_batch(kf_exchange_t *ex, void *const *grads, const
     return red.rc;
 }
 
-int kf_exchange_reduce_shards_mx8_batch(kf_exchange_t *ex, void *const *grads,
-                                        const size_t *counts, int nb, KungFu_Datatype dt, int *np,
-                                        void *stream)
+// What the three MXFP8 reduce entries share: `entry`'s checks, then
+// reduce_to_shards_mx8 with `pack`; `residuals`: the error-feedback entry's table.
+static int exchange_reduce_mx8(const char *entry, kf_exchange_t *ex, void *const *grads,
+                               void *const *residuals, bool ef, const size_t *counts, int nb,
+                               KungFu_Datatype dt, int *np, void *stream, const Mx8Pack &pack)
 {
-    const std::string fn = "kf_exchange_reduce_shards_mx8_batch: ";
+    const std::string fn = std::string(entry) + ": ";
     if (!ex || nb < 0 || !np) return fail(KF_ERR_ARG, fn + "bad arguments");
     if (dt != KungFu_FLOAT && dt != KungFu_BFLOAT16 && dt != KungFu_FLOAT16) {
         return fail(KF_ERR_DTYPE, fn + "f32, bf16 and f16 only");
     }
-    if (nb > 0 && (!grads || !counts)) return fail(KF_ERR_ARG, fn + "null table");
+    if (nb > 0 && (!grads || !counts || (ef && !residuals))) return fail(KF_ERR_ARG, fn + "null table");
     if (ex->world > KF_MAX_INPUTS) return fail(KF_ERR_ARG, fn + "at most 16 ranks");
     const size_t W = static_cast<size_t>(ex->world);
     for (int b = 0; b < nb; ++b) {  // a count % world tail is allowed: it travels unquantized
@@ -1944,12 +1952,49 @@ int kf_exchange_reduce_shards_mx8_batch(kf_exchange_t *ex, void *const *grads,
             return fail(KF_ERR_ARG, fn + "shard lengths (count / world) must be multiples of 32");
         }
         if (off16(grads[b])) return fail(KF_ERR_ARG, fn + kShardOff16);
+        if (ef && (!residuals[b] || off16(residuals[b]))) {
+            return fail(KF_ERR_ARG, fn + "every non-empty bucket needs a 16-byte aligned residual");
+        }
     }
     DeviceGuard g(ex->device);
     std::lock_guard<std::mutex> lk(ex->mu);
-    const int rc = reduce_to_shards_mx8(*ex, grads, counts, nb, dt, static_cast<hipStream_t>(stream));
+    const int rc = reduce_to_shards_mx8(*ex, grads, counts, nb, dt, static_cast<hipStream_t>(stream), pack);
     if (rc == KF_OK) *np = 0;
     return rc;
+}
+
+int kf_exchange_reduce_shards_mx8_batch(kf_exchange_t *ex, void *const *grads,
+                                        const size_t *counts, int nb, KungFu_Datatype dt, int *np,
+                                        void *stream)
+{
+    return exchange_reduce_mx8(
+        "kf_exchange_reduce_shards_mx8_batch", ex, grads, nullptr, false, counts, nb, dt, np, stream,
+        {"kf_mx8_pack_batch", [&](void *const *packed, hipStream_t s) {
+             return kf_mx8_pack_batch(grads, packed, counts, nb, ex->world, dt, s);
+         }});
+}
+
+int kf_exchange_reduce_shards_mx8_ef_batch(kf_exchange_t *ex, void *const *grads,
+                                           void *const *residuals, const size_t *counts, int nb,
+                                           KungFu_Datatype dt, int *np, void *stream)
+{
+    return exchange_reduce_mx8(
+        "kf_exchange_reduce_shards_mx8_ef_batch", ex, grads, residuals, true, counts, nb, dt, np,
+        stream, {"kf_mx8_pack_ef_batch", [&](void *const *packed, hipStream_t s) {
+                     return kf_mx8_pack_ef_batch(grads, residuals, packed, counts, nb, ex->world, dt, s);
+                 }});
+}
+
+int kf_exchange_reduce_shards_mx8_sr_batch(kf_exchange_t *ex, void *const *grads,
+                                           const size_t *counts, int nb, KungFu_Datatype dt,
+                                           uint64_t seed, uint64_t step, int *np, void *stream)
+{
+    return exchange_reduce_mx8(
+        "kf_exchange_reduce_shards_mx8_sr_batch", ex, grads, nullptr, false, counts, nb, dt, np,
+        stream, {"kf_mx8_pack_sr_batch", [&](void *const *packed, hipStream_t s) {
+                     return kf_mx8_pack_sr_batch(grads, packed, counts, nb, ex->world, dt, seed, step,
+                                                 ex->rank, 0, s);
+                 }});
 }
 
 int kf_exchange_adam_gated_batch(kf_exchange_t *ex, void *const *params, void *const *grads,

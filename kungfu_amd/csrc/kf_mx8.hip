@@ -52,6 +52,12 @@
 //   * unpack: its elements are the one quiet NaN 0x7fc00000 by a select (the
 //     instruction gives a NaN with the sign bit set).
 //
+// Two more pack kernels, mx8_pack_ef_kernel (error feedback: a f32 residual
+// carried from step to step) and mx8_pack_sr_kernel (stochastic rounding with
+// Philox draws), share the pack's skeleton; they are described where they
+// stand, and in DESIGN.md §25. The format, the fold and the plain pack are
+// the same under all three.
+//
 // No contraction (the pragma of kf_reduce_kernels.hpp and -ffp-contract=off),
 // no LDS, no scratch.
 #include <hip/hip_runtime.h>
@@ -59,6 +65,7 @@
 #include <string>
 #include <vector>
 
+#include "kf_philox.hpp"
 #include "kf_sgd_elt.hpp"
 #include "kf_update_batch.hpp"
 
@@ -194,6 +201,169 @@ template <typename T> __global__ void __launch_bounds__(kMx8Block) mx8_pack_kern
     mx8_pack_body<T>(g, blk, nblk);
 }
 
+// ---- pack with error feedback, pack with stochastic rounding --------------------
+// mx8_pack_body's skeleton (tiles, quads, the scale byte, both stores, the
+// shard that ends inside a tile) with another element step each.
+//
+// Error feedback (EF-SGD, 1-bit Adam): s = widen(g) + r with the f32 residual
+// r of the same bucket index, scale and codes from s as mx8_pack_body makes
+// them from g, d = the codes unpacked in registers (v_cvt_scalef32_pk_f32_fp8
+// on the two code dwords the lane is about to store), r' = s - d stored over
+// r. A block that is not finite (scale byte 0xFF) leaves 32 residuals of
+// +0.0. The residual moves as two 16-byte loads and two 16-byte stores per
+// lane; the policy is KF_MX8_EF_R_NT / KF_MX8_EF_ST_NT (DESIGN.md §25 has the
+// A/B): 8 more bytes per element than the plain pack. The gradients are only
+// read.
+//
+// Stochastic rounding. The scale byte is the plain pack's. With y = x * 2^-e
+// (one v_ldexp_f32: exact unless y is an f32 subnormal, far below what any
+// draw can lift to a code), t = |y| and a 16-bit draw r16:
+//   t >= 2^-6: code_mag = ((bits(t) + (r16 << 4)) >> 20) - 960
+//   t <  2^-6: code_mag = (trunc_u32(t * 2^29) + (r16 << 4)) >> 20   (0 .. 8)
+//   code = sign(x) << 7 | code_mag
+// 20 mantissa bits are dropped either way (below 2^-6 the unit is E4M3's
+// subnormal step 2^-9, so t * 2^29 counts it in 2^-20ths), r16 << 4 is a
+// uniform 20-bit addend with four zero bits below, and a value that is an
+// E4M3 value at its scale has those 20 bits zero: it is returned whatever the
+// draw. The block's largest element is below 448, so rounding up ends at 448
+// (0x7e), never at the NaN code. Plain integer ALU; the hardware's *_sr_*
+// conversions were not taken.
+//
+// The draws are a pure function of (seed, step, rank, bucket index, element
+// index in the bucket); launch geometry and the segment split play no part.
+// The host folds the first four into two words per bucket,
+//   w = splitmix64(splitmix64(splitmix64(seed) ^ step) ^ (rank << 32 | bucket))
+//   key = low32(w), c1 = high32(w)
+// and one Philox2x32-10 evaluation serves the four consecutive elements
+// 4c .. 4c + 3 of the bucket: (a, b) = philox2x32_10(c0 = c, c1, key), draws
+// a >> 16, a & 0xffff, b >> 16, b & 0xffff. A lane's 8 elements start at a
+// multiple of 8 (pieces are whole blocks), so it makes two evaluations.
+#ifndef KF_MX8_EF_R_NT
+#define KF_MX8_EF_R_NT 0  // the residual's loads, 1 = non-temporal
+#endif
+#ifndef KF_MX8_EF_ST_NT
+#define KF_MX8_EF_ST_NT 0  // the residual's stores
+#endif
+
+struct Mx8EfSeg {
+    const void *src;  // as Mx8PackSeg
+    void *dst;
+    size_t n;
+    void *res;  // the piece's q f32 residuals, read and written
+};
+struct Mx8SrSeg {
+    const void *src;
+    void *dst;
+    size_t n;
+    uint64_t base;         // the bucket index of the piece's first element, a multiple of 32
+    uint32_t key, stream;  // Philox key and counter word c1 of the bucket
+};
+template <typename SEG> struct Mx8VarArgs {
+    SEG seg[kMx8Seg];
+    unsigned blk0[kMx8Seg + 1];
+    int nseg;
+};
+static_assert(sizeof(Mx8VarArgs<Mx8SrSeg>) <= 1536, "kernarg budget");
+
+// one element's code under the draw r16 < 2^16; nege = -e. The arm that is
+// not taken converts a clamped t, so that the conversion is always in range.
+__device__ __forceinline__ unsigned mx8_sr_code(float x, int nege, uint32_t r16)
+{
+    const unsigned b = __float_as_uint(ldexpf(x, nege));
+    const unsigned t = b & 0x7fffffffu, r = r16 << 4;
+    const unsigned normal = ((t + r) >> 20) - 960u;
+    const unsigned sub    = (static_cast<unsigned>(__uint_as_float(min(t, 0x3c800000u)) * 0x1p29f) + r) >> 20;
+    return ((b >> 31) << 7) | (t >= 0x3c800000u ? normal : sub);
+}
+
+// four elements, the bucket's elements 4 * c0 .. 4 * c0 + 3 -> four codes in a dword
+__device__ __forceinline__ unsigned mx8_sr4(const float *x, int nege, uint32_t c0, const Mx8SrSeg &h)
+{
+    const Philox2 p = philox2x32_10(c0, h.stream, h.key);
+    return mx8_sr_code(x[0], nege, p.a >> 16) | (mx8_sr_code(x[1], nege, p.a & 0xffffu) << 8) |
+           (mx8_sr_code(x[2], nege, p.b >> 16) << 16) | (mx8_sr_code(x[3], nege, p.b & 0xffffu) << 24);
+}
+
+template <typename T, typename SEG>
+__device__ __forceinline__ void mx8_pack_var_body(const SEG &h, size_t blk, size_t nblk)
+{
+    constexpr bool EF   = std::is_same<SEG, Mx8EfSeg>::value;
+    constexpr int B     = kMx8Block;
+    const size_t nunit  = h.n / kMx8PackElts;
+    const size_t ntiles = (nunit + B - 1) / B;
+    char *codes         = static_cast<char *>(h.dst);
+    char *scales        = codes + h.n;
+    // uniform over the workgroup: every lane takes every cross-lane step
+    for (size_t t = blk; t < ntiles; t += nblk) {
+        const size_t u    = t * B + threadIdx.x;
+        const bool active = u < nunit;  // uniform over a quad: n % 32 == 0
+        float x[8];
+        mx8_load8<T>(h.src, u, active, x);
+        if constexpr (EF) {
+            u32x4 r0 = {0, 0, 0, 0}, r1 = {0, 0, 0, 0};
+            if (active) {
+                r0 = ld_u4<KF_MX8_EF_R_NT>(h.res, 2 * u);
+                r1 = ld_u4<KF_MX8_EF_R_NT>(h.res, 2 * u + 1);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                x[i]     = __fadd_rn(x[i], __uint_as_float(r0[i]));
+                x[4 + i] = __fadd_rn(x[4 + i], __uint_as_float(r1[i]));
+            }
+        }
+        unsigned mag = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) mag = max(mag, __float_as_uint(x[i]) & 0x7fffffffu);
+        const unsigned byte = mx8_scale_byte(mx8_quad_max(mag));
+        const float scale   = __uint_as_float(byte << 23);  // the instructions read the exponent field
+        mx8_u32x2 out;
+        if constexpr (EF) {
+            out = mx8_u32x2{mx8_cvt4(x[0], x[1], x[2], x[3], scale),
+                            mx8_cvt4(x[4], x[5], x[6], x[7], scale)};
+        } else {
+            const int nege    = 127 - static_cast<int>(byte);
+            const uint32_t c0 = static_cast<uint32_t>((h.base + u * kMx8PackElts) >> 2);
+            out = mx8_u32x2{mx8_sr4(x, nege, c0, h), mx8_sr4(x + 4, nege, c0 + 1, h)};
+        }
+        if (byte == 0xffu) out = mx8_u32x2{0, 0};
+        const u32x4 sc = mx8_wave_scales(byte);
+        if (active) reinterpret_cast<mx8_u32x2 *>(codes)[u] = out;
+        const size_t uw = u & ~static_cast<size_t>(63);  // the wave's first unit
+        if ((threadIdx.x & 63u) == 0 && uw < nunit) st_u4<0>(scales, uw / 64, sc);
+        if constexpr (EF) {
+            u32x4 r[2];
+#pragma unroll
+            for (int w = 0; w < 2; ++w) {
+                const f32x2 lo = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(out[w], scale, false);
+                const f32x2 hi = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(out[w], scale, true);
+                r[w] = u32x4{__float_as_uint(__fsub_rn(x[4 * w], lo.x)),
+                             __float_as_uint(__fsub_rn(x[4 * w + 1], lo.y)),
+                             __float_as_uint(__fsub_rn(x[4 * w + 2], hi.x)),
+                             __float_as_uint(__fsub_rn(x[4 * w + 3], hi.y))};
+                if (byte == 0xffu) r[w] = u32x4{0, 0, 0, 0};
+            }
+            if (active) {
+                st_u4<KF_MX8_EF_ST_NT>(h.res, 2 * u, r[0]);
+                st_u4<KF_MX8_EF_ST_NT>(h.res, 2 * u + 1, r[1]);
+            }
+        }
+    }
+}
+
+template <typename T> __global__ void __launch_bounds__(kMx8Block) mx8_pack_ef_kernel(Mx8VarArgs<Mx8EfSeg> a)
+{
+    size_t blk, nblk;
+    const Mx8EfSeg &g = a.seg[batch_segment(a, blk, nblk)];
+    mx8_pack_var_body<T>(g, blk, nblk);
+}
+
+template <typename T> __global__ void __launch_bounds__(kMx8Block) mx8_pack_sr_kernel(Mx8VarArgs<Mx8SrSeg> a)
+{
+    size_t blk, nblk;
+    const Mx8SrSeg &g = a.seg[batch_segment(a, blk, nblk)];
+    mx8_pack_var_body<T>(g, blk, nblk);
+}
+
 // ---- fold ---------------------------------------------------------------------
 struct Mx8FoldSeg {
     const void *pk;  // the world received pieces of this rank's shard, `stride` apart
@@ -312,6 +482,8 @@ namespace
 using namespace kf;
 
 constexpr UpdateFail fail_pack{"kf_mx8_pack_batch"};
+constexpr UpdateFail fail_pack_ef{"kf_mx8_pack_ef_batch"};
+constexpr UpdateFail fail_pack_sr{"kf_mx8_pack_sr_batch"};
 constexpr UpdateFail fail_fold{"kf_mx8_fold_batch"};
 
 size_t piece_bytes(size_t q) { return (q + q / kMx8Blk + 15) / 16 * 16; }
@@ -365,6 +537,58 @@ int launch_pack(const void *const *grads, void *const *packed, const size_t *cou
         });
 }
 
+// The pack variants: launch_pack's segments, `fill(seg, b, j, q)` adding what
+// the variant's segment holds beyond src, dst and n.
+template <typename T, typename SEG, typename KERNEL, typename FILL>
+int launch_pack_var(const UpdateFail &fail, KERNEL kernel, const void *const *grads,
+                    void *const *packed, const size_t *counts, int nb, int world, hipStream_t s,
+                    FILL &&fill)
+{
+    const size_t W = static_cast<size_t>(world);
+    std::vector<size_t> qs(static_cast<size_t>(nb) * W);
+    for (size_t i = 0; i < qs.size(); ++i) qs[i] = counts[i / W] / W;
+    return plan_update_batch<Mx8VarArgs<SEG>>(
+        qs.data(), static_cast<int>(qs.size()), kMx8PackElts, kMx8Block,
+        [&](SEG &g, int i) {
+            const size_t b = i / W, j = i % W, q = qs[i];
+            g.src = static_cast<const char *>(grads[b]) + j * q * sizeof(typename SgdElt<T>::S);
+            g.dst = static_cast<char *>(packed[b]) + j * piece_bytes(q);
+            g.n   = q;
+            fill(g, b, j, q);
+        },
+        [&](unsigned gx, unsigned gy, const Mx8VarArgs<SEG> &a) {
+            kernel<<<dim3(gx, gy), kMx8Block, 0, s>>>(a);
+            return launch_status(fail);
+        });
+}
+
+template <typename T>
+int launch_pack_ef(const void *const *grads, void *const *residuals, void *const *packed,
+                   const size_t *counts, int nb, int world, hipStream_t s)
+{
+    return launch_pack_var<T, Mx8EfSeg>(
+        fail_pack_ef, mx8_pack_ef_kernel<T>, grads, packed, counts, nb, world, s,
+        [&](Mx8EfSeg &g, size_t b, size_t j, size_t q) {
+            g.res = static_cast<float *>(residuals[b]) + j * q;
+        });
+}
+
+template <typename T>
+int launch_pack_sr(const void *const *grads, void *const *packed, const size_t *counts, int nb,
+                   int world, uint64_t seed, uint64_t step, int rank, int bucket0, hipStream_t s)
+{
+    const uint64_t at = splitmix64(splitmix64(seed) ^ step);
+    return launch_pack_var<T, Mx8SrSeg>(
+        fail_pack_sr, mx8_pack_sr_kernel<T>, grads, packed, counts, nb, world, s,
+        [&](Mx8SrSeg &g, size_t b, size_t j, size_t q) {
+            const uint64_t bucket = static_cast<uint32_t>(bucket0) + b;
+            const uint64_t w = splitmix64(at ^ (static_cast<uint64_t>(rank) << 32 | bucket));
+            g.base   = j * q;
+            g.key    = static_cast<uint32_t>(w);
+            g.stream = static_cast<uint32_t>(w >> 32);
+        });
+}
+
 template <typename T, int DIV>
 int launch_fold(const void *const *packed, void *const *outs, const size_t *q, int nb, int world,
                 const Div &dv, hipStream_t s)
@@ -411,6 +635,47 @@ int kf_mx8_pack_batch(const void *const *grads, void *const *packed, const size_
     if (dt == KungFu_FLOAT) return launch_pack<float>(grads, packed, counts, nb, world, s);
     if (dt == KungFu_BFLOAT16) return launch_pack<bf16_t>(grads, packed, counts, nb, world, s);
     return launch_pack<f16_t>(grads, packed, counts, nb, world, s);
+}
+
+int kf_mx8_pack_ef_batch(const void *const *grads, void *const *residuals, void *const *packed,
+                         const size_t *counts, int nb, int world, KungFu_Datatype dt, void *stream)
+{
+    const UpdateFail &fail = fail_pack_ef;
+    const size_t W         = static_cast<size_t>(world);
+    int rc = mx8_check(fail, grads, packed, counts, nb, world, dt, 0, [&](int b) { return counts[b] / W; });
+    if (rc != KF_OK || nb == 0) return rc;
+    if (!residuals) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null table");
+    for (int b = 0; b < nb; ++b) {
+        if (counts[b] / W == 0) continue;
+        if (!residuals[b]) return fail(KF_ERR_ARG, "KF_ERR_ARG", "null residual of a non-empty bucket");
+        if (off16(residuals[b])) return fail(KF_ERR_ARG, "KF_ERR_ARG", "residuals must be 16-byte aligned");
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dt == KungFu_FLOAT) return launch_pack_ef<float>(grads, residuals, packed, counts, nb, world, s);
+    if (dt == KungFu_BFLOAT16) {
+        return launch_pack_ef<bf16_t>(grads, residuals, packed, counts, nb, world, s);
+    }
+    return launch_pack_ef<f16_t>(grads, residuals, packed, counts, nb, world, s);
+}
+
+int kf_mx8_pack_sr_batch(const void *const *grads, void *const *packed, const size_t *counts, int nb,
+                         int world, KungFu_Datatype dt, uint64_t seed, uint64_t step, int rank,
+                         int bucket0, void *stream)
+{
+    const UpdateFail &fail = fail_pack_sr;
+    const int rc = mx8_check(fail, grads, packed, counts, nb, world, dt, 0,
+                             [&](int b) { return counts[b] / static_cast<size_t>(world); });
+    if (rc != KF_OK || nb == 0) return rc;
+    if (rank < 0 || rank >= world) return fail(KF_ERR_ARG, "KF_ERR_ARG", "rank must be in [0, world)");
+    if (bucket0 < 0) return fail(KF_ERR_ARG, "KF_ERR_ARG", "bucket0 < 0");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dt == KungFu_FLOAT) {
+        return launch_pack_sr<float>(grads, packed, counts, nb, world, seed, step, rank, bucket0, s);
+    }
+    if (dt == KungFu_BFLOAT16) {
+        return launch_pack_sr<bf16_t>(grads, packed, counts, nb, world, seed, step, rank, bucket0, s);
+    }
+    return launch_pack_sr<f16_t>(grads, packed, counts, nb, world, seed, step, rank, bucket0, s);
 }
 
 int kf_mx8_fold_batch(const void *const *packed, void *const *out_shards, const size_t *q, int nb,

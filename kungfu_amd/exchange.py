@@ -136,7 +136,7 @@ class NativeExchange:
         self.groups = int(groups)
         return self
 
-    def set_grad_wire(self, wire):
+    def set_grad_wire(self, wire, *, error_feedback=False, rounding="nearest", seed=0):
         """What phase 1 of the sharded steps carries: None (the default), the
         gradient buckets in their own dtype, or "mx8", block-scaled MXFP8 (one
         E4M3 code per element and one E8M0 scale byte per 32: 1.03125 bytes per
@@ -148,11 +148,64 @@ class NativeExchange:
         Shard lengths must be multiples of 32 (the optimizers' are). A lossy
         wire: |error| <= 2^-4 |x| per element and rank. all_reduce_, start_,
         start_into_, sma_ and all_reduce_named ignore the setting: variables
-        and SMA sums are not gradients."""
+        and SMA sums are not gradients.
+
+        The plain pack rounds to nearest, with the same bias at every step.
+        Two remedies, one at a time:
+
+        error_feedback=True: reduce_shards_ keeps one f32 residual tensor per
+        gradient bucket (zeros at first use, keyed by the bucket's data_ptr(),
+        length and dtype, freed by close()), packs g + r and leaves in r what
+        the pack dropped, so the next step sends it: 4 bytes per gradient
+        element per rank. grad_residuals() returns the tensors,
+        reset_grad_residuals() drops them. The residual is in the gradients'
+        units: a caller whose loss scale changes multiplies it by new / old.
+        A gated step that is skipped has consumed its gradient into the
+        residual all the same (a block that was not finite leaves zeros).
+        There is no host state per step, so a captured graph replays it.
+
+        rounding="stochastic": every element goes to one of its two E4M3
+        neighbours, unbiased per step, no memory. The draws come from `seed`
+        (an int in [0, 2**64)), the number of reduce_shards_ calls so far,
+        this rank and the bucket's index in the call. That count is a
+        host-side kernel argument: a captured graph replays the draws of the
+        step it was captured at."""
         if wire not in GRAD_WIRES:
             raise ValueError("grad_wire must be None or 'mx8' (got %r)" % (wire,))
+        if rounding not in ("nearest", "stochastic"):
+            raise ValueError("grad_wire rounding must be 'nearest' or 'stochastic' (got %r)"
+                             % (rounding,))
+        stochastic = rounding == "stochastic"
+        if (error_feedback or stochastic) and wire is None:
+            raise ValueError("grad_wire: error_feedback and rounding need a wire")
+        if error_feedback and stochastic:
+            raise ValueError("grad_wire: error_feedback or stochastic rounding, not both")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise ValueError("grad_wire seed must be an int in [0, 2**64), not %r" % (seed,))
         self._wire = wire
+        self._wire_mode = "ef" if error_feedback else "sr" if stochastic else None
+        self._wire_seed, self._wire_step = seed, 0
         return self
+
+    def grad_residuals(self):
+        """The error-feedback residuals reduce_shards_ keeps, one f32 tensor of
+        its bucket's length per gradient bucket, in order of first use; the
+        tensors themselves, for saving, loading (copy_) or rescaling."""
+        return list(self.__dict__.get("_residuals", {}).values())
+
+    def reset_grad_residuals(self):
+        """Drop the residuals: the next reduce_shards_ starts from zeros."""
+        self.__dict__.pop("_residuals", None)
+
+    def _grad_residuals(self, grads):
+        kept = self.__dict__.setdefault("_residuals", {})
+        out = []
+        for g in grads:
+            key = (g.data_ptr(), g.numel(), g.dtype)
+            if key not in kept:
+                kept[key] = torch.zeros(g.numel(), dtype=torch.float32, device=g.device)
+            out.append(kept[key])
+        return out
 
     def set_timing(self, on):
         """kf_exchange_set_timing: start (zeroed) or stop the per-phase timing
@@ -394,18 +447,31 @@ class NativeExchange:
         rank-order folds, queued on the current stream. Returns what the
         update must still divide by: the world after a reduce-scatter, 0 after
         the fold or under rs_avg, 1 at world 1 on the built-in transport.
-        Under set_grad_wire("mx8"): kf_exchange_reduce_shards_mx8_batch, and 0."""
+        Under set_grad_wire("mx8"): kf_exchange_reduce_shards_mx8_batch (or its
+        _ef / _sr variant, as set_grad_wire's options say), and 0."""
         grads = list(grad_buckets)
         if grads:
             self._check(grads)
         np_ = ctypes.c_int(0)
         dt = int(kungfu_dtype(grads[0])) if grads else 0x20408
         if getattr(self, "_wire", None):  # "mx8": the only wire
-            rc = self.lib.kf_exchange_reduce_shards_mx8_batch(
-                self._h, _lib.ptr_array([g.data_ptr() for g in grads]),
-                _arr(ctypes.c_size_t, [g.numel() for g in grads]), len(grads), dt,
-                ctypes.byref(np_), torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(rc, "kf_exchange_reduce_shards_mx8_batch")
+            tabs = (self._h, _lib.ptr_array([g.data_ptr() for g in grads]))
+            tail = (_arr(ctypes.c_size_t, [g.numel() for g in grads]), len(grads), dt)
+            end = (ctypes.byref(np_), torch.cuda.current_stream(self.device).cuda_stream)
+            mode = getattr(self, "_wire_mode", None)
+            if mode == "ef":
+                res = _lib.ptr_array([r.data_ptr() for r in self._grad_residuals(grads)])
+                name = "kf_exchange_reduce_shards_mx8_ef_batch"
+                rc = self.lib.kf_exchange_reduce_shards_mx8_ef_batch(*tabs, res, *tail, *end)
+            elif mode == "sr":
+                name = "kf_exchange_reduce_shards_mx8_sr_batch"
+                rc = self.lib.kf_exchange_reduce_shards_mx8_sr_batch(
+                    *tabs, *tail, self._wire_seed, self._wire_step, *end)
+                self._wire_step += 1
+            else:
+                name = "kf_exchange_reduce_shards_mx8_batch"
+                rc = self.lib.kf_exchange_reduce_shards_mx8_batch(*tabs, *tail, *end)
+            _lib.check(rc, name)
             return np_.value
         rc = self.lib.kf_exchange_reduce_shards_batch(
             self._h, _lib.ptr_array([g.data_ptr() for g in grads]),
@@ -516,6 +582,7 @@ class NativeExchange:
             torch.cuda.synchronize(self.device)
             self.lib.kf_exchange_destroy(self._h)
             self._h = None
+            self.reset_grad_residuals()
 
     def __del__(self):
         try:

@@ -666,6 +666,64 @@ def mx8_pack_batch_(grads, world, packed=None, stream=None):
     return packed
 
 
+def _mx8_pack_variant(name, grads, world, packed, stream, call):
+    """What the two pack variants share with mx8_pack_batch_: its checks, then
+    call(lib, grad pointers, packed pointers, counts, nb, dtype, stream)."""
+    grads, world = list(grads), int(world)
+    if world < 1:
+        raise ValueError("%s: world >= 1" % name)
+    need = [world * mx8_piece_bytes(g.numel() // world) for g in grads]
+    if packed is None:
+        packed = [torch.empty(n, dtype=torch.uint8, device=g.device) for n, g in zip(need, grads)]
+    packed = list(packed)
+    if len(packed) != len(grads):
+        raise ValueError("%s: one packed tensor per bucket" % name)
+    if not grads:
+        return packed
+    _check_dev(grads + packed)
+    for g, p, n in zip(grads, packed, need):
+        if g.dtype != grads[0].dtype or p.dtype != torch.uint8 or p.numel() != n:
+            raise ValueError("%s: one dtype, and uint8 tensors of world pieces" % name)
+    cnt = (ctypes.c_size_t * len(grads))(*[g.numel() for g in grads])
+    rc = call(_lib.load(), _lib.ptr_array([g.data_ptr() for g in grads]),
+              _lib.ptr_array([p.data_ptr() for p in packed]), cnt, len(grads),
+              int(kungfu_dtype(grads[0])), _stream(stream, grads[0].device))
+    _lib.check(rc, "kf_" + name.rstrip("_"), source="")
+    return packed
+
+
+def mx8_pack_ef_batch_(grads, residuals, world, packed=None, stream=None):
+    """mx8_pack_batch_ with error feedback (kf_mx8_pack_ef_batch, DESIGN.md
+    §25): residuals[b] is an f32 tensor of grads[b]'s length; every piece packs
+    g + r and leaves r = (g + r) - unpack(what was packed) in place, +0.0 over a
+    block that was not finite. grads are only read; the numel % world tail's
+    residuals are not touched."""
+    grads, residuals = list(grads), list(residuals)
+    if len(residuals) != len(grads) or any(
+            r.dtype != torch.float32 or r.numel() != g.numel() or not r.is_contiguous()
+            for r, g in zip(residuals, grads)):
+        raise ValueError("mx8_pack_ef_batch_: one contiguous f32 residual of its bucket's length "
+                         "per bucket")
+    _check_dev(grads + residuals)
+    res = _lib.ptr_array([r.data_ptr() for r in residuals])
+    return _mx8_pack_variant(
+        "mx8_pack_ef_batch_", grads, world, packed, stream,
+        lambda lib, g, p, cnt, nb, dt, s: lib.kf_mx8_pack_ef_batch(g, res, p, cnt, nb, int(world), dt,
+                                                                   s))
+
+
+def mx8_pack_sr_batch_(grads, world, seed, step, rank, bucket0=0, packed=None, stream=None):
+    """mx8_pack_batch_ with stochastic rounding (kf_mx8_pack_sr_batch,
+    DESIGN.md §25): every element goes to one of its two E4M3 neighbours at
+    the block's scale, up with the probability of its distance from the lower
+    one. The draws are a pure function of (seed, step, rank, bucket0 + b,
+    element index in the bucket); seed and step are ints in [0, 2**64)."""
+    return _mx8_pack_variant(
+        "mx8_pack_sr_batch_", grads, world, packed, stream,
+        lambda lib, g, p, cnt, nb, dt, s: lib.kf_mx8_pack_sr_batch(
+            g, p, cnt, nb, int(world), dt, int(seed), int(step), int(rank), int(bucket0), s))
+
+
 def mx8_fold_batch_(packed, out_shards, world, np_=0, stream=None):
     """out_shards[b] = (the `world` pieces of packed[b], unpacked and added in
     f32 in rank order) / np_ (np_ > 0), narrowed once to the shard's dtype
