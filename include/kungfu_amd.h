@@ -829,6 +829,72 @@ int kf_mx8_pack_sr_batch(const void *const *grads, void *const *packed, const si
                          int world, KungFu_Datatype dt, uint64_t seed, uint64_t step, int rank,
                          int bucket0, void *stream);
 
+/* ---- Lion: a sign update, dense or over a 2-bit wire ------------------------
+ *
+ * Lion (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms") on
+ * the shard step: one state tensor, and an update that is one of three values.
+ * kungfu_amd/csrc/kf_lion.hip, DESIGN.md §26.
+ *
+ * Lion. Per element, compute type C = f32, each parenthesis one IEEE
+ * operation, no contraction:
+ *   g  = np > 0 ? sum / np : sum          (Div's rounding in C, as kf_sgd's)
+ *   c  = (b1*m) + (c1*g)                   c1 = 1 - beta1
+ *   m' = (b2*m) + (c2*g)                   c2 = 1 - beta2
+ *   code = c > 0 ? 1 : c < 0 ? 3 : c == c ? 0 : 2        (2: c is NaN)
+ *   if weight_decay != 0:  p = dk*p        dk = 1 - lr*weight_decay
+ *   code 1: p = p + nlr     code 3: p = p - nlr          nlr = -lr
+ *   code 0: p keeps dk*p (keeps its bits, a -0 included, when weight_decay == 0)
+ *   code 2: p = the canonical quiet NaN of the storage type (0x7fc00000, 0x7fc0)
+ * c1, c2, dk and nlr are computed in double on the host and cast once. The
+ * momentum has the parameters' dtype and starts as zeros; there is no first
+ * step. dt is KungFu_FLOAT or KungFu_BFLOAT16, anything else KF_ERR_DTYPE:
+ * f16 has no stochastic narrowing here, and rounded to nearest a step of
+ * lr = 1e-4 is below half an ulp of every |p| >= 0.25 and would be dropped.
+ * bf16: g, m and p are widened exactly; m' is stored round-to-nearest-even
+ * (f32_to_bf16); p is stored as sr(p, r_p) of "Adam, stochastic rounding",
+ * with that section's "Random bits": for element i of segment b, e = bases[b] +
+ * i, (a, b) = philox2x32_10((uint32_t)(e >> 1), streams[b], key), w = (e & 1) ?
+ * b : a, r_p = w >> 16. Round-to-nearest would drop every update below half a
+ * bf16 ulp of p, at lr = 1e-4 nearly every one; and as the draws depend on
+ * (key, stream word, element index) alone, every rank and both phase-3 paths
+ * round alike. Code 2 stores the NaN and code 0 without decay the old bits,
+ * neither through sr.
+ *
+ * The sign code format. A piece of q elements (q % 32 == 0) is q / 16
+ * little-endian dwords: element i's code sits in bits 2*(i % 16) and
+ * 2*(i % 16) + 1 of dword i / 16. Zero dwords then fill up to the next 16
+ * bytes: kf_lion_sign_bytes(q) = ceil(q / 4 / 16) * 16 bytes in all.
+ *
+ * kf_lion_update_batch: the whole update on nb segments, reading grads, moms
+ * and params and writing moms and params. kf_lion_signs_batch: c, m' and the
+ * codes; reads grads and moms, writes moms and kf_lion_sign_bytes(counts[b])
+ * bytes at codes[b], never a parameter. kf_lion_apply_signs_batch: the last
+ * four lines of "Lion" on params[b] with the codes at codes[b]. apply(p,
+ * signs(g, m)) and update(p, g, m) give the same bits. One launch per 32
+ * segments; hyper[b] is segment b's. bases, streams and key are read only for
+ * bf16 and may be NULL / 0 for f32.
+ *
+ * Checks, all before any HIP call, in this order: nb < 0; (nb == 0 is KF_OK);
+ * a null table (bases and streams not among them); dt (KF_ERR_DTYPE); for
+ * bf16 a null bases or streams where the entry draws (update, apply); np < 0
+ * (update, signs); then per non-empty segment: a null pointer, a pointer off
+ * a 16-byte boundary, counts[b] % 32 != 0 (there is no tail path), and where
+ * the entry draws, bases[b] not a multiple of 8 or bases[b] + counts[b] above
+ * 2^33. All KF_ERR_ARG but the dtype. */
+typedef struct { double lr, beta1, beta2, weight_decay; } kf_lion_hyper;
+size_t kf_lion_sign_bytes(size_t q);
+int kf_lion_update_batch(void *const *params, const void *const *grads, void *const *moms,
+                         const size_t *counts, const uint64_t *bases, const uint32_t *streams,
+                         int nb, KungFu_Datatype dt, int np, const kf_lion_hyper *hyper,
+                         uint32_t key, void *stream);
+int kf_lion_signs_batch(const void *const *grads, void *const *moms, void *const *codes,
+                        const size_t *counts, int nb, KungFu_Datatype dt, int np,
+                        const kf_lion_hyper *hyper, void *stream);
+int kf_lion_apply_signs_batch(void *const *params, const void *const *codes, const size_t *counts,
+                              const uint64_t *bases, const uint32_t *streams, int nb,
+                              KungFu_Datatype dt, const kf_lion_hyper *hyper, uint32_t key,
+                              void *stream);
+
 /* ---- gradient monitors: segmented squared norms ------------------------- */
 
 /* What MonitorGradientNoiseScaleOptimizer and MonitorGradientVarianceOptimizer
@@ -1458,6 +1524,28 @@ int kf_exchange_all_gather_doubles(kf_exchange_t *ex, const double *send, double
  * phase 3. */
 int kf_exchange_gather_params_batch(kf_exchange_t *ex, void *const *params, const size_t *counts,
                                     int nb, KungFu_Datatype dt, void *stream);
+/* The sharded step with Lion ("Lion" above). sign_wire == 0 is
+ * kf_exchange_sgd_batch's shape: phase 1, kf_lion_update_batch on this rank's
+ * shards with the / world fused (bases rank * q), the parameters' all-gather.
+ * sign_wire != 0: phase 1, kf_lion_signs_batch on the shards into the
+ * exchange's workspace (counted under phase 2), one grouped all-gather of
+ * kf_lion_sign_bytes(q) bytes per bucket and kf_lion_apply_signs_batch over
+ * all `world` pieces of every bucket, the own one included (both under phase
+ * 3): 2 bits per element on the wire where the parameters are 32 or 16, and
+ * the same bits in every replica as the dense path leaves, at the price of
+ * one read and one write of the whole replica. World 1 on the built-in
+ * transport makes codes and applies them too; only the transport call is
+ * skipped. mom_shards[b] holds q = counts[b] / world elements of dt (f32 or
+ * bf16, KF_ERR_DTYPE otherwise); streams[b] is bucket b's stream word and key
+ * the step's key (bf16 only; streams may be NULL for f32). Checks on every
+ * rank before any collective: the tables, the algo, and per non-empty bucket
+ * kf_exchange_adam_batch's (null buckets, counts[b] % world, the momentum
+ * shard, alignment), then q % 32. Un-pipelined; after its first call it
+ * allocates nothing and never waits on the host. */
+int kf_exchange_lion_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
+                           void *const *mom_shards, const size_t *counts, int nb,
+                           KungFu_Datatype dt, const kf_lion_hyper *hyper, const uint32_t *streams,
+                           uint32_t key, int algo, int sign_wire, void *stream);
 /* Pipelined schedule for the batch calls (default 1 = off): the buckets of a
  * call are split into `groups` groups of consecutive buckets of about equal
  * bytes; the RCCL phases stay on the caller's stream in the same order on

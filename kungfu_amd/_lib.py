@@ -163,6 +163,11 @@ EXPORTED = (
     "kf_mx8_pack_sr_batch",
     "kf_exchange_reduce_shards_mx8_ef_batch",
     "kf_exchange_reduce_shards_mx8_sr_batch",
+    "kf_lion_sign_bytes",
+    "kf_lion_update_batch",
+    "kf_lion_signs_batch",
+    "kf_lion_apply_signs_batch",
+    "kf_exchange_lion_batch",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -225,6 +230,22 @@ def adam_hyper_array(hypers):
         a.eps, a.weight_decay = float(h.get("eps", 1e-8)), float(h.get("weight_decay", 0.0))
         a.bias_correction1, a.bias_correction2 = 1.0 - b1 ** t, 1.0 - b2 ** t
         a.decoupled = int(bool(h.get("decoupled", False)))
+    return arr
+
+
+class LionHyper(ctypes.Structure):
+    """kf_lion_hyper (include/kungfu_amd.h): one segment's Lion scalars."""
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("weight_decay", ctypes.c_double)]
+
+
+def lion_hyper_array(hypers):
+    """A kf_lion_hyper[] from dicts with lr and optionally betas = (beta1,
+    beta2) (Lion's defaults, 0.9 and 0.99) and weight_decay."""
+    arr = (LionHyper * max(1, len(hypers)))()
+    for a, h in zip(arr, hypers):
+        a.lr, a.weight_decay = float(h["lr"]), float(h.get("weight_decay", 0.0))
+        a.beta1, a.beta2 = (float(b) for b in h.get("betas", (0.9, 0.99)))
     return arr
 
 
@@ -703,6 +724,22 @@ def load():
     lib.kf_exchange_reduce_shards_mx8_sr_batch.argtypes = [
         c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_u64, c_u64, P(c_int), c_void_p]
     lib.kf_exchange_reduce_shards_mx8_sr_batch.restype = c_int
+    lib.kf_lion_sign_bytes.argtypes = [c_size_t]
+    lib.kf_lion_sign_bytes.restype = c_size_t
+    lib.kf_lion_update_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_size_t),
+                                         P(c_u64), P(u32), c_int, c_int, c_int, P(LionHyper), u32,
+                                         c_void_p]
+    lib.kf_lion_update_batch.restype = c_int
+    lib.kf_lion_signs_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_size_t), c_int,
+                                        c_int, c_int, P(LionHyper), c_void_p]
+    lib.kf_lion_signs_batch.restype = c_int
+    lib.kf_lion_apply_signs_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_size_t), P(c_u64),
+                                              P(u32), c_int, c_int, P(LionHyper), u32, c_void_p]
+    lib.kf_lion_apply_signs_batch.restype = c_int
+    lib.kf_exchange_lion_batch.argtypes = [c_void_p, P(c_void_p), P(c_void_p), P(c_void_p),
+                                           P(c_size_t), c_int, c_int, P(LionHyper), P(u32), u32,
+                                           c_int, c_int, c_void_p]
+    lib.kf_exchange_lion_batch.restype = c_int
     _lib = lib
     # HIP resources go back while the runtime is alive, before the C exit
     # handlers run (include/kungfu_amd.h kf_shutdown)

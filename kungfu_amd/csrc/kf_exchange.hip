@@ -2045,6 +2045,131 @@ int kf_exchange_gather_params_batch(kf_exchange_t *ex, void *const *params, cons
     return gather_shards(*ex, params, counts, nb, dt, static_cast<hipStream_t>(stream));
 }
 
+// The sharded step with Lion (kf_lion.hip), dense or over the
+// sign wire. Dense is sharded_step's shape. The sign wire: phase 1 and the
+// fold as ever; the signs kernel on the shards writes this rank's piece of
+// every bucket's code area in the workspace (phase 2); the pieces' grouped
+// all-gather and the apply kernel over all W pieces of every bucket (phase 3).
+// A single peer on the built-in transport makes its one piece and applies it.
+struct LionStep {
+    void *const *params;
+    void *const *moms;
+    const kf_lion_hyper *hyper;
+    const uint32_t *streams;
+    uint32_t key;
+    bool sign_wire;
+};
+static int lion_step(kf_exchange &x, void *const *grads, const size_t *counts, int nb,
+                     KungFu_Datatype dt, int algo, hipStream_t s, const LionStep &L)
+{
+    Schedule sc{x, counts, nb, dt, KungFu_SUM, s};
+    const bool alone = sc.alone();
+    const size_t W   = sc.W;
+    int rc           = alone ? KF_OK : sc.resolve(algo, 1);
+    if (rc != KF_OK) return rc;
+    sc.ws = alone ? kf::Workspace{std::vector<size_t>(nb, 0), std::vector<size_t>(nb, 0)}
+                  : kf::plan_workspace(counts, nb, W, sc.sz, sc.a == KF_ALGO_ALL_TO_ALL);
+    std::vector<size_t> code_at(nb, 0), piece(nb, 0);
+    for (int b = 0; b < nb && L.sign_wire; ++b) {
+        piece[b]   = kf_lion_sign_bytes(sc.q(b));
+        code_at[b] = sc.ws.bytes;
+        sc.ws.bytes += align_up(W * piece[b], 256);
+    }
+    if (sc.ws.bytes) rc = x.ensure_ws(sc.ws.bytes, s);
+    if (rc != KF_OK) return rc;
+    sc.wsp = static_cast<char *>(x.ws);
+    const int np = alone ? 1 : sc.np();
+    auto lion    = [](int e, const char *what) {
+        return e == KF_OK ? KF_OK : fail(e, std::string(what) + ": " + kf_last_error());
+    };
+    // this rank's shards: the tables of the update and of the signs
+    std::vector<void *> ps(nb), cs(nb);
+    std::vector<const void *> gs(nb);
+    std::vector<size_t> qs(nb);
+    std::vector<uint64_t> bases(nb);
+    for (int b = 0; b < nb; ++b) {
+        ps[b]    = sc.shard(static_cast<char *>(L.params[b]), b);
+        gs[b]    = sc.shard(static_cast<const char *>(grads[b]), b);
+        cs[b]    = sc.wsp + code_at[b] + sc.r * piece[b];
+        qs[b]    = sc.q(b);
+        bases[b] = sc.r * qs[b];
+    }
+    auto phase1 = [&] { return alone ? KF_OK : sc.scatter(grads, grads, 0, nb); };
+    auto phase2 = [&] {
+        int e = alone ? KF_OK : sc.fold(grads, x.world, 0, nb, s);
+        if (e != KF_OK) return e;
+        if (!L.sign_wire) {
+            return lion(kf_lion_update_batch(ps.data(), gs.data(), L.moms, qs.data(), bases.data(),
+                                             L.streams, nb, dt, np, L.hyper, L.key, s),
+                        "kf_lion_update_batch");
+        }
+        return lion(kf_lion_signs_batch(gs.data(), L.moms, cs.data(), qs.data(), nb, dt, np, L.hyper, s),
+                    "kf_lion_signs_batch");
+    };
+    auto phase3 = [&] {
+        if (!L.sign_wire) return alone ? KF_OK : sc.gather(L.params, 0, nb);
+        if (!alone) {
+            const int e = grouped(x, 0, nb, "all_gather of the sign codes", [&](int b) {
+                char *area = sc.wsp + code_at[b];
+                return qs[b] ? x.T->all_gather(area + sc.r * piece[b], area, piece[b], x.comm, s) : 0;
+            });
+            if (e != KF_OK) return e;
+        }
+        // one segment per (bucket, piece), the own piece like every other
+        const size_t n = static_cast<size_t>(nb) * W;
+        std::vector<void *> ap(n);
+        std::vector<const void *> ac(n);
+        std::vector<size_t> an(n);
+        std::vector<uint64_t> ab(n);
+        std::vector<uint32_t> as(n, 0);
+        std::vector<kf_lion_hyper> ah(n);
+        for (int b = 0; b < nb; ++b) {
+            for (size_t j = 0; j < W; ++j) {
+                const size_t i = b * W + j;
+                ap[i] = static_cast<char *>(L.params[b]) + j * qs[b] * sc.sz;
+                ac[i] = sc.wsp + code_at[b] + j * piece[b];
+                an[i] = qs[b];
+                ab[i] = j * qs[b];
+                if (L.streams) as[i] = L.streams[b];
+                ah[i] = L.hyper[b];
+            }
+        }
+        return lion(kf_lion_apply_signs_batch(ap.data(), ac.data(), an.data(), ab.data(), as.data(),
+                                              static_cast<int>(n), dt, ah.data(), L.key, s),
+                    "kf_lion_apply_signs_batch");
+    };
+    return sc.serial(phase1, phase2, phase3, nothing);
+}
+
+int kf_exchange_lion_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
+                           void *const *mom_shards, const size_t *counts, int nb,
+                           KungFu_Datatype dt, const kf_lion_hyper *hyper, const uint32_t *streams,
+                           uint32_t key, int algo, int sign_wire, void *stream)
+{
+    const std::string fn = "kf_exchange_lion_batch: ";
+    if (!ex || nb < 0) return fail(KF_ERR_ARG, fn + "bad arguments");
+    if (dt != KungFu_FLOAT && dt != KungFu_BFLOAT16) {
+        return fail(KF_ERR_DTYPE, fn + "f32 and bf16 only");
+    }
+    if (nb == 0) return KF_OK;
+    const bool tables = params && grads && mom_shards && counts && hyper;
+    if (!tables || (dt == KungFu_BFLOAT16 && !streams)) return fail(KF_ERR_ARG, fn + "null table");
+    if (check_algo(algo) != KF_OK) return KF_ERR_ARG;
+    const ShardTab m{mom_shards, "every non-empty bucket needs its momentum shard"};
+    const size_t W = static_cast<size_t>(ex->world);
+    for (int b = 0; b < nb; ++b) {
+        const int rc = check_shard_bucket(fn, {params, grads}, {m}, b, counts[b], ex->world, tsize(dt));
+        if (rc != KF_OK) return rc;
+        if ((counts[b] / W) % 32) {
+            return fail(KF_ERR_ARG, fn + "shard lengths (count / world) must be multiples of 32");
+        }
+    }
+    DeviceGuard g(ex->device);
+    std::lock_guard<std::mutex> lk(ex->mu);
+    return lion_step(*ex, grads, counts, nb, dt, algo, static_cast<hipStream_t>(stream),
+                     LionStep{params, mom_shards, hyper, streams, key, sign_wire != 0});
+}
+
 int kf_exchange_adam_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
                            void *const *exp_avg_shards, void *const *exp_avg_sq_shards,
                            const size_t *counts, int nb, KungFu_Datatype dt,

@@ -374,6 +374,80 @@ class NativeExchange:
                                 param_buckets, grad_buckets,
                                 (master_shards, exp_avg_shards, exp_avg_sq_shards), hypers)
 
+    def lion_step_(self, param_buckets, grad_buckets, mom_shards, hypers, sign_wire=False,
+                   sr=None):
+        """sgd_step_ with the Lion update (kf_exchange_lion_batch, DESIGN.md
+        §26); f32 or bf16 buckets, mom_shards[b] of numel // world elements,
+        hypers[b] a dict with lr and optionally betas and weight_decay. bf16
+        needs sr = (streams, key): a 32-bit stream word per bucket and the
+        step's 32-bit key.
+
+        sign_wire=False: reduce-scatter, ops.lion_update_batch_'s kernel on this
+        rank's shards, the parameters' all-gather. sign_wire=True: phase 3
+        carries 2 bits per element instead of the parameters:
+        ops.lion_signs_batch_'s kernel on the shards, one all-gather of
+        ops.lion_sign_bytes(numel // world) bytes per bucket, and
+        ops.lion_apply_signs_batch_'s kernel over every rank's piece of every
+        bucket. The same bits either way, on every rank. Under
+        set_grad_wire("mx8") phase 1 is reduce_shards_ over that wire and the
+        rest runs from here: the same kernels, the codes gathered through
+        gather_params_."""
+        params, grads, hypers = list(param_buckets), list(grad_buckets), list(hypers)
+        moms = list(mom_shards)
+        if not all(len(x) == len(params) for x in (grads, hypers, moms)):
+            raise ValueError("lion_step_: one grad bucket, momentum shard and hyper per bucket")
+        if not params:
+            return params
+        self._shard_tables("lion_step_", params, grads, [moms])
+        bf16 = params[0].dtype == torch.bfloat16
+        streams, key = (list(sr[0]), int(sr[1])) if sr is not None else ([0] * len(params), 0)
+        if bf16 and sr is None or len(streams) != len(params):
+            raise ValueError("lion_step_: bf16 needs sr=(a stream word per bucket, key)")
+        if getattr(self, "_wire", None):
+            return self._wired_lion(params, grads, moms, hypers, sign_wire, streams, key)
+        rc = self.lib.kf_exchange_lion_batch(
+            self._h, _lib.ptr_array([p.data_ptr() for p in params]),
+            _lib.ptr_array([g.data_ptr() for g in grads]),
+            _lib.ptr_array([m.data_ptr() for m in moms]),
+            _arr(ctypes.c_size_t, [p.numel() for p in params]), len(params),
+            int(kungfu_dtype(params[0])), _lib.lion_hyper_array(hypers),
+            _arr(ctypes.c_uint32, streams), key, ALGOS[self.algo], 1 if sign_wire else 0,
+            torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(rc, "kf_exchange_lion_batch")
+        return params
+
+    def _wired_lion(self, params, grads, moms, hypers, sign_wire, streams, key):
+        """lion_step_ under set_grad_wire, _wired_step's way: reduce_shards_
+        over the wire, then the Lion kernels on the shards from here. The sign
+        codes live in one int32 tensor per bucket (kept, keyed by the bucket's
+        address) whose float32 view gather_params_ gathers bit for bit."""
+        from . import ops
+        W, r = self.world, self.rank
+        q = [p.numel() // W for p in params]
+        np_ = self.reduce_shards_(grads)
+        mine, gs = self.grad_shards_(params), self.grad_shards_(grads)
+        if not sign_wire:
+            ops.lion_update_batch_(mine, gs, moms, hypers, np_,
+                                   ([r * n for n in q], streams, key))
+            return self.gather_params_(params)
+        kept = self.__dict__.setdefault("_lion_codes", {})
+        areas = []
+        for p, n in zip(params, q):
+            k = (p.data_ptr(), p.numel())
+            if k not in kept:
+                kept[k] = torch.zeros(W * ops.lion_sign_bytes(n) // 4, dtype=torch.int32,
+                                      device=p.device)
+            areas.append(kept[k])
+        pieces = [list(a.chunk(W)) if a.numel() else [a] * W for a in areas]
+        ops.lion_signs_batch_(gs, moms, [c[r] for c in pieces], hypers, np_)
+        self.gather_params_([a.view(torch.float32) for a in areas])
+        ops.lion_apply_signs_batch_(
+            [p[j * n:(j + 1) * n] for p, n in zip(params, q) for j in range(W)],
+            [c[j] for c in pieces for j in range(W)],
+            [h for h in hypers for _ in range(W)],
+            ([j * n for n in q for j in range(W)], [s for s in streams for _ in range(W)], key))
+        return params
+
     def _shard_call(self, name, fn, cname, hyper_array, param_buckets, grad_buckets,
                     state_shards, hypers):
         """What sgd_step_, adam_step_ and adam_master_step_ share: the checks
@@ -583,6 +657,7 @@ class NativeExchange:
             self.lib.kf_exchange_destroy(self._h)
             self._h = None
             self.reset_grad_residuals()
+            self.__dict__.pop("_lion_codes", None)
 
     def __del__(self):
         try:

@@ -519,6 +519,116 @@ def adam_sr_narrow(x, r):
     return out
 
 
+# -- Lion (include/kungfu_amd.h "Lion") -------------------------
+
+def lion_sign_bytes(q):
+    """The bytes of a piece's sign codes (kf_lion_sign_bytes; no device needed):
+    q / 16 dwords, padded to the next 16 bytes."""
+    return int(_lib.load().kf_lion_sign_bytes(int(q)))
+
+
+def _lion_tables(name, tables, hypers, sr):
+    """The checks the three Lion wrappers share; tables[0] leads (its dtype,
+    f32 or bf16, is every float table's). Returns (nb, counts, hyper array,
+    bases, streams, key) for the C call."""
+    nb = len(tables[0])
+    if any(len(t) != nb for t in tables) or len(hypers) != nb:
+        raise ValueError("%s: one tensor of every table and one hyper per segment" % name)
+    for t in tables:
+        _check_dev(t)
+    lead = tables[0][0]
+    if any(x.dtype != lead.dtype or x.numel() != y.numel()
+           for t in tables for x, y in zip(t, tables[0])):
+        raise ValueError("%s: shape/dtype mismatch" % name)
+    bases = streams = None
+    key = 0
+    if lead.dtype == torch.bfloat16 and sr is not False:
+        if sr is None:
+            raise ValueError("%s: bf16 needs sr=(bases, streams, key)" % name)
+        b, s, key = [int(x) for x in sr[0]], [int(x) for x in sr[1]], int(sr[2])
+        if len(b) != nb or len(s) != nb or not 0 <= key < 1 << 32 or \
+                any(not 0 <= x < 1 << 32 for x in s) or any(not 0 <= x < 1 << 64 for x in b):
+            raise ValueError("%s: a base (64-bit) and a stream word (32-bit) per segment and a "
+                             "32-bit key" % name)
+        bases, streams = (ctypes.c_uint64 * nb)(*b), (ctypes.c_uint32 * nb)(*s)
+    counts = (ctypes.c_size_t * nb)(*[p.numel() for p in tables[0]])
+    return nb, counts, _lib.lion_hyper_array(hypers), bases, streams, key
+
+
+def _ptrs(ts):
+    return _lib.ptr_array([t.data_ptr() for t in ts])
+
+
+def lion_update_batch_(params, grads, moms, hypers, np_=0, sr=None, stream=None):
+    """The Lion update of many flat segments of one dtype (f32 or bf16) in one
+    launch per 32 of them (kf_lion_update_batch, kungfu_amd/csrc/kf_lion.hip),
+    in place on params and moms:
+
+      g = grads[b] / np_ (np_ > 0) ; c = b1 * m + (1 - b1) * g ; m = b2 * m + (1 - b2) * g
+      p *= 1 - lr * wd ; p -= lr * sign(c)
+
+    rounded as include/kungfu_amd.h ("Lion") states. hypers[b] is a dict with
+    lr and optionally betas (0.9, 0.99) and weight_decay. bf16 parameters are
+    stored with stochastic rounding and need sr = (bases, streams, key) as
+    adam_sr_update_batch_ takes them. Lengths are multiples of 32; every tensor
+    starts 16-byte aligned. grads are only read."""
+    params, grads, moms, hypers = list(params), list(grads), list(moms), list(hypers)
+    if not params and not grads and not moms:
+        return params
+    nb, cnt, h, bases, streams, key = _lion_tables("lion_update_batch_", (params, grads, moms),
+                                                   hypers, sr)
+    rc = _lib.load().kf_lion_update_batch(_ptrs(params), _ptrs(grads), _ptrs(moms), cnt, bases,
+                                          streams, nb, int(kungfu_dtype(params[0])), int(np_), h,
+                                          key, _stream(stream, params[0].device))
+    _lib.check(rc, "kf_lion_update_batch", source="")
+    return params
+
+
+def _lion_codes(name, codes, lead):
+    """codes[b]: int32, lion_sign_bytes(n) / 4 values for a segment of n elements."""
+    _check_dev(codes)
+    if len(codes) != len(lead) or any(
+            c.dtype != torch.int32 or c.numel() * 4 != lion_sign_bytes(p.numel())
+            for c, p in zip(codes, lead)):
+        raise ValueError("%s: codes[b] holds lion_sign_bytes(n) / 4 int32 values" % name)
+
+
+def lion_signs_batch_(grads, moms, codes, hypers, np_=0, stream=None):
+    """Lion's momentum update and the 2-bit codes of its sign update
+    (kf_lion_signs_batch): reads grads and moms, writes moms and codes, touches
+    no parameter. codes[b] is an int32 tensor of lion_sign_bytes(n) / 4 values:
+    element i's code (0 keep, 1 p -= lr, 3 p += lr, 2 NaN) in bits 2 * (i % 16)
+    of value i // 16, zero padding behind."""
+    grads, moms, codes, hypers = list(grads), list(moms), list(codes), list(hypers)
+    if not grads and not moms and not codes:
+        return codes
+    nb, cnt, h, _, _, _ = _lion_tables("lion_signs_batch_", (grads, moms), hypers, False)
+    _lion_codes("lion_signs_batch_", codes, grads)
+    rc = _lib.load().kf_lion_signs_batch(_ptrs(grads), _ptrs(moms), _ptrs(codes), cnt, nb,
+                                         int(kungfu_dtype(grads[0])), int(np_), h,
+                                         _stream(stream, grads[0].device))
+    _lib.check(rc, "kf_lion_signs_batch", source="")
+    return codes
+
+
+def lion_apply_signs_batch_(params, codes, hypers, sr=None, stream=None):
+    """Apply lion_signs_batch_'s codes to params in place
+    (kf_lion_apply_signs_batch): the decay, then -lr, 0 or +lr per element (or
+    NaN). lion_apply_signs_batch_(p, lion_signs_batch_(g, m)) leaves the bits
+    lion_update_batch_(p, g, m) leaves; for bf16 with the same sr = (bases,
+    streams, key), however the elements are cut into segments."""
+    params, codes, hypers = list(params), list(codes), list(hypers)
+    if not params and not codes:
+        return params
+    nb, cnt, h, bases, streams, key = _lion_tables("lion_apply_signs_batch_", (params,), hypers, sr)
+    _lion_codes("lion_apply_signs_batch_", codes, params)
+    rc = _lib.load().kf_lion_apply_signs_batch(_ptrs(params), _ptrs(codes), cnt, bases, streams, nb,
+                                               int(kungfu_dtype(params[0])), h, key,
+                                               _stream(stream, params[0].device))
+    _lib.check(rc, "kf_lion_apply_signs_batch", source="")
+    return params
+
+
 # -- Adam, 8-bit block-wise state (include/kungfu_amd.h, DESIGN.md §20) --------
 
 ADAM8_ZERO_CODE = (127, 0)       # the code of 0.0: signed (exp_avg), unsigned (exp_avg_sq)

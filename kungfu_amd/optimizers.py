@@ -33,6 +33,9 @@ Operator surface kept from the reference:
 * ``ShardedLARSOptimizer(optimizer, named_parameters=None, ...)`` — LARS on
   the sharded SGD step: a per-tensor rate in front of the momentum update,
   with fp32 master weights and momentum for bf16 / f16 models.
+* ``ShardedLionOptimizer(optimizer, named_parameters=None, ...)`` — Lion on
+  the shard: one state tensor, a sign update, and with ``sign_wire=True`` a
+  phase 3 of 2-bit codes that every rank applies to its replica.
 
 Buckets: parameters are grouped (in registration order, per dtype/device) into
 flat padded device buckets (``collective.GradBuckets``); ``p.grad`` (S-SGD) or
@@ -1649,6 +1652,120 @@ class _ShardedLARS(_Sharded):
             for p, r in zip(L["owners"], L["ratio"].cpu().tolist()):
                 out[p] = float(r)
         return out
+
+
+class _ShardedLion(_ShardedSGD):
+    """reduce-scatter(grads) -> Lion on the own shard -> all-gather of the
+    parameters, or with the sign wire of 2 bits per element and the apply pass
+    on every rank. The momentum is one shard per bucket,
+    zeros from the start: _ShardedSGD's, with its checkpoint path."""
+
+    _kf_name = "ShardedLionOptimizer"
+    _kf_dtypes = ("float32", "bfloat16")
+    _kf_dtype_words = "f32 and bf16"
+    _kf_sign_wire = False
+    _kf_sr_seed = 0
+    _kf_lion_steps = 0
+
+    def _kf_new_group(self):
+        return {"moms": None, "first": True, "streams": None}
+
+    def step(self, closure=None):
+        loss = self._kf_closure(closure)
+        if self._kf_groups is None:
+            self._kf_build_sharded()
+        ex = self._kf_ex
+        for G in self._kf_groups:
+            _SyncSGD._kf_place(G["ps"], G["gb"])
+        self._kf_lion_steps += 1
+        for j, G in enumerate(self._kf_groups):
+            pg = self.param_groups[G["gi"]]  # read at every step: schedulers change them
+            h = {"lr": float(pg["lr"]), "betas": tuple(float(b) for b in pg["betas"]),
+                 "weight_decay": float(pg["weight_decay"])}
+            pb, gb, nb = G["pb"].buckets, G["gb"].buckets, len(G["pb"].buckets)
+            moms = self._kf_moms(G)
+            if G["streams"] is None:
+                G["streams"] = [sr_stream_word(self._kf_sr_seed, j, i) for i in range(nb)]
+            # the step's key: every rank counts the same steps
+            key = splitmix64(splitmix64(self._kf_sr_seed) ^ self._kf_lion_steps) & 0xffffffff
+            if hasattr(ex, "lion_step_"):
+                ex.lion_step_(pb, gb, moms, [h] * nb, sign_wire=self._kf_sign_wire,
+                              sr=(G["streams"], key))
+            else:  # the exchange's phases around the HIP update
+                from . import ops
+                q = [b.numel() // ex.world for b in pb]
+                mine = [b[ex.rank * n:(ex.rank + 1) * n] for b, n in zip(pb, q)]
+                np_ = ex.reduce_shards_(gb, ("lion", j))
+                ops.lion_update_batch_(mine, ex.grad_shards_(gb, ("lion", j)), moms, [h] * nb, np_,
+                                       ([ex.rank * n for n in q], G["streams"], key))
+                ex.gather_params_(pb)
+            G["first"] = False
+        _finish(ex)
+        return loss
+
+
+def ShardedLionOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20,
+                         sign_wire=False, sr_seed=0):
+    """Lion (Chen et al. 2023, "Symbolic Discovery of Optimization
+    Algorithms") with the update and its one state tensor sharded over the
+    ranks as ShardedSGDOptimizer's are. Every step is
+
+      reduce-scatter(grads)
+        -> [own shard: g / np, c = b1 m + (1 - b1) g, m = b2 m + (1 - b2) g,
+            p *= 1 - lr * weight_decay, p -= lr * sign(c)]
+        -> all-gather(params)
+
+    rounded as include/kungfu_amd.h ("Lion") states. f32 and bf16 parameters
+    (TypeError on the first step otherwise); bf16 parameters are stored with
+    stochastic rounding, because rounded to nearest nearly every step of
+    lr = 1e-4 would be lost. The draws come from sr_seed, the bucket group, the
+    bucket, the step count and the element's index in its bucket, and from
+    nothing else, so every rank rounds alike.
+
+    sign_wire=True: the update is one of three values per element, so phase 3
+    carries 2-bit codes instead of the parameters (16 times fewer bytes than
+    f32, 8 times fewer than bf16) and every rank applies every rank's codes
+    to its own replica, one more read and write of it. The parameters and the
+    momentum come out bit for bit as without it. Needs exchange.NativeExchange
+    (ValueError otherwise).
+
+    `optimizer` must be a torch.optim.Adam or torch.optim.AdamW (TypeError
+    otherwise), ShardedLAMBOptimizer's rule: it only lends its class and its
+    param_groups (lr, betas, weight_decay, read at every step, so LR
+    schedulers work; eps is ignored). weight_decay is decoupled for both
+    classes, as Lion defines it. Lion's usual betas are (0.9, 0.99), and its
+    lr a third to a tenth of AdamW's.
+
+    momentum_buffers() / load_momentum_buffers() are ShardedSGDOptimizer's
+    checkpoint path. Not offered: f16 and f64, master weights, a gate, the
+    pipelined schedule, overlap=True, amsgrad, maximize, capturable,
+    differentiable."""
+    import torch
+    name = "ShardedLionOptimizer"
+    if not isinstance(optimizer, (torch.optim.Adam, torch.optim.AdamW)):
+        raise TypeError("%s wraps a torch.optim.Adam or AdamW, not %s"
+                        % (name, type(optimizer).__name__))
+    for g in optimizer.param_groups:
+        for option in ("amsgrad", "maximize", "capturable", "differentiable"):
+            if g.get(option, False):
+                raise ValueError("%s: %s=True is not supported" % (name, option))
+    if isinstance(sr_seed, bool) or not isinstance(sr_seed, int) or not 0 <= sr_seed < 1 << 64:
+        raise ValueError("%s: sr_seed must be an int in [0, 2**64), not %r" % (name, sr_seed))
+    if not isinstance(sign_wire, bool):
+        raise ValueError("%s: sign_wire must be True or False, not %r" % (name, sign_wire))
+    opt = _wrap(optimizer, _ShardedLion)
+    opt._kf_setup(named_parameters, exchange, bucket_bytes)
+    ex = opt._kf_ex
+    if sign_wire and not hasattr(ex, "lion_step_"):
+        raise ValueError("%s: sign_wire=True needs an exchange.NativeExchange, not %s"
+                         % (name, type(ex).__name__))
+    if not hasattr(ex, "lion_step_"):
+        for method in ("reduce_shards_", "grad_shards_", "gather_params_"):
+            if not hasattr(ex, method):
+                raise ValueError("%s needs an exchange with %s() (collective.Exchange or "
+                                 "exchange.NativeExchange)" % (name, method))
+    opt._kf_sign_wire, opt._kf_sr_seed = sign_wire, sr_seed
+    return opt
 
 
 def ShardedSGDOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20):

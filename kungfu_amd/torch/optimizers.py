@@ -26,7 +26,9 @@ momentum sharded over the ranks) likewise takes ``named_parameters``
 positionally, and so does ``ShardedAdamOptimizer`` (the same for
 torch.optim.Adam / AdamW and their two state tensors) and
 ``ShardedLAMBOptimizer`` (LAMB's layer-wise trust ratios on the same shards)
-and ``ShardedLARSOptimizer`` (LARS's layer-wise rates on the sharded SGD step).
+and ``ShardedLARSOptimizer`` (LARS's layer-wise rates on the sharded SGD step)
+and ``ShardedLionOptimizer`` (Lion's sign update, optionally with phase 3 as
+2-bit codes).
 """
 from .. import optimizers as _opt
 from ..optimizers import SynchronousAveragingOptimizer
@@ -34,7 +36,7 @@ from ..optimizers import SynchronousAveragingOptimizer
 __all__ = ["SynchronousSGDOptimizer", "SynchronousAveragingOptimizer",
            "MonitorGradientNoiseScaleOptimizer", "MonitorGradientVarianceOptimizer",
            "PairAveragingOptimizer", "ShardedSGDOptimizer", "ShardedAdamOptimizer",
-           "ShardedLAMBOptimizer", "ShardedLARSOptimizer"]
+           "ShardedLAMBOptimizer", "ShardedLARSOptimizer", "ShardedLionOptimizer"]
 
 
 def SynchronousSGDOptimizer(optimizer, named_parameters, op=None, **kwargs):
@@ -96,3 +98,10 @@ def ShardedLARSOptimizer(optimizer, named_parameters, **kwargs):
     positional. Keywords pass through: `exchange`, `bucket_bytes`,
     `master_weights`, `trust_coefficient`, `eps` and `always_adapt`."""
     return _opt.ShardedLARSOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
+
+
+def ShardedLionOptimizer(optimizer, named_parameters, **kwargs):
+    """kungfu_amd.optimizers.ShardedLionOptimizer with `named_parameters`
+    positional. Keywords pass through: `exchange`, `bucket_bytes`, `sign_wire`
+    and `sr_seed`."""
+    return _opt.ShardedLionOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
