@@ -829,6 +829,58 @@ int kf_mx8_pack_sr_batch(const void *const *grads, void *const *packed, const si
                          int world, KungFu_Datatype dt, uint64_t seed, uint64_t step, int rank,
                          int bucket0, void *stream);
 
+/* ---- 1-bit gradient wire ----------------------------------------------------
+ *
+ * What phase 1 of a sharded step carries under kf_exchange_reduce_shards_
+ * sign1_batch (kungfu_amd/csrc/kf_sign1.hip; tests/sign1_ref.py
+ * restates it in numpy): one sign bit per gradient element, one f32 scale per
+ * block of 64 consecutive elements of a piece, and an f32 residual per element
+ * that carries what was dropped to the next step (1-bit SGD, EF-signSGD,
+ * 1-bit Adam): 0.1875 bytes per element. The residual is part of the format.
+ *
+ * Pack, per block; g is the gradient widened to f32 (exactly), r the residual:
+ *   s     = g + r                 one f32 add
+ *   a     = the sum of |s| over the block as a pairwise tree of adjacent
+ *           elements, six levels: (|s0| + |s1|), (|s2| + |s3|), ... then the
+ *           sums of adjacent sums, in f32
+ *   scale = a * 2^-6              an f32, exact up to subnormal rounding
+ *   bit i = the sign bit of s[i] (-0 counts as negative), LSB first: element
+ *           i of the piece is bit i % 8 of byte i / 8
+ *   d[i]  = scale with the sign bit taken from bit i
+ *   r'[i] = s[i] - d[i]           one f32 subtract, stored over r
+ * A block is not finite when a is not finite (an inf or NaN element, or a sum
+ * that overflows): it sends the scale word 0x7fc00000 and zero bits and leaves
+ * 64 residuals of +0.0. An all-zero block has scale +0 and decodes to +-0.
+ * Unpack: d[i] as above; a block whose scale word is not finite is 0x7fc00000
+ * in every element whatever its bits, so a step that was not finite stays so.
+ * Per block |s - d|^2 = |s|^2 - |s|_1^2 / 64 <= |s|^2: the residual is bounded.
+ * Fold: kf_mx8_fold_batch's, over the decoded pieces in rank order, starting
+ * from rank 0's value: f32 adds, then / np (np > 0), then one RNE narrowing.
+ *
+ * The packed form of one bucket of `count` elements over `world` ranks is
+ * `world` pieces, piece j what rank j receives: q = count / world elements as
+ * q / 8 bytes of bits, q / 64 f32 scales, zero bytes up to the next multiple
+ * of 16; pieces lie kf_sign1_piece_bytes(q) = ceil((q / 8 + q / 16) / 16) * 16
+ * apart. The count % world tail is not packed, and its residuals are neither
+ * read nor written.
+ *
+ * kf_sign1_pack_ef_batch: grads[b] (dt: f32, bf16 or f16; only read) and
+ * residuals[b] (counts[b] f32 values, read and written) -> packed[b], world *
+ * kf_sign1_piece_bytes(counts[b] / world) bytes. kf_sign1_fold_batch:
+ * packed[b], the world pieces received for this rank's shard of q[b] elements
+ * -> out_shards[b] in dt. A bucket with q == 0 is not looked at. Checks, in
+ * kf_mx8_pack_batch's order and before any HIP call: nb < 0; (nb == 0: KF_OK;)
+ * a null table; dt (KF_ERR_DTYPE); world outside [1, KF_MAX_INPUTS]; np < 0
+ * (fold); then per non-empty bucket a null pointer, q % 64 != 0, a pointer off
+ * a 16-byte boundary; then (pack) a null residual table, a null residual, a
+ * residual off a 16-byte boundary. All KF_ERR_ARG but the dtype's, each with
+ * its kf_last_error() text. */
+size_t kf_sign1_piece_bytes(size_t q);
+int kf_sign1_pack_ef_batch(const void *const *grads, void *const *residuals, void *const *packed,
+                           const size_t *counts, int nb, int world, KungFu_Datatype dt, void *stream);
+int kf_sign1_fold_batch(const void *const *packed, void *const *out_shards, const size_t *q, int nb,
+                        int world, KungFu_Datatype dt, int np, void *stream);
+
 /* ---- Lion: a sign update, dense or over a 2-bit wire ------------------------
  *
  * Lion (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms") on
@@ -1509,6 +1561,14 @@ int kf_exchange_reduce_shards_mx8_ef_batch(kf_exchange_t *ex, void *const *grads
 int kf_exchange_reduce_shards_mx8_sr_batch(kf_exchange_t *ex, void *const *grads,
                                            const size_t *counts, int nb, KungFu_Datatype dt,
                                            uint64_t seed, uint64_t step, int *np, void *stream);
+/* kf_exchange_reduce_shards_mx8_ef_batch over the 1-bit gradient wire (above):
+ * kf_sign1_pack_ef_batch, the all-to-all of kf_sign1_piece_bytes(q) bytes per
+ * rank and bucket, kf_sign1_fold_batch with / world fused; the same body, so
+ * workspace, grouped phase 1, tails, timing and the world-1 built-in transport
+ * are the MXFP8 wire's. q must be a multiple of 64. *np = 0. */
+int kf_exchange_reduce_shards_sign1_batch(kf_exchange_t *ex, void *const *grads,
+                                          void *const *residuals, const size_t *counts, int nb,
+                                          KungFu_Datatype dt, int *np, void *stream);
 /* recv[r * n + k] = rank r's send[k], k < n: the transport's byte all_gather
  * of n doubles per rank (device pointers; send may be recv + rank * n). World
  * 1 on the built-in transport is a copy. */

@@ -168,6 +168,10 @@ EXPORTED = (
     "kf_lion_signs_batch",
     "kf_lion_apply_signs_batch",
     "kf_exchange_lion_batch",
+    "kf_sign1_piece_bytes",
+    "kf_sign1_pack_ef_batch",
+    "kf_sign1_fold_batch",
+    "kf_exchange_reduce_shards_sign1_batch",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -724,6 +728,14 @@ def load():
     lib.kf_exchange_reduce_shards_mx8_sr_batch.argtypes = [
         c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_u64, c_u64, P(c_int), c_void_p]
     lib.kf_exchange_reduce_shards_mx8_sr_batch.restype = c_int
+    # the 1-bit wire's entries take what their MXFP8 counterparts take
+    for name, like in (("kf_sign1_piece_bytes", lib.kf_mx8_piece_bytes),
+                       ("kf_sign1_pack_ef_batch", lib.kf_mx8_pack_ef_batch),
+                       ("kf_sign1_fold_batch", lib.kf_mx8_fold_batch),
+                       ("kf_exchange_reduce_shards_sign1_batch",
+                        lib.kf_exchange_reduce_shards_mx8_ef_batch)):
+        getattr(lib, name).argtypes = like.argtypes
+        getattr(lib, name).restype = like.restype
     lib.kf_lion_sign_bytes.argtypes = [c_size_t]
     lib.kf_lion_sign_bytes.restype = c_size_t
     lib.kf_lion_update_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_size_t),

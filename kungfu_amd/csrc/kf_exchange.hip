@@ -856,20 +856,29 @@ static Reduced reduce_to_shards(kf_exchange &x, const void *const *sends, void *
     return {rc, sc.np()};
 }
 
-// reduce_to_shards over the MXFP8 gradient wire (kf_mx8.hip):
-// the buckets' pieces packed into the workspace, one grouped phase 1 (the
-// packed pieces' all-to-all and the tails' all-gather), the received pieces
-// folded into this rank's shards with / world fused, then the tails' fold.
-// A single peer on the built-in transport packs and folds too (its one piece
-// is folded where it was packed); only the transport call is skipped.
-// `pack` is the entry that fills the pieces: kf_mx8_pack_batch, or its
-// error-feedback or stochastic-rounding variant.
-struct Mx8Pack {
+// reduce_to_shards over a packed gradient wire (MXFP8: kf_mx8.hip, DESIGN.md
+// §24; 1-bit: kf_sign1.hip, §27): the buckets' pieces packed into the
+// workspace, one grouped phase 1 (the packed pieces' all-to-all and the tails'
+// all-gather), the received pieces folded into this rank's shards with / world
+// fused, then the tails' fold. A single peer on the built-in transport packs
+// and folds too (its one piece is folded where it was packed); only the
+// transport call is skipped.
+// `pack` is the entry that fills the pieces: kf_mx8_pack_batch, its
+// error-feedback or stochastic-rounding variant, or
+// kf_sign1_pack_ef_batch; the piece size, the fold and the shard lengths'
+// block go with it and are the MXFP8 wire's unless set.
+struct WirePack {
     const char *name;
     std::function<int(void *const *packed, hipStream_t s)> run;
+    size_t (*piece_bytes)(size_t q) = kf_mx8_piece_bytes;
+    const char *fold_name           = "kf_mx8_fold_batch";
+    int (*fold)(const void *const *packed, void *const *shards, const size_t *q, int nb, int world,
+                KungFu_Datatype dt, int np, void *stream) = kf_mx8_fold_batch;
+    unsigned block    = 32;
+    const char *phase = "phase-1 collective (MXFP8 wire)";
 };
-static int reduce_to_shards_mx8(kf_exchange &x, void *const *grads, const size_t *counts, int nb,
-                                KungFu_Datatype dt, hipStream_t s, const Mx8Pack &pack)
+static int reduce_to_shards_wire(kf_exchange &x, void *const *grads, const size_t *counts, int nb,
+                                 KungFu_Datatype dt, hipStream_t s, const WirePack &pack)
 {
     Schedule sc{x, counts, nb, dt, KungFu_SUM, s};
     sc.a = KF_ALGO_REDUCE_SCATTER;  // Schedule's own all-to-all is off: fold() takes the tails only
@@ -884,7 +893,7 @@ static int reduce_to_shards_mx8(kf_exchange &x, void *const *grads, const size_t
     };
     for (int b = 0; b < nb; ++b) {
         qs[b]              = sc.q(b);
-        const size_t bytes = W * kf_mx8_piece_bytes(qs[b]);
+        const size_t bytes = W * pack.piece_bytes(qs[b]);
         if (qs[b]) take(send[b], bytes);
         if (qs[b] && !alone) take(sc.ws.shards[b], bytes);
         if (alone) sc.ws.shards[b] = send[b];
@@ -901,16 +910,16 @@ static int reduce_to_shards_mx8(kf_exchange &x, void *const *grads, const size_t
         recvd[b]  = sc.wsp + sc.ws.shards[b];
         shards[b] = sc.shard(static_cast<char *>(grads[b]), b);
     }
-    auto mx8 = [](int e, const char *what) {
+    auto wire = [](int e, const char *what) {
         return e == KF_OK ? KF_OK : fail(e, std::string(what) + ": " + kf_last_error());
     };
     auto phase1 = [&] {
-        const int e = mx8(pack.run(packed.data(), s), pack.name);
+        const int e = wire(pack.run(packed.data(), s), pack.name);
         if (e != KF_OK || alone) return e;
-        return grouped(x, 0, nb, "phase-1 collective (MXFP8 wire)", [&](int b) {
+        return grouped(x, 0, nb, pack.phase, [&](int b) {
             int t = 0;
             if (qs[b]) {
-                t = x.T->all_to_all(packed[b], sc.wsp + sc.ws.shards[b], kf_mx8_piece_bytes(qs[b]),
+                t = x.T->all_to_all(packed[b], sc.wsp + sc.ws.shards[b], pack.piece_bytes(qs[b]),
                                     x.comm, s);
             }
             if (t != 0 || !sc.t(b)) return t;
@@ -919,9 +928,9 @@ static int reduce_to_shards_mx8(kf_exchange &x, void *const *grads, const size_t
         });
     };
     auto folds = [&] {
-        const int e = mx8(kf_mx8_fold_batch(recvd.data(), shards.data(), qs.data(), nb, x.world, dt,
-                                            x.world, s),
-                          "kf_mx8_fold_batch");
+        const int e = wire(pack.fold(recvd.data(), shards.data(), qs.data(), nb, x.world, dt,
+                                     x.world, s),
+                           pack.fold_name);
         return e == KF_OK ? sc.fold(grads, x.world, 0, nb, s) : e;
     };
     return sc.serial(phase1, folds, nothing, nothing);
@@ -1931,11 +1940,11 @@ int kf_exchange_reduce_shards_batch(kf_exchange_t *ex, void *const *grads, const
     return red.rc;
 }
 
-// What the three MXFP8 reduce entries share: `entry`'s checks, then
-// reduce_to_shards_mx8 with `pack`; `residuals`: the error-feedback entry's table.
-static int exchange_reduce_mx8(const char *entry, kf_exchange_t *ex, void *const *grads,
-                               void *const *residuals, bool ef, const size_t *counts, int nb,
-                               KungFu_Datatype dt, int *np, void *stream, const Mx8Pack &pack)
+// What the packed wires' reduce entries share: `entry`'s checks, then
+// reduce_to_shards_wire with `pack`; `residuals`: the error-feedback entries' table.
+static int exchange_reduce_wire(const char *entry, kf_exchange_t *ex, void *const *grads,
+                                void *const *residuals, bool ef, const size_t *counts, int nb,
+                                KungFu_Datatype dt, int *np, void *stream, const WirePack &pack)
 {
     const std::string fn = std::string(entry) + ": ";
     if (!ex || nb < 0 || !np) return fail(KF_ERR_ARG, fn + "bad arguments");
@@ -1948,8 +1957,9 @@ static int exchange_reduce_mx8(const char *entry, kf_exchange_t *ex, void *const
     for (int b = 0; b < nb; ++b) {  // a count % world tail is allowed: it travels unquantized
         if (counts[b] == 0) continue;
         if (!grads[b]) return fail(KF_ERR_ARG, fn + "null bucket");
-        if ((counts[b] / W) % 32) {
-            return fail(KF_ERR_ARG, fn + "shard lengths (count / world) must be multiples of 32");
+        if ((counts[b] / W) % pack.block) {
+            return fail(KF_ERR_ARG, fn + "shard lengths (count / world) must be multiples of " +
+                                        std::to_string(pack.block));
         }
         if (off16(grads[b])) return fail(KF_ERR_ARG, fn + kShardOff16);
         if (ef && (!residuals[b] || off16(residuals[b]))) {
@@ -1958,7 +1968,7 @@ static int exchange_reduce_mx8(const char *entry, kf_exchange_t *ex, void *const
     }
     DeviceGuard g(ex->device);
     std::lock_guard<std::mutex> lk(ex->mu);
-    const int rc = reduce_to_shards_mx8(*ex, grads, counts, nb, dt, static_cast<hipStream_t>(stream), pack);
+    const int rc = reduce_to_shards_wire(*ex, grads, counts, nb, dt, static_cast<hipStream_t>(stream), pack);
     if (rc == KF_OK) *np = 0;
     return rc;
 }
@@ -1967,7 +1977,7 @@ int kf_exchange_reduce_shards_mx8_batch(kf_exchange_t *ex, void *const *grads,
                                         const size_t *counts, int nb, KungFu_Datatype dt, int *np,
                                         void *stream)
 {
-    return exchange_reduce_mx8(
+    return exchange_reduce_wire(
         "kf_exchange_reduce_shards_mx8_batch", ex, grads, nullptr, false, counts, nb, dt, np, stream,
         {"kf_mx8_pack_batch", [&](void *const *packed, hipStream_t s) {
              return kf_mx8_pack_batch(grads, packed, counts, nb, ex->world, dt, s);
@@ -1978,7 +1988,7 @@ int kf_exchange_reduce_shards_mx8_ef_batch(kf_exchange_t *ex, void *const *grads
                                            void *const *residuals, const size_t *counts, int nb,
                                            KungFu_Datatype dt, int *np, void *stream)
 {
-    return exchange_reduce_mx8(
+    return exchange_reduce_wire(
         "kf_exchange_reduce_shards_mx8_ef_batch", ex, grads, residuals, true, counts, nb, dt, np,
         stream, {"kf_mx8_pack_ef_batch", [&](void *const *packed, hipStream_t s) {
                      return kf_mx8_pack_ef_batch(grads, residuals, packed, counts, nb, ex->world, dt, s);
@@ -1989,12 +1999,27 @@ int kf_exchange_reduce_shards_mx8_sr_batch(kf_exchange_t *ex, void *const *grads
                                            const size_t *counts, int nb, KungFu_Datatype dt,
                                            uint64_t seed, uint64_t step, int *np, void *stream)
 {
-    return exchange_reduce_mx8(
+    return exchange_reduce_wire(
         "kf_exchange_reduce_shards_mx8_sr_batch", ex, grads, nullptr, false, counts, nb, dt, np,
         stream, {"kf_mx8_pack_sr_batch", [&](void *const *packed, hipStream_t s) {
                      return kf_mx8_pack_sr_batch(grads, packed, counts, nb, ex->world, dt, seed, step,
                                                  ex->rank, 0, s);
                  }});
+}
+
+int kf_exchange_reduce_shards_sign1_batch(kf_exchange_t *ex, void *const *grads,
+                                          void *const *residuals, const size_t *counts, int nb,
+                                          KungFu_Datatype dt, int *np, void *stream)
+{
+    return exchange_reduce_wire(
+        "kf_exchange_reduce_shards_sign1_batch", ex, grads, residuals, true, counts, nb, dt, np,
+        stream,
+        {"kf_sign1_pack_ef_batch",
+         [&](void *const *packed, hipStream_t s) {
+             return kf_sign1_pack_ef_batch(grads, residuals, packed, counts, nb, ex->world, dt, s);
+         },
+         kf_sign1_piece_bytes, "kf_sign1_fold_batch", kf_sign1_fold_batch, 64,
+         "phase-1 collective (1-bit wire)"});
 }
 
 int kf_exchange_adam_gated_batch(kf_exchange_t *ex, void *const *params, void *const *grads,

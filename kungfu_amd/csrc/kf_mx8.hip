@@ -66,8 +66,8 @@
 #include <vector>
 
 #include "kf_philox.hpp"
-#include "kf_sgd_elt.hpp"
 #include "kf_update_batch.hpp"
+#include "kf_wire_elt.hpp"
 
 namespace kf
 {
@@ -140,31 +140,6 @@ struct Mx8PackArgs {
 };
 static_assert(sizeof(Mx8PackArgs) <= 1024, "kernarg budget");
 
-// the lane's 8 elements, widened (exactly); zeros outside the shard
-template <typename T>
-__device__ __forceinline__ void mx8_load8(const void *src, size_t u, bool active, float (&x)[8])
-{
-    u32x4 r0 = {0, 0, 0, 0}, r1 = {0, 0, 0, 0};
-    if constexpr (std::is_same<T, float>::value) {
-        if (active) {
-            r0 = ld_u4<1>(src, 2 * u);
-            r1 = ld_u4<1>(src, 2 * u + 1);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            x[i]     = __uint_as_float(r0[i]);
-            x[4 + i] = __uint_as_float(r1[i]);
-        }
-    } else {
-        if (active) r0 = ld_u4<1>(src, u);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            x[2 * i]     = SgdElt<T>::widen(static_cast<uint16_t>(r0[i]));
-            x[2 * i + 1] = SgdElt<T>::widen(static_cast<uint16_t>(r0[i] >> 16));
-        }
-    }
-}
-
 template <typename T>
 __device__ __forceinline__ void mx8_pack_body(const Mx8PackSeg &h, size_t blk, size_t nblk)
 {
@@ -178,7 +153,7 @@ __device__ __forceinline__ void mx8_pack_body(const Mx8PackSeg &h, size_t blk, s
         const size_t u    = t * B + threadIdx.x;
         const bool active = u < nunit;  // uniform over a quad: n % 32 == 0
         float x[8];
-        mx8_load8<T>(h.src, u, active, x);
+        wire_load8<T>(h.src, u, active, x);
         unsigned mag = 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) mag = max(mag, __float_as_uint(x[i]) & 0x7fffffffu);
@@ -298,7 +273,7 @@ __device__ __forceinline__ void mx8_pack_var_body(const SEG &h, size_t blk, size
         const size_t u    = t * B + threadIdx.x;
         const bool active = u < nunit;  // uniform over a quad: n % 32 == 0
         float x[8];
-        mx8_load8<T>(h.src, u, active, x);
+        wire_load8<T>(h.src, u, active, x);
         if constexpr (EF) {
             u32x4 r0 = {0, 0, 0, 0}, r1 = {0, 0, 0, 0};
             if (active) {
@@ -407,14 +382,6 @@ __device__ __forceinline__ void mx8_decode16(const Mx8Raw &r, float (&v)[16])
     }
 }
 
-// the one narrowing of a finished f32 value: never fused with the operation
-// that made it (kf_reduce_kernels.hpp f32_product_to_f16)
-template <typename T> __device__ __forceinline__ uint16_t mx8_narrow(float s)
-{
-    asm("" : "+v"(s));
-    return SgdElt<T>::narrow(s);
-}
-
 template <typename T, int DIV>
 __device__ __forceinline__ void mx8_fold_body(const Mx8FoldSeg &h, int world, const Div &d,
                                               size_t blk, size_t nblk)
@@ -441,29 +408,7 @@ __device__ __forceinline__ void mx8_fold_body(const Mx8FoldSeg &h, int world, co
             }
             cur = next;
         }
-        if constexpr (DIV != 0) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = SgdElt<float>::div<DIV == 1>(acc[i], d);
-        }
-        if constexpr (std::is_same<T, float>::value) {
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                st_u4<0>(h.out, 4 * u + w,
-                         u32x4{__float_as_uint(acc[4 * w]), __float_as_uint(acc[4 * w + 1]),
-                               __float_as_uint(acc[4 * w + 2]), __float_as_uint(acc[4 * w + 3])});
-            }
-        } else {
-#pragma unroll
-            for (int w = 0; w < 2; ++w) {
-                u32x4 raw;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    raw[i] = static_cast<unsigned>(mx8_narrow<T>(acc[8 * w + 2 * i])) |
-                             (static_cast<unsigned>(mx8_narrow<T>(acc[8 * w + 2 * i + 1])) << 16);
-                }
-                st_u4<0>(h.out, 2 * u + w, raw);
-            }
-        }
+        wire_store16<T, DIV>(h.out, u, acc, d);
     }
 }
 

@@ -32,7 +32,7 @@ from .base import OP, OP_NAMES
 from .ops import kungfu_dtype
 
 ALGOS = {"auto": 0, "rs": 1, "a2a": 2, "rs_avg": 3}
-GRAD_WIRES = (None, "mx8")  # NativeExchange.set_grad_wire
+GRAD_WIRES = (None, "mx8", "sign1")  # NativeExchange.set_grad_wire
 # kf_exchange_phase_times' order: phase 1 (reduce-scatter, or all-to-all for
 # the rank-order fold), phase 2 (/np epilogue or the fold), phase 3
 # (all-gather), the SMA blend
@@ -169,9 +169,24 @@ class NativeExchange:
         (an int in [0, 2**64)), the number of reduce_shards_ calls so far,
         this rank and the bucket's index in the call. That count is a
         host-side kernel argument: a captured graph replays the draws of the
-        step it was captured at."""
+        step it was captured at.
+
+        "sign1" (with error_feedback=True, which is part of the format;
+        DESIGN.md §27): one sign bit per element and one f32 scale per block
+        of 64, the mean of |g + r| over the block: 0.1875 bytes per element.
+        reduce_shards_ is kf_exchange_reduce_shards_sign1_batch; shard lengths
+        must be multiples of 64 (the optimizers' are). Lossy per step by
+        design: a step sends signs and one magnitude per block, and the f32
+        residual (the same tensors as above, grad_residuals() and
+        reset_grad_residuals() included) carries the rest to later steps.
+        What is said above of the residual holds: it is in the gradients'
+        units, so a caller rescales it on a loss-scale change; a skipped
+        gated step has still consumed its gradient; there is no per-step host
+        state, so a captured graph replays it. Without error_feedback=True,
+        or with rounding="stochastic", the wire is refused: a sign wire
+        without memory does not converge."""
         if wire not in GRAD_WIRES:
-            raise ValueError("grad_wire must be None or 'mx8' (got %r)" % (wire,))
+            raise ValueError("grad_wire must be None, 'mx8' or 'sign1' (got %r)" % (wire,))
         if rounding not in ("nearest", "stochastic"):
             raise ValueError("grad_wire rounding must be 'nearest' or 'stochastic' (got %r)"
                              % (rounding,))
@@ -180,6 +195,9 @@ class NativeExchange:
             raise ValueError("grad_wire: error_feedback and rounding need a wire")
         if error_feedback and stochastic:
             raise ValueError("grad_wire: error_feedback or stochastic rounding, not both")
+        if wire == "sign1" and not error_feedback:
+            raise ValueError("grad_wire 'sign1' needs error_feedback=True and rounding='nearest': "
+                             "the residual is part of the format")
         if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
             raise ValueError("grad_wire seed must be an int in [0, 2**64), not %r" % (seed,))
         self._wire = wire
@@ -522,21 +540,23 @@ class NativeExchange:
         update must still divide by: the world after a reduce-scatter, 0 after
         the fold or under rs_avg, 1 at world 1 on the built-in transport.
         Under set_grad_wire("mx8"): kf_exchange_reduce_shards_mx8_batch (or its
-        _ef / _sr variant, as set_grad_wire's options say), and 0."""
+        _ef / _sr variant, as set_grad_wire's options say), and 0; under
+        "sign1": kf_exchange_reduce_shards_sign1_batch, and 0."""
         grads = list(grad_buckets)
         if grads:
             self._check(grads)
         np_ = ctypes.c_int(0)
         dt = int(kungfu_dtype(grads[0])) if grads else 0x20408
-        if getattr(self, "_wire", None):  # "mx8": the only wire
+        wire = getattr(self, "_wire", None)
+        if wire:
             tabs = (self._h, _lib.ptr_array([g.data_ptr() for g in grads]))
             tail = (_arr(ctypes.c_size_t, [g.numel() for g in grads]), len(grads), dt)
             end = (ctypes.byref(np_), torch.cuda.current_stream(self.device).cuda_stream)
             mode = getattr(self, "_wire_mode", None)
-            if mode == "ef":
+            if mode == "ef":  # "sign1" has no other mode
                 res = _lib.ptr_array([r.data_ptr() for r in self._grad_residuals(grads)])
-                name = "kf_exchange_reduce_shards_mx8_ef_batch"
-                rc = self.lib.kf_exchange_reduce_shards_mx8_ef_batch(*tabs, res, *tail, *end)
+                name = "kf_exchange_reduce_shards_%s_batch" % {"mx8": "mx8_ef", "sign1": "sign1"}[wire]
+                rc = getattr(self.lib, name)(*tabs, res, *tail, *end)
             elif mode == "sr":
                 name = "kf_exchange_reduce_shards_mx8_sr_batch"
                 rc = self.lib.kf_exchange_reduce_shards_mx8_sr_batch(

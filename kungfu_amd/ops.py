@@ -776,13 +776,14 @@ def mx8_pack_batch_(grads, world, packed=None, stream=None):
     return packed
 
 
-def _mx8_pack_variant(name, grads, world, packed, stream, call):
-    """What the two pack variants share with mx8_pack_batch_: its checks, then
+def _mx8_pack_variant(name, grads, world, packed, stream, call, piece_bytes=mx8_piece_bytes):
+    """What the pack variants (and the 1-bit wire's pack, with its own
+    piece_bytes) share with mx8_pack_batch_: its checks, then
     call(lib, grad pointers, packed pointers, counts, nb, dtype, stream)."""
     grads, world = list(grads), int(world)
     if world < 1:
         raise ValueError("%s: world >= 1" % name)
-    need = [world * mx8_piece_bytes(g.numel() // world) for g in grads]
+    need = [world * piece_bytes(g.numel() // world) for g in grads]
     if packed is None:
         packed = [torch.empty(n, dtype=torch.uint8, device=g.device) for n, g in zip(need, grads)]
     packed = list(packed)
@@ -802,24 +803,53 @@ def _mx8_pack_variant(name, grads, world, packed, stream, call):
     return packed
 
 
+def _wire_pack_ef(name, piece_bytes, grads, residuals, world, packed, stream):
+    """An error-feedback pack (kf_<name>): the residuals' checks, then
+    _mx8_pack_variant's."""
+    grads, residuals = list(grads), list(residuals)
+    if len(residuals) != len(grads) or any(
+            r.dtype != torch.float32 or r.numel() != g.numel() or not r.is_contiguous()
+            for r, g in zip(residuals, grads)):
+        raise ValueError("%s: one contiguous f32 residual of its bucket's length per bucket" % name)
+    _check_dev(grads + residuals)
+    res = _lib.ptr_array([r.data_ptr() for r in residuals])
+    entry = "kf_" + name.rstrip("_")
+    return _mx8_pack_variant(
+        name, grads, world, packed, stream,
+        lambda lib, g, p, cnt, nb, dt, s: getattr(lib, entry)(g, res, p, cnt, nb, int(world), dt, s),
+        piece_bytes)
+
+
+def _wire_fold(name, piece_bytes, packed, out_shards, world, np_, stream):
+    """A wire's fold (kf_<name>): one shard per packed tensor of world pieces."""
+    packed, outs, world = list(packed), list(out_shards), int(world)
+    if len(packed) != len(outs):
+        raise ValueError("%s: one shard per packed tensor" % name)
+    if not outs:
+        return outs
+    _check_dev(packed + outs)
+    for p, o in zip(packed, outs):
+        if o.dtype != outs[0].dtype or p.dtype != torch.uint8 or \
+                p.numel() != world * piece_bytes(o.numel()):
+            raise ValueError("%s: one dtype, and uint8 tensors of world pieces" % name)
+    q = (ctypes.c_size_t * len(outs))(*[o.numel() for o in outs])
+    entry = "kf_" + name.rstrip("_")
+    rc = getattr(_lib.load(), entry)(_lib.ptr_array([p.data_ptr() for p in packed]),
+                                     _lib.ptr_array([o.data_ptr() for o in outs]), q, len(outs),
+                                     world, int(kungfu_dtype(outs[0])), int(np_),
+                                     _stream(stream, outs[0].device))
+    _lib.check(rc, entry, source="")
+    return outs
+
+
 def mx8_pack_ef_batch_(grads, residuals, world, packed=None, stream=None):
     """mx8_pack_batch_ with error feedback (kf_mx8_pack_ef_batch, DESIGN.md
     §25): residuals[b] is an f32 tensor of grads[b]'s length; every piece packs
     g + r and leaves r = (g + r) - unpack(what was packed) in place, +0.0 over a
     block that was not finite. grads are only read; the numel % world tail's
     residuals are not touched."""
-    grads, residuals = list(grads), list(residuals)
-    if len(residuals) != len(grads) or any(
-            r.dtype != torch.float32 or r.numel() != g.numel() or not r.is_contiguous()
-            for r, g in zip(residuals, grads)):
-        raise ValueError("mx8_pack_ef_batch_: one contiguous f32 residual of its bucket's length "
-                         "per bucket")
-    _check_dev(grads + residuals)
-    res = _lib.ptr_array([r.data_ptr() for r in residuals])
-    return _mx8_pack_variant(
-        "mx8_pack_ef_batch_", grads, world, packed, stream,
-        lambda lib, g, p, cnt, nb, dt, s: lib.kf_mx8_pack_ef_batch(g, res, p, cnt, nb, int(world), dt,
-                                                                   s))
+    return _wire_pack_ef("mx8_pack_ef_batch_", mx8_piece_bytes, grads, residuals, world, packed,
+                         stream)
 
 
 def mx8_pack_sr_batch_(grads, world, seed, step, rank, bucket0=0, packed=None, stream=None):
@@ -839,23 +869,38 @@ def mx8_fold_batch_(packed, out_shards, world, np_=0, stream=None):
     f32 in rank order) / np_ (np_ > 0), narrowed once to the shard's dtype
     (kf_mx8_fold_batch), all buckets in one launch. packed[b]: uint8, world *
     mx8_piece_bytes(q) bytes for a shard of q elements (a multiple of 32)."""
-    packed, outs, world = list(packed), list(out_shards), int(world)
-    if len(packed) != len(outs):
-        raise ValueError("mx8_fold_batch_: one shard per packed tensor")
-    if not outs:
-        return outs
-    _check_dev(packed + outs)
-    for p, o in zip(packed, outs):
-        if o.dtype != outs[0].dtype or p.dtype != torch.uint8 or \
-                p.numel() != world * mx8_piece_bytes(o.numel()):
-            raise ValueError("mx8_fold_batch_: one dtype, and uint8 tensors of world pieces")
-    q = (ctypes.c_size_t * len(outs))(*[o.numel() for o in outs])
-    rc = _lib.load().kf_mx8_fold_batch(_lib.ptr_array([p.data_ptr() for p in packed]),
-                                       _lib.ptr_array([o.data_ptr() for o in outs]), q, len(outs),
-                                       world, int(kungfu_dtype(outs[0])), int(np_),
-                                       _stream(stream, outs[0].device))
-    _lib.check(rc, "kf_mx8_fold_batch", source="")
-    return outs
+    return _wire_fold("mx8_fold_batch_", mx8_piece_bytes, packed, out_shards, world, np_, stream)
+
+
+# -- the 1-bit gradient wire (include/kungfu_amd.h, DESIGN.md §27) -------------
+
+SIGN1_BLOCK = 64                 # elements per f32 scale
+
+
+def sign1_piece_bytes(q):
+    """The bytes of one packed piece of q elements (kf_sign1_piece_bytes):
+    q // 8 bytes of sign bits, q // 64 f32 scales, rounded up to 16."""
+    return int(_lib.load().kf_sign1_piece_bytes(int(q)))
+
+
+def sign1_pack_ef_batch_(grads, residuals, world, packed=None, stream=None):
+    """Every flat f32, bf16 or f16 bucket of `grads` as `world` packed 1-bit
+    pieces (kf_sign1_pack_ef_batch), all buckets in one launch: per block of 64
+    elements the sign bits of s = g + r and the scale mean(|s|); residuals[b]
+    (f32, grads[b]'s length) is left as s - (the scale with s's sign), +0.0
+    over a block that was not finite. packed[b] is a uint8 tensor of world *
+    sign1_piece_bytes(numel // world) bytes, new unless given. numel // world
+    must be a multiple of 64; the numel % world tail is not packed and its
+    residuals are not touched. grads are only read."""
+    return _wire_pack_ef("sign1_pack_ef_batch_", sign1_piece_bytes, grads, residuals, world, packed,
+                         stream)
+
+
+def sign1_fold_batch_(packed, out_shards, world, np_=0, stream=None):
+    """mx8_fold_batch_ over 1-bit pieces (kf_sign1_fold_batch): packed[b] is
+    uint8, world * sign1_piece_bytes(q) bytes for a shard of q elements (a
+    multiple of 64)."""
+    return _wire_fold("sign1_fold_batch_", sign1_piece_bytes, packed, out_shards, world, np_, stream)
 
 
 # -- LAMB (include/kungfu_amd.h "LAMB", DESIGN.md §17) -------------------------
