@@ -947,6 +947,70 @@ int kf_lion_apply_signs_batch(void *const *params, const void *const *codes, con
                               KungFu_Datatype dt, const kf_lion_hyper *hyper, uint32_t key,
                               void *stream);
 
+/* ---- Muon: momentum, then a Newton-Schulz orthogonalised update ---------------
+ *
+ * Muon on the sharded step (kungfu_amd/csrc/kf_muon.hip). The
+ * momentum is f32 and sharded; its bf16 direction is gathered, and every rank
+ * orthogonalises every tensor (rows x cols = shape[0] x the rest) with
+ *   X = d / (|d|_F + 1e-7)
+ *   steps times:  A = X X^T ;  B = b*A + c*A*A ;  X = a*X + B*X
+ *   (rows > cols: A = X^T X and X = a*X + X*B), (a, b, c) = (3.4445, -4.7750, 2.0315)
+ *   p = dk*p + nc*X       dk = 1 - lr*weight_decay, nc = -lr*scale
+ * with scale = sqrt(max(1, rows / cols)), the caller's to compute. X, A and B
+ * are bf16; every product accumulates in f32 and is narrowed once.
+ *
+ * kf_muon_momentum_batch, per element, f32, each parenthesis one IEEE
+ * operation: g = np > 0 ? sum / np : sum (kf_sgd's Div); m' = (mu*m) + g;
+ * d = nesterov ? g + (mu*m') : m', stored as bf16 round-to-nearest-even at
+ * dirs[b]. dt is the gradients' and the momentum's type, KungFu_FLOAT.
+ * Pointers are 16-byte aligned and counts multiples of 8.
+ *
+ * kf_muon_scale_batch: xs[b][i] = bf16(d[b][i] * s_b), s_b = (float)(1 /
+ * (sqrt(sq[b]) + 1e-7)) with sq[b] an f64 on the DEVICE (kf_segnorm_run's
+ * out over the same tensors): no host synchronisation. kf_muon_apply_batch:
+ * the last line above on f32 params[b] with bf16 xs[b]; dk and nc are
+ * computed in double and cast once. Both take tensors at any element of a
+ * bucket: pointers are aligned to their element only.
+ *
+ * kf_muon_gemm_grouped: for every problem i < count, in one launch per 32
+ * problems,  C = alpha*Cin + beta*op(A)*op(B)  with op(A) m x k, op(B) k x n,
+ * all row-major bf16 (dt is KungFu_BFLOAT16): A is stored m x k (trans_a = 0)
+ * or k x m (1), B k x n (trans_b = 0) or n x k (1), each with its leading
+ * dimension in elements. cin may be NULL (then alpha is not read) and may be
+ * c itself; c must not overlap a or b. Every m, n, k >= 1 is taken as it is:
+ * ragged edges are handled in the kernel. Per element
+ *   C = bf16((alpha*Cin) + (beta*acc)),  acc the f32 sum of the exact products
+ * in the order of the kernel's K walk (no atomics, no split-K: the same bits
+ * on every run and rank). kf_muon_tile() is the kernel's block tile (both
+ * ways), for tests; it needs no device.
+ *
+ * Checks, all before any HIP call, in this order. The batch entries: nb < 0;
+ * (nb == 0 is KF_OK); dt (KF_ERR_DTYPE); a null table; per non-empty segment
+ * a null pointer, then a misaligned one; and for the momentum np < 0, then a
+ * counts[b] % 8 != 0. The GEMM: count < 0; (0 is KF_OK); dt; a null table;
+ * then per problem a dimension below 1, k above INT_MAX - 32, a null a, b or
+ * c, a pointer off a 2-byte boundary, trans_a or trans_b not 0 or 1, a
+ * leading dimension smaller than the stored row, more than 2^22 block tiles
+ * in one problem.
+ * All KF_ERR_ARG but the dtype. */
+typedef struct { double momentum; int nesterov; } kf_muon_hyper;
+typedef struct { double lr, weight_decay, scale; } kf_muon_apply;
+typedef struct {
+    const void *a, *b, *cin;
+    void *c;
+    int m, n, k, lda, ldb, ldcin, ldc, trans_a, trans_b;
+} kf_muon_gemm;
+int kf_muon_tile(void);
+int kf_muon_momentum_batch(const void *const *grads, void *const *moms, void *const *dirs,
+                           const size_t *counts, int nb, KungFu_Datatype dt, int np,
+                           const kf_muon_hyper *hyper, void *stream);
+int kf_muon_scale_batch(const void *const *dirs, void *const *xs, const size_t *counts,
+                        const double *sq, int nb, void *stream);
+int kf_muon_gemm_grouped(const kf_muon_gemm *problems, int count, KungFu_Datatype dt, float alpha,
+                         float beta, void *stream);
+int kf_muon_apply_batch(void *const *params, const void *const *xs, const size_t *counts,
+                        const kf_muon_apply *hyper, int nb, KungFu_Datatype dt, void *stream);
+
 /* ---- gradient monitors: segmented squared norms ------------------------- */
 
 /* What MonitorGradientNoiseScaleOptimizer and MonitorGradientVarianceOptimizer
@@ -1606,6 +1670,23 @@ int kf_exchange_lion_batch(kf_exchange_t *ex, void *const *params, void *const *
                            void *const *mom_shards, const size_t *counts, int nb,
                            KungFu_Datatype dt, const kf_lion_hyper *hyper, const uint32_t *streams,
                            uint32_t key, int algo, int sign_wire, void *stream);
+/* Phases 1 to 3 of the Muon step ("Muon" above): phase 1 of the f32 gradient
+ * buckets, kf_muon_momentum_batch on this rank's shards with the / world fused
+ * (mom_shards[b]: q = counts[b] / world f32 elements), writing the bf16
+ * direction at dirs[b] + rank * q, and the in-place all-gather of the
+ * direction buckets dirs[b] (counts[b] bf16 elements each): half the bytes of
+ * the parameters' gather. World 1 on the built-in transport runs the kernel
+ * alone. dt is the gradients' and the momentum's type, KungFu_FLOAT
+ * (KF_ERR_DTYPE otherwise). Checks on every rank before any collective: ex
+ * and nb; dt; (nb == 0 is KF_OK); the tables; the algo; and per non-empty
+ * bucket kf_exchange_adam_batch's over grads and dirs (null buckets,
+ * counts[b] % world, the momentum shard, alignment), then q % 8.
+ * Un-pipelined; after its first call it allocates nothing and never waits on
+ * the host. The Newton-Schulz iteration and the update follow on every rank
+ * (kf_muon_scale_batch, kf_muon_gemm_grouped, kf_muon_apply_batch). */
+int kf_exchange_muon_batch(kf_exchange_t *ex, void *const *dirs, void *const *grads,
+                           void *const *mom_shards, const size_t *counts, int nb,
+                           KungFu_Datatype dt, const kf_muon_hyper *hyper, int algo, void *stream);
 /* Pipelined schedule for the batch calls (default 1 = off): the buckets of a
  * call are split into `groups` groups of consecutive buckets of about equal
  * bytes; the RCCL phases stay on the caller's stream in the same order on

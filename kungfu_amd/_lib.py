@@ -172,6 +172,12 @@ EXPORTED = (
     "kf_sign1_pack_ef_batch",
     "kf_sign1_fold_batch",
     "kf_exchange_reduce_shards_sign1_batch",
+    "kf_muon_tile",
+    "kf_muon_momentum_batch",
+    "kf_muon_scale_batch",
+    "kf_muon_gemm_grouped",
+    "kf_muon_apply_batch",
+    "kf_exchange_muon_batch",
 )
 
 # kf_segnorm_run modes (include/kungfu_amd.h)
@@ -251,6 +257,33 @@ def lion_hyper_array(hypers):
         a.lr, a.weight_decay = float(h["lr"]), float(h.get("weight_decay", 0.0))
         a.beta1, a.beta2 = (float(b) for b in h.get("betas", (0.9, 0.99)))
     return arr
+
+
+class MuonHyper(ctypes.Structure):
+    """kf_muon_hyper (include/kungfu_amd.h): one segment's momentum scalars."""
+    _fields_ = [("momentum", ctypes.c_double), ("nesterov", ctypes.c_int)]
+
+
+def muon_hyper_array(hypers):
+    """A kf_muon_hyper[] from dicts with momentum and optionally nesterov."""
+    arr = (MuonHyper * max(1, len(hypers)))()
+    for a, h in zip(arr, hypers):
+        a.momentum, a.nesterov = float(h["momentum"]), int(bool(h.get("nesterov", False)))
+    return arr
+
+
+class MuonApply(ctypes.Structure):
+    """kf_muon_apply (include/kungfu_amd.h): one tensor's update scalars."""
+    _fields_ = [("lr", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("scale", ctypes.c_double)]
+
+
+class MuonGemm(ctypes.Structure):
+    """kf_muon_gemm (include/kungfu_amd.h): one problem of the grouped GEMM."""
+    _fields_ = [("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("cin", ctypes.c_void_p),
+                ("c", ctypes.c_void_p)] + \
+               [(k, ctypes.c_int) for k in ("m", "n", "k", "lda", "ldb", "ldcin", "ldc",
+                                            "trans_a", "trans_b")]
 
 
 class LambGroup(ctypes.Structure):
@@ -752,6 +785,23 @@ def load():
                                            P(c_size_t), c_int, c_int, P(LionHyper), P(u32), u32,
                                            c_int, c_int, c_void_p]
     lib.kf_exchange_lion_batch.restype = c_int
+    lib.kf_muon_tile.argtypes = []
+    lib.kf_muon_tile.restype = c_int
+    lib.kf_muon_momentum_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_size_t), c_int,
+                                           c_int, c_int, P(MuonHyper), c_void_p]
+    lib.kf_muon_momentum_batch.restype = c_int
+    lib.kf_muon_scale_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_size_t), c_void_p, c_int,
+                                        c_void_p]
+    lib.kf_muon_scale_batch.restype = c_int
+    lib.kf_muon_gemm_grouped.argtypes = [P(MuonGemm), c_int, c_int, ctypes.c_float, ctypes.c_float,
+                                         c_void_p]
+    lib.kf_muon_gemm_grouped.restype = c_int
+    lib.kf_muon_apply_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_size_t), P(MuonApply), c_int,
+                                        c_int, c_void_p]
+    lib.kf_muon_apply_batch.restype = c_int
+    lib.kf_exchange_muon_batch.argtypes = [c_void_p, P(c_void_p), P(c_void_p), P(c_void_p),
+                                           P(c_size_t), c_int, c_int, P(MuonHyper), c_int, c_void_p]
+    lib.kf_exchange_muon_batch.restype = c_int
     _lib = lib
     # HIP resources go back while the runtime is alive, before the C exit
     # handlers run (include/kungfu_amd.h kf_shutdown)

@@ -2195,6 +2195,75 @@ int kf_exchange_lion_batch(kf_exchange_t *ex, void *const *params, void *const *
                      LionStep{params, mom_shards, hyper, streams, key, sign_wire != 0});
 }
 
+// Phases 1 to 3 of the Muon step (kf_muon.hip): lion_step's
+// dense shape, but what phase 3 gathers is not what phase 1 reduced: the f32
+// gradient buckets come in, the momentum kernel writes this rank's slice of
+// the bf16 direction buckets (the same element offsets, half the bytes), and
+// those are gathered. A single peer on the built-in transport runs the kernel
+// over the whole buckets.
+static int muon_step(kf_exchange &x, void *const *dirs, void *const *grads, void *const *moms,
+                     const size_t *counts, int nb, int algo, hipStream_t s,
+                     const kf_muon_hyper *hyper)
+{
+    Schedule sc{x, counts, nb, KungFu_FLOAT, KungFu_SUM, s};
+    const bool alone = sc.alone();
+    int rc           = alone ? KF_OK : sc.resolve(algo, 1);
+    if (rc != KF_OK) return rc;
+    if (alone) sc.ws = kf::Workspace{std::vector<size_t>(nb, 0), std::vector<size_t>(nb, 0)};
+    else rc = sc.reserve();
+    if (rc != KF_OK) return rc;
+    const int np = alone ? 1 : sc.np();
+    std::vector<const void *> gs(nb);
+    std::vector<void *> ds(nb);
+    std::vector<size_t> qs(nb);
+    for (int b = 0; b < nb; ++b) {
+        qs[b] = sc.q(b);
+        gs[b] = sc.shard(static_cast<const char *>(grads[b]), b);
+        ds[b] = static_cast<char *>(dirs[b]) + sc.r * qs[b] * sizeof(uint16_t);
+    }
+    auto phase1 = [&] { return alone ? KF_OK : sc.scatter(grads, grads, 0, nb); };
+    auto phase2 = [&] {
+        int e = alone ? KF_OK : sc.fold(grads, x.world, 0, nb, s);
+        if (e != KF_OK) return e;
+        e = kf_muon_momentum_batch(gs.data(), moms, ds.data(), qs.data(), nb, KungFu_FLOAT, np, hyper, s);
+        return e == KF_OK ? KF_OK : fail(e, std::string("kf_muon_momentum_batch: ") + kf_last_error());
+    };
+    auto phase3 = [&] {
+        if (alone) return static_cast<int>(KF_OK);
+        return grouped(x, 0, nb, "all_gather of the directions", [&](int b) {
+            char *buf          = static_cast<char *>(dirs[b]);
+            const size_t bytes = qs[b] * sizeof(uint16_t);
+            return qs[b] ? x.T->all_gather(buf + sc.r * bytes, buf, bytes, x.comm, s) : 0;
+        });
+    };
+    return sc.serial(phase1, phase2, phase3, nothing);
+}
+
+int kf_exchange_muon_batch(kf_exchange_t *ex, void *const *dirs, void *const *grads,
+                           void *const *mom_shards, const size_t *counts, int nb,
+                           KungFu_Datatype dt, const kf_muon_hyper *hyper, int algo, void *stream)
+{
+    const std::string fn = "kf_exchange_muon_batch: ";
+    if (!ex || nb < 0) return fail(KF_ERR_ARG, fn + "bad arguments");
+    if (dt != KungFu_FLOAT) return fail(KF_ERR_DTYPE, fn + "f32 gradients and momentum only");
+    if (nb == 0) return KF_OK;
+    if (!dirs || !grads || !mom_shards || !counts || !hyper) return fail(KF_ERR_ARG, fn + "null table");
+    if (check_algo(algo) != KF_OK) return KF_ERR_ARG;
+    const ShardTab m{mom_shards, "every non-empty bucket needs its momentum shard"};
+    const size_t W = static_cast<size_t>(ex->world);
+    for (int b = 0; b < nb; ++b) {
+        const int rc = check_shard_bucket(fn, {grads, dirs}, {m}, b, counts[b], ex->world, 4);
+        if (rc != KF_OK) return rc;
+        if ((counts[b] / W) % 8) {  // a bf16 shard of whole 16-byte vectors
+            return fail(KF_ERR_ARG, fn + "shard lengths (count / world) must be multiples of 8");
+        }
+    }
+    DeviceGuard g(ex->device);
+    std::lock_guard<std::mutex> lk(ex->mu);
+    return muon_step(*ex, dirs, grads, mom_shards, counts, nb, algo, static_cast<hipStream_t>(stream),
+                     hyper);
+}
+
 int kf_exchange_adam_batch(kf_exchange_t *ex, void *const *params, void *const *grads,
                            void *const *exp_avg_shards, void *const *exp_avg_sq_shards,
                            const size_t *counts, int nb, KungFu_Datatype dt,

@@ -466,6 +466,46 @@ class NativeExchange:
             ([j * n for n in q for j in range(W)], [s for s in streams for _ in range(W)], key))
         return params
 
+    def muon_step_(self, dir_buckets, grad_buckets, mom_shards, hypers):
+        """Phases 1 to 3 of the Muon step (kf_exchange_muon_batch, DESIGN.md
+        §28), queued on the current stream: phase 1 of the f32 gradient
+        buckets, ops.muon_momentum_batch_'s kernel on this rank's shards (f32
+        momentum of numel // world elements, the / world inside it) writing
+        this rank's slice of the bf16 direction buckets, and the in-place
+        all-gather of those: half the bytes of the parameters' all-gather.
+        hypers[b] is a dict with momentum and optionally nesterov. The
+        Newton-Schulz iteration and the update then run on every rank
+        (ops.MuonPlan, ops.muon_apply_batch_). The gradient buckets are
+        scratch. Under set_grad_wire phase 1 is reduce_shards_ over that wire
+        and the same kernel and gather_params_ run from here."""
+        dirs, grads, moms, hypers = (list(x) for x in (dir_buckets, grad_buckets, mom_shards, hypers))
+        if not all(len(x) == len(dirs) for x in (grads, moms, hypers)):
+            raise ValueError("muon_step_: one grad bucket, momentum shard and hyper per bucket")
+        if not dirs:
+            return dirs
+        self._check(dirs)
+        self._check(grads + moms)
+        if dirs[0].dtype != torch.bfloat16 or grads[0].dtype != torch.float32 or any(
+                g.numel() != d.numel() or m.numel() * self.world != d.numel()
+                for d, g, m in zip(dirs, grads, moms)):
+            raise ValueError("muon_step_: bf16 direction buckets, f32 gradient buckets of their "
+                             "size and f32 momentum shards of numel // world elements")
+        if getattr(self, "_wire", None):
+            from . import ops
+            np_ = self.reduce_shards_(grads)
+            ops.muon_momentum_batch_(self.grad_shards_(grads), moms, self.grad_shards_(dirs), hypers,
+                                     np_)
+            return self.gather_params_(dirs)
+        rc = self.lib.kf_exchange_muon_batch(
+            self._h, _lib.ptr_array([d.data_ptr() for d in dirs]),
+            _lib.ptr_array([g.data_ptr() for g in grads]),
+            _lib.ptr_array([m.data_ptr() for m in moms]),
+            _arr(ctypes.c_size_t, [d.numel() for d in dirs]), len(dirs),
+            int(kungfu_dtype(grads[0])), _lib.muon_hyper_array(hypers), ALGOS[self.algo],
+            torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(rc, "kf_exchange_muon_batch")
+        return dirs
+
     def _shard_call(self, name, fn, cname, hyper_array, param_buckets, grad_buckets,
                     state_shards, hypers):
         """What sgd_step_, adam_step_ and adam_master_step_ share: the checks

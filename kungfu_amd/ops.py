@@ -629,6 +629,219 @@ def lion_apply_signs_batch_(params, codes, hypers, sr=None, stream=None):
     return params
 
 
+# -- Muon (include/kungfu_amd.h "Muon") -------------------------
+
+MUON_COEFFS = (3.4445, -4.7750, 2.0315)  # the quintic's (a, b, c)
+
+
+def muon_tile():
+    """The grouped GEMM kernel's block tile, both ways (kf_muon_tile; no device
+    needed)."""
+    return int(_lib.load().kf_muon_tile())
+
+
+def _muon_flat(name, tables, dtypes):
+    """The checks of the element-wise Muon wrappers: one tensor per table and
+    segment, table i of dtypes[i], equal lengths across a segment."""
+    nb = len(tables[0])
+    if any(len(t) != nb for t in tables):
+        raise ValueError("%s: one tensor of every table per segment" % name)
+    for t, dt in zip(tables, dtypes):
+        _check_dev(t)
+        if any(x.dtype != dt or x.numel() != y.numel() for x, y in zip(t, tables[0])):
+            raise ValueError("%s: shape/dtype mismatch" % name)
+    return nb, (ctypes.c_size_t * max(1, nb))(*[t.numel() for t in tables[0]])
+
+
+def muon_momentum_batch_(grads, moms, dirs, hypers, np_=0, stream=None):
+    """Muon's momentum on many flat f32 segments in one launch per 32 of them
+    (kf_muon_momentum_batch, kungfu_amd/csrc/kf_muon.hip):
+
+      g = grads[b] / np_ (np_ > 0) ; m = mu * m + g ; d = nesterov ? g + mu * m : m
+
+    moms in place (f32), d rounded once into the bf16 dirs[b]. hypers[b] is a
+    dict with momentum and optionally nesterov. Lengths are multiples of 8;
+    every tensor starts 16-byte aligned. grads are only read."""
+    grads, moms, dirs, hypers = list(grads), list(moms), list(dirs), list(hypers)
+    if not grads and not moms and not dirs:
+        return dirs
+    nb, cnt = _muon_flat("muon_momentum_batch_", (grads, moms, dirs),
+                         (torch.float32, torch.float32, torch.bfloat16))
+    if len(hypers) != nb:
+        raise ValueError("muon_momentum_batch_: one hyper per segment")
+    rc = _lib.load().kf_muon_momentum_batch(_ptrs(grads), _ptrs(moms), _ptrs(dirs), cnt, nb,
+                                            int(DataType.F32), int(np_),
+                                            _lib.muon_hyper_array(hypers),
+                                            _stream(stream, grads[0].device))
+    _lib.check(rc, "kf_muon_momentum_batch", source="")
+    return dirs
+
+
+def muon_scale_batch_(dirs, xs, sq, stream=None):
+    """xs[b] = dirs[b] / (sqrt(sq[b]) + 1e-7) (kf_muon_scale_batch): bf16 in and
+    out, sq a float64 device tensor of at least len(dirs) squared norms
+    (SegNorm.run's out over dirs). Nothing synchronises the host."""
+    dirs, xs = list(dirs), list(xs)
+    if not dirs and not xs:
+        return xs
+    nb, cnt = _muon_flat("muon_scale_batch_", (dirs, xs), (torch.bfloat16, torch.bfloat16))
+    _check_dev([sq])
+    if sq.dtype != torch.float64 or sq.numel() < nb:
+        raise ValueError("muon_scale_batch_: sq holds a float64 squared norm per segment")
+    rc = _lib.load().kf_muon_scale_batch(_ptrs(dirs), _ptrs(xs), cnt, sq.data_ptr(), nb,
+                                         _stream(stream, dirs[0].device))
+    _lib.check(rc, "kf_muon_scale_batch", source="")
+    return xs
+
+
+def muon_apply_batch_(params, xs, hypers, stream=None):
+    """p = (1 - lr * weight_decay) * p - lr * scale * x on many flat f32
+    segments with bf16 xs (kf_muon_apply_batch), in place. hypers[b] is a dict
+    with lr and optionally weight_decay and scale (Muon's
+    sqrt(max(1, rows / cols)); 1 by default). Tensors may start at any element."""
+    params, xs, hypers = list(params), list(xs), list(hypers)
+    if not params and not xs:
+        return params
+    nb, cnt = _muon_flat("muon_apply_batch_", (params, xs), (torch.float32, torch.bfloat16))
+    if len(hypers) != nb:
+        raise ValueError("muon_apply_batch_: one hyper per segment")
+    h = (_lib.MuonApply * max(1, nb))()
+    for a, x in zip(h, hypers):
+        a.lr, a.weight_decay = float(x["lr"]), float(x.get("weight_decay", 0.0))
+        a.scale = float(x.get("scale", 1.0))
+    rc = _lib.load().kf_muon_apply_batch(_ptrs(params), _ptrs(xs), cnt, h, nb, int(DataType.F32),
+                                         _stream(stream, params[0].device))
+    _lib.check(rc, "kf_muon_apply_batch", source="")
+    return params
+
+
+def _muon_table(name, problems):
+    """(kf_muon_gemm[], the tensors kept alive) of problems (a, b, c[, cin[,
+    trans_a[, trans_b]]]): 2-D bf16 device tensors whose rows are contiguous
+    (stride(1) == 1; stride(0) is the leading dimension)."""
+    tab, keep = (_lib.MuonGemm * max(1, len(problems)))(), []
+    for q, prob in zip(tab, problems):
+        a, b, c, cin, ta, tb = (tuple(prob) + (None, False, False))[:6]
+        ts = [t for t in (a, b, c, cin) if t is not None]
+        for t in ts:
+            if not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 2 or \
+                    (t.shape[1] > 1 and t.stride(1) != 1):
+                raise ValueError("%s: 2-D bf16 GPU tensors with contiguous rows" % name)
+        (m, k), (k2, n) = (a.shape[::-1] if ta else a.shape), (b.shape[::-1] if tb else b.shape)
+        if k != k2 or tuple(c.shape) != (m, n) or (cin is not None and tuple(cin.shape) != (m, n)):
+            raise ValueError("%s: op(a) is m x k, op(b) k x n, c and cin m x n" % name)
+        ld = lambda t: max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1])  # noqa: E731
+        q.a, q.b, q.c = a.data_ptr(), b.data_ptr(), c.data_ptr()
+        q.cin = cin.data_ptr() if cin is not None else None
+        q.m, q.n, q.k, q.lda, q.ldb, q.ldc = m, n, k, ld(a), ld(b), ld(c)
+        q.ldcin = ld(cin) if cin is not None else 0
+        q.trans_a, q.trans_b = int(bool(ta)), int(bool(tb))
+        keep.append(ts)
+    return tab, keep
+
+
+def _muon_gemm(tab, count, alpha, beta, stream):
+    rc = _lib.load().kf_muon_gemm_grouped(tab, count, int(DataType.BF16), float(alpha), float(beta),
+                                          stream)
+    _lib.check(rc, "kf_muon_gemm_grouped", source="")
+
+
+def muon_gemm_grouped_(problems, alpha=1.0, beta=1.0, stream=None):
+    """c = alpha * cin + beta * op(a) @ op(b) for every problem, in one launch
+    per 32 problems of the MFMA kernel (kf_muon_gemm_grouped): bf16 matrices,
+    f32 accumulation, one rounding. A problem is (a, b, c[, cin[, trans_a[,
+    trans_b]]]); op(x) is x.T where its flag is set; any m, n, k >= 1; rows may
+    be strided. c must not overlap a or b (cin may be c). The same bits on
+    every run. Returns the cs."""
+    problems = list(problems)
+    if not problems:
+        return []
+    tab, keep = _muon_table("muon_gemm_grouped_", problems)
+    _muon_gemm(tab, len(problems), alpha, beta, _stream(stream, problems[0][2].device))
+    return [p[2] for p in problems]
+
+
+class MuonPlan:
+    """Newton-Schulz over a fixed list of tensors: dirs[t] is a flat bf16
+    device tensor of rows * cols elements (a tensor's view in a direction
+    bucket: any element offset) and shapes[t] its (rows, cols). Made once: the
+    workspace (two copies of every tensor and two s x s matrices each, s =
+    min(rows, cols): 2 * sum(rows * cols) + 2 * sum(s * s) bf16, each piece
+    16-byte aligned), the norms' SegNorm plan and the GEMM tables are kept, so
+    run() allocates nothing, does not synchronise the host and can be captured
+    into a graph.
+
+    run(steps) -> the orthogonalised tensors, as rows x cols views of the
+    workspace that the next run overwrites: 2 launches for the norms, the
+    scale, and per step 3 grouped GEMM launches per 32 tensors (X X^T; b A + c
+    A A; a X + B X; for rows > cols X^T X and a X + X B)."""
+
+    def __init__(self, dirs, shapes):
+        dirs, shapes = list(dirs), [tuple(int(x) for x in s) for s in shapes]
+        if not dirs or len(dirs) != len(shapes):
+            raise ValueError("MuonPlan: at least one tensor, and a (rows, cols) for each")
+        _check_dev(dirs)
+        for d, (r, c) in zip(dirs, shapes):
+            if d.dtype != torch.bfloat16 or d.dim() != 1 or r < 1 or c < 1 or d.numel() != r * c:
+                raise ValueError("MuonPlan: flat bf16 tensors of rows * cols >= 1 elements")
+        up = lambda n: (n + 7) // 8 * 8  # noqa: E731
+        need = sum(2 * up(r * c) + 2 * up(min(r, c) ** 2) for r, c in shapes)
+        self.device, self.dirs, self.shapes = dirs[0].device, dirs, shapes
+        self.workspace = torch.zeros(need, dtype=torch.bfloat16, device=self.device)
+        self.norms = SegNorm(dirs)
+        self.sq = torch.zeros(len(dirs) + 1, dtype=torch.float64, device=self.device)
+        off, self.x, gram, quint, xmul = 0, ([], []), ([], []), [], ([], [])
+
+        def take(n):
+            nonlocal off
+            off += up(n)
+            return self.workspace[off - up(n):off - up(n) + n]
+
+        for r, c in shapes:
+            s, tall = min(r, c), r > c
+            x = [take(r * c).view(r, c) for _ in range(2)]
+            a, b = (take(s * s).view(s, s) for _ in range(2))
+            quint.append((a, a, b, a))
+            for p in range(2):
+                self.x[p].append(x[p])
+                # rows > cols: the short side's Gram matrix, with no transposed copy
+                gram[p].append((x[p], x[p], a, None, tall, not tall))
+                xmul[p].append((x[p], b, x[1 - p], x[p]) if tall else (b, x[p], x[1 - p], x[p]))
+        self._tables = [[_muon_table("MuonPlan", t) for t in (gram[p], quint, xmul[p])]
+                        for p in range(2)]
+
+    def run(self, steps=5, stream=None):
+        if isinstance(steps, bool) or not isinstance(steps, int) or not 1 <= steps <= 16:
+            raise ValueError("MuonPlan.run: steps must be an int in [1, 16], not %r" % (steps,))
+        n, a, b, c = len(self.dirs), *MUON_COEFFS
+        self.norms.run("sq", out=self.sq, stream=stream)
+        muon_scale_batch_(self.dirs, [x.view(-1) for x in self.x[0]], self.sq, stream=stream)
+        s = _stream(stream, self.device)
+        for i in range(steps):
+            gram, quint, xmul = self._tables[i & 1]
+            _muon_gemm(gram[0], n, 0.0, 1.0, s)
+            _muon_gemm(quint[0], n, b, c, s)
+            _muon_gemm(xmul[0], n, a, 1.0, s)
+        return self.x[steps & 1]
+
+
+def muon_newton_schulz_(tensors2d, steps=5, stream=None):
+    """Every tensor (bf16, contiguous, viewed as shape[0] x the rest) replaced
+    by its Newton-Schulz orthogonalisation, `steps` iterations of the quintic
+    on t / (|t|_F + 1e-7): the whole chain of a MuonPlan made for this call.
+    An optimizer keeps its plan instead (MuonPlan)."""
+    ts = list(tensors2d)
+    if not ts:
+        return ts
+    for t in ts:
+        if t.dim() < 2 or not t.is_contiguous():
+            raise ValueError("muon_newton_schulz_: contiguous tensors of 2 or more dimensions")
+    plan = MuonPlan([t.view(-1) for t in ts], [(t.shape[0], t.numel() // t.shape[0]) for t in ts])
+    for t, x in zip(ts, plan.run(steps, stream)):
+        t.view(x.shape).copy_(x)
+    return ts
+
+
 # -- Adam, 8-bit block-wise state (include/kungfu_amd.h, DESIGN.md §20) --------
 
 ADAM8_ZERO_CODE = (127, 0)       # the code of 0.0: signed (exp_avg), unsigned (exp_avg_sq)

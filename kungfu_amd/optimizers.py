@@ -36,6 +36,9 @@ Operator surface kept from the reference:
 * ``ShardedLionOptimizer(optimizer, named_parameters=None, ...)`` — Lion on
   the shard: one state tensor, a sign update, and with ``sign_wire=True`` a
   phase 3 of 2-bit codes that every rank applies to its replica.
+* ``ShardedMuonOptimizer(optimizer, named_parameters=None, ...)`` — Muon:
+  sharded f32 momentum, a gather of bf16 directions, and a Newton-Schulz
+  orthogonalised update of every weight matrix on every rank.
 
 Buckets: parameters are grouped (in registration order, per dtype/device) into
 flat padded device buckets (``collective.GradBuckets``); ``p.grad`` (S-SGD) or
@@ -1765,6 +1768,142 @@ def ShardedLionOptimizer(optimizer, named_parameters=None, exchange=None, bucket
                 raise ValueError("%s needs an exchange with %s() (collective.Exchange or "
                                  "exchange.NativeExchange)" % (name, method))
     opt._kf_sign_wire, opt._kf_sr_seed = sign_wire, sr_seed
+    return opt
+
+
+class _ShardedMuon(_ShardedSGD):
+    """reduce-scatter(grads) -> momentum on the own shard, its bf16 direction
+    into a direction bucket -> all-gather(direction buckets) -> on every rank
+    Newton-Schulz on every tensor and the update of the whole replica
+    (DESIGN.md §28). The momentum is one f32 shard per bucket, zeros from the
+    start: _ShardedSGD's, with its checkpoint path."""
+
+    _kf_name = "ShardedMuonOptimizer"
+    _kf_dtypes = ("float32",)
+    _kf_dtype_words = "f32"
+    _kf_ns_steps = 5
+
+    def _kf_new_group(self):
+        return {"moms": None, "first": True, "db": None, "plan": None, "at": None, "scale": None}
+
+    def _kf_build_muon(self, G):
+        """The group's direction buckets (bf16 twins of the parameter buckets)
+        and its Newton-Schulz plan over every tensor's view in them."""
+        import torch
+        from . import ops
+        pb = G["pb"].buckets
+        G["db"] = [torch.zeros(b.numel(), dtype=torch.bfloat16, device=b.device) for b in pb]
+        dirs, shapes, G["at"], G["scale"] = [], [], [], []
+        for p, v in zip(G["ps"], G["pb"].views):
+            if not p.numel():
+                continue
+            j = next(j for j, b in enumerate(pb)
+                     if b.data_ptr() <= v.data_ptr() < b.data_ptr() + b.numel() * b.element_size())
+            off = (v.data_ptr() - pb[j].data_ptr()) // v.element_size()
+            rows, cols = p.shape[0], p.numel() // p.shape[0]
+            dirs.append(G["db"][j][off:off + p.numel()])
+            shapes.append((rows, cols))
+            G["at"].append(v)
+            G["scale"].append(max(1.0, rows / cols) ** 0.5)
+        G["plan"] = ops.MuonPlan(dirs, shapes) if dirs else None
+
+    def step(self, closure=None):
+        from . import ops
+        loss = self._kf_closure(closure)
+        if self._kf_groups is None:
+            self._kf_build_sharded()
+        ex = self._kf_ex
+        for G in self._kf_groups:
+            _SyncSGD._kf_place(G["ps"], G["gb"])
+        for j, G in enumerate(self._kf_groups):
+            pg = self.param_groups[G["gi"]]  # read at every step: schedulers change them
+            lr, wd = float(pg["lr"]), float(pg["weight_decay"])
+            h = {"momentum": float(pg["momentum"]), "nesterov": bool(pg["nesterov"])}
+            if G["db"] is None:
+                self._kf_build_muon(G)
+            gb, db, nb = G["gb"].buckets, G["db"], len(G["db"])
+            moms = self._kf_moms(G)
+            if hasattr(ex, "muon_step_"):
+                ex.muon_step_(db, gb, moms, [h] * nb)
+            else:  # the exchange's phases around the HIP momentum
+                q = [d.numel() // ex.world for d in db]
+                np_ = ex.reduce_shards_(gb, ("muon", j))
+                ops.muon_momentum_batch_(ex.grad_shards_(gb, ("muon", j)), moms,
+                                         [d[ex.rank * n:(ex.rank + 1) * n] for d, n in zip(db, q)],
+                                         [h] * nb, np_)
+                ex.gather_params_(db)
+            if G["plan"] is not None:  # replicated: every rank, every tensor
+                xs = G["plan"].run(self._kf_ns_steps)
+                ops.muon_apply_batch_(G["at"], [x.view(-1) for x in xs],
+                                      [{"lr": lr, "weight_decay": wd, "scale": s} for s in G["scale"]])
+            G["first"] = False
+        _finish(ex)
+        return loss
+
+
+def ShardedMuonOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20,
+                         ns_steps=5):
+    """Muon (Jordan et al. 2024: momentum, then an update orthogonalised by a
+    quintic Newton-Schulz iteration) on the sharded step.
+    Every step is
+
+      reduce-scatter(grads)
+        -> [own shard: g / np, m = mu * m + g, d = nesterov ? g + mu * m : m;
+            m f32 and sharded, d bf16 into a direction bucket]
+        -> all-gather(direction buckets): half the bytes of the parameters'
+        -> [every rank, every tensor as shape[0] x the rest:
+            X = d / (|d| + 1e-7); ns_steps times A = X X^T, B = b A + c A A,
+            X = a X + B X; p = p (1 - lr * weight_decay)
+                               - lr * sqrt(max(1, rows / cols)) * X]
+
+    The parameters never travel: every replica applies the same deterministic
+    kernels to the same gathered bits and stays bit-identical. The
+    Newton-Schulz work (bf16 products on the matrix units, one grouped launch
+    per product for all tensors of a bucket group: ops.MuonPlan) is therefore
+    REPLICATED on every rank; partitioning it needs a second exchange and is
+    not offered.
+
+    `optimizer` must be a torch.optim.SGD (TypeError otherwise), which lends
+    lr, momentum, nesterov and weight_decay (decoupled here), read at every
+    step. Every parameter has 2 or more dimensions (ValueError otherwise):
+    give biases, norms and embeddings to a ShardedAdamOptimizer built over
+    their own named_parameters, the usual Muon practice. f32 parameters
+    (TypeError on the first step otherwise). With an exchange that has no
+    muon_step_ the step runs as reduce_shards_ / grad_shards_ / gather_params_
+    around the same kernels.
+
+    momentum_buffers() / load_momentum_buffers() are ShardedSGDOptimizer's
+    checkpoint path. Not offered: bf16 / f16 parameters, master weights, a
+    gate, overlap=True, the pipelined schedule, partitioned Newton-Schulz,
+    dampening, maximize."""
+    import torch
+    name = "ShardedMuonOptimizer"
+    if not isinstance(optimizer, torch.optim.SGD):
+        raise TypeError("%s wraps a torch.optim.SGD, not %s" % (name, type(optimizer).__name__))
+    for g in optimizer.param_groups:
+        if g.get("dampening", 0) != 0:
+            raise ValueError("%s: dampening must be 0 (Muon's momentum has none), not %r"
+                             % (name, g["dampening"]))
+        for option in ("maximize", "differentiable"):
+            if g.get(option, False):
+                raise ValueError("%s: %s=True is not supported" % (name, option))
+    if isinstance(ns_steps, bool) or not isinstance(ns_steps, int) or not 1 <= ns_steps <= 16:
+        raise ValueError("%s: ns_steps must be an int in [1, 16], not %r" % (name, ns_steps))
+    opt = _wrap(optimizer, _ShardedMuon)
+    opt._kf_setup(named_parameters, exchange, bucket_bytes)
+    for p in opt._kf_params:
+        if p.dim() < 2:
+            raise ValueError("%s orthogonalises weight matrices: a parameter of shape %s has fewer "
+                             "than 2 dimensions. Give such parameters (biases, norms) to a "
+                             "ShardedAdamOptimizer built over their own named_parameters."
+                             % (name, tuple(p.shape)))
+    ex = opt._kf_ex
+    if not hasattr(ex, "muon_step_"):
+        for method in ("reduce_shards_", "grad_shards_", "gather_params_"):
+            if not hasattr(ex, method):
+                raise ValueError("%s needs an exchange with %s() (collective.Exchange or "
+                                 "exchange.NativeExchange)" % (name, method))
+    opt._kf_ns_steps = ns_steps
     return opt
 
 

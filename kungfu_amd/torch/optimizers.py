@@ -28,7 +28,8 @@ torch.optim.Adam / AdamW and their two state tensors) and
 ``ShardedLAMBOptimizer`` (LAMB's layer-wise trust ratios on the same shards)
 and ``ShardedLARSOptimizer`` (LARS's layer-wise rates on the sharded SGD step)
 and ``ShardedLionOptimizer`` (Lion's sign update, optionally with phase 3 as
-2-bit codes).
+2-bit codes) and ``ShardedMuonOptimizer`` (Muon: sharded momentum, a bf16
+direction gather and a Newton-Schulz orthogonalised update on every rank).
 """
 from .. import optimizers as _opt
 from ..optimizers import SynchronousAveragingOptimizer
@@ -36,7 +37,8 @@ from ..optimizers import SynchronousAveragingOptimizer
 __all__ = ["SynchronousSGDOptimizer", "SynchronousAveragingOptimizer",
            "MonitorGradientNoiseScaleOptimizer", "MonitorGradientVarianceOptimizer",
            "PairAveragingOptimizer", "ShardedSGDOptimizer", "ShardedAdamOptimizer",
-           "ShardedLAMBOptimizer", "ShardedLARSOptimizer", "ShardedLionOptimizer"]
+           "ShardedLAMBOptimizer", "ShardedLARSOptimizer", "ShardedLionOptimizer",
+           "ShardedMuonOptimizer"]
 
 
 def SynchronousSGDOptimizer(optimizer, named_parameters, op=None, **kwargs):
@@ -105,3 +107,10 @@ def ShardedLionOptimizer(optimizer, named_parameters, **kwargs):
     positional. Keywords pass through: `exchange`, `bucket_bytes`, `sign_wire`
     and `sr_seed`."""
     return _opt.ShardedLionOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
+
+
+def ShardedMuonOptimizer(optimizer, named_parameters, **kwargs):
+    """kungfu_amd.optimizers.ShardedMuonOptimizer with `named_parameters`
+    positional. Keywords pass through: `exchange`, `bucket_bytes` and
+    `ns_steps`."""
+    return _opt.ShardedMuonOptimizer(optimizer, named_parameters=named_parameters, **kwargs)
