@@ -984,6 +984,22 @@ int kf_lion_apply_signs_batch(void *const *params, const void *const *codes, con
  * on every run and rank). kf_muon_tile() is the kernel's block tile (both
  * ways), for tests; it needs no device.
  *
+ * kf_muon_syrk_grouped: the grouped symmetric rank-k product, for the two
+ * products of an iteration whose result is symmetric (X X^T, and b*A + c*A*A
+ * with A symmetric). Per problem, with S = op(A) m x k (A stored m x k, or
+ * k x m with trans_a = 1),
+ *   row >= col:  C[row][col] = bf16((alpha*Cin[row][col]) + (beta*acc)),
+ *                acc the f32 sum of the exact products S[row][.] S[col][.] in
+ *                the general kernel's K order: the bits of
+ *                kf_muon_gemm_grouped's product of op(A) and op(A)^T
+ *   row <  col:  C[row][col] = C[col][row], the same bits, copied
+ * so C is symmetric bit for bit and Cin is never read above the diagonal.
+ * Only the lower triangle of the grid of 64 x 64 tiles is computed. It reads
+ * a, lda, trans_a, m, k, cin, ldcin, c and ldc of a kf_muon_gemm; b must be
+ * NULL and n equal to m. cin may be NULL (alpha is then not read) and may be
+ * c; c must not overlap a. Every m, k >= 1 and every element offset is taken.
+ * The block tile is kf_muon_tile().
+ *
  * Checks, all before any HIP call, in this order. The batch entries: nb < 0;
  * (nb == 0 is KF_OK); dt (KF_ERR_DTYPE); a null table; per non-empty segment
  * a null pointer, then a misaligned one; and for the momentum np < 0, then a
@@ -991,7 +1007,11 @@ int kf_lion_apply_signs_batch(void *const *params, const void *const *codes, con
  * then per problem a dimension below 1, k above INT_MAX - 32, a null a, b or
  * c, a pointer off a 2-byte boundary, trans_a or trans_b not 0 or 1, a
  * leading dimension smaller than the stored row, more than 2^22 block tiles
- * in one problem.
+ * in one problem. The symmetric product: count < 0; (0 is KF_OK); dt; a null
+ * table; then per problem m or k below 1, k above INT_MAX - 32, n != m or a b
+ * that is not NULL, a null a or c, a pointer off a 2-byte boundary, trans_a
+ * not 0 or 1, a leading dimension smaller than the stored row, more than 2^22
+ * launched tiles (the lower triangle's) in one problem.
  * All KF_ERR_ARG but the dtype. */
 typedef struct { double momentum; int nesterov; } kf_muon_hyper;
 typedef struct { double lr, weight_decay, scale; } kf_muon_apply;
@@ -1007,6 +1027,8 @@ int kf_muon_momentum_batch(const void *const *grads, void *const *moms, void *co
 int kf_muon_scale_batch(const void *const *dirs, void *const *xs, const size_t *counts,
                         const double *sq, int nb, void *stream);
 int kf_muon_gemm_grouped(const kf_muon_gemm *problems, int count, KungFu_Datatype dt, float alpha,
+                         float beta, void *stream);
+int kf_muon_syrk_grouped(const kf_muon_gemm *problems, int count, KungFu_Datatype dt, float alpha,
                          float beta, void *stream);
 int kf_muon_apply_batch(void *const *params, const void *const *xs, const size_t *counts,
                         const kf_muon_apply *hyper, int nb, KungFu_Datatype dt, void *stream);

@@ -176,6 +176,7 @@ EXPORTED = (
     "kf_muon_momentum_batch",
     "kf_muon_scale_batch",
     "kf_muon_gemm_grouped",
+    "kf_muon_syrk_grouped",
     "kf_muon_apply_batch",
     "kf_exchange_muon_batch",
 )
@@ -796,6 +797,8 @@ def load():
     lib.kf_muon_gemm_grouped.argtypes = [P(MuonGemm), c_int, c_int, ctypes.c_float, ctypes.c_float,
                                          c_void_p]
     lib.kf_muon_gemm_grouped.restype = c_int
+    lib.kf_muon_syrk_grouped.argtypes = lib.kf_muon_gemm_grouped.argtypes
+    lib.kf_muon_syrk_grouped.restype = c_int
     lib.kf_muon_apply_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_size_t), P(MuonApply), c_int,
                                         c_int, c_void_p]
     lib.kf_muon_apply_batch.restype = c_int

@@ -41,9 +41,36 @@
 //   * No atomics, no split-K, no inline asm: every C element is one lane's sum
 //     in a fixed order, so the result is a pure function of the inputs.
 //
-// Not done: a larger block tile for large matrices, the
-// epilogue's stores through LDS as 16-byte rows, X X^T's two operands from
-// one LDS tile, and skipping the symmetric half of A.
+// muon_syrk_kernel:  C_i = alpha*Cin_i + beta*S_i*S_i^T with S = op(A_i), the
+// two products of an iteration whose result is symmetric (A = X X^T, and
+// B = b*A + c*A*A = b*A + c*A*A^T), opt-in (kf_muon_syrk_grouped).
+//
+//   * Work split. Only the tiles (ti, tj), tj <= ti, of the T x T grid of
+//     64 x 64 tiles are launched: T(T+1)/2 blocks a problem, the prefix table
+//     counts those, and a block turns its linear index into (ti, tj) with a
+//     float square root and an integer correction (muon_tri).
+//   * Operands. Both MFMA operands are row panels of S, rows 64*ti.. as the
+//     first and rows 64*tj.. as the second, in the general kernel's K-major
+//     LDS layout and K order: for row >= col the accumulator is the general
+//     kernel's NT (TN) accumulator bit for bit. A diagonal tile stages ONE
+//     panel a K step and reads both fragments from it. (Its quadrant above
+//     the diagonal is computed and dropped: a wave-uniform branch round the
+//     MFMAs costs 16 VGPRs of accumulator copies and two waves per SIMD.)
+//     With A stored m x k there is no 2-byte LDS store at all; stored k x m,
+//     both panels are transposed on their way in as the general kernel does it.
+//   * Epilogue through LDS. After the K walk's last barrier the operand
+//     buffers are free: every lane narrows its 16 elements (Cin read only
+//     where row >= col) into a 64 x 64 bf16 tile whose rows are 33 dwords
+//     apart, so the 8 lanes that gather one transposed row read LDS rows 8
+//     apart, which start 8 banks apart. An off-diagonal tile leaves LDS twice, row-wise to (ti, tj) and
+//     column-wise to (tj, ti); a diagonal one once, out[r][c] =
+//     lds[max(r, c)][min(r, c)]. The upper half of C is therefore a copy of
+//     the lower one's bits, never a second computation. Stores are 16-byte
+//     chunks where the chunk lies inside C and c and ldc are multiples of 16
+//     bytes, masked 2-byte stores otherwise, chosen per chunk.
+//
+// Not done: a larger block tile for large matrices, and the
+// general kernel's epilogue through LDS.
 //
 // The element-wise kernels. muon_momentum_kernel is kf_sgd.hip's shape on the
 // shard (16-byte vectors, 8 elements per lane: f32 g and m in, f32 m and bf16
@@ -78,7 +105,9 @@ struct MuonGemmSeg {
     uint16_t *c;
     int m, n, k;
     int lda, ldb, ldcin, ldc;
-    int flags;  // bit 0: A stored K x M, bit 1: B stored N x K, bits 2, 3: a, b take 16-byte loads
+    // bit 0: A stored K x M, bit 1: B stored N x K, bits 2, 3: a, b take 16-byte loads,
+    // bit 4 (muon_syrk_kernel, which reads no b and no n): c takes 16-byte stores
+    int flags;
 };
 struct MuonGemmArgs {
     MuonGemmSeg seg[kMuonSeg];
@@ -197,6 +226,135 @@ __global__ void __launch_bounds__(kMuonBlock)
     }
 }
 
+// ---- the symmetric product -------------------------------------------------------
+constexpr int kMuonLdC = kMuonTile + 2;  // the epilogue tile's LDS row in elements: 33 dwords
+
+// Elements (r, c .. c + 7) of v into a row-major M x M matrix, nothing outside it.
+__device__ __forceinline__ void muon_st8(uint16_t *p, int ld, int r, int c, int M, bool vec,
+                                         const u32x4 &v)
+{
+    if (r >= M || c >= M) return;
+    uint16_t *q = p + static_cast<size_t>(r) * ld + c;
+    if (vec && c + 8 <= M) {
+        *reinterpret_cast<u32x4 *>(q) = v;
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if (c + i < M) q[i] = static_cast<uint16_t>(v[i / 2] >> (16 * (i & 1)));
+    }
+}
+
+// Tile t of a lower triangle counted row by row -> (ti, tj), tj <= ti:
+// ti = the largest i with i (i + 1) / 2 <= t. The float estimate can be off
+// by one from 8 t + 1 >= 2^24 on; the integer steps make it exact for every t
+// (the host admits t < 2^22, so ti < 2896 and nothing here overflows).
+__device__ __forceinline__ void muon_tri(unsigned t, int &ti, int &tj)
+{
+    unsigned i = static_cast<unsigned>((sqrtf(8.0f * static_cast<float>(t) + 1.0f) - 1.0f) * 0.5f);
+    while (i * (i + 1) / 2 > t) --i;
+    while ((i + 1) * (i + 2) / 2 <= t) ++i;
+    ti = static_cast<int>(i);
+    tj = static_cast<int>(t - i * (i + 1) / 2);
+}
+
+__global__ void __launch_bounds__(kMuonBlock)
+    muon_syrk_kernel(MuonGemmArgs args, float alpha, float beta)
+{
+    static_assert(kMuonTile == 64 && kMuonBlock == 256, "four waves, 2 x 2 quadrants of 32 x 32");
+    static_assert(kMuonTile * kMuonLdC <= 4 * kMuonTile * kMuonLd, "the epilogue tile fits");
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2][2][kMuonTile * kMuonLd];
+    size_t blk, nblk;
+    const MuonGemmSeg &h = args.seg[batch_segment(args, blk, nblk)];
+    const int M = h.m, K = h.k;
+    const unsigned tm = (M + kMuonTile - 1) / kMuonTile;
+    const unsigned t  = static_cast<unsigned>(blk);
+    if (t >= tm * (tm + 1) / 2) return;  // a row's blocks past the problem's last tile
+    int ti, tj;
+    muon_tri(t, ti, tj);
+    const bool diag = ti == tj;
+    const bool kmajor = !(h.flags & 1), avec = (h.flags & 4) != 0, cvec = (h.flags & 16) != 0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = 32 * (wave >> 1), wn = 32 * (wave & 1);
+    const int m0 = ti * kMuonTile, n0 = tj * kMuonTile;
+    const int frag = (lane & 31) * kMuonLd + 8 * (lane >> 5);
+    const int nk = (K + kMuonBK - 1) / kMuonBK;
+    const int second = diag ? 0 : 1;  // the LDS panel of the second operand
+    f32x16 acc;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
+
+    u32x4 ra = muon_fetch(h.a, h.lda, kmajor, avec, m0, M, 0, K);
+    u32x4 rb = {0u, 0u, 0u, 0u};
+    if (!diag) rb = muon_fetch(h.a, h.lda, kmajor, avec, n0, M, 0, K);
+    muon_stage(lds[0][0], kmajor, ra);
+    if (!diag) muon_stage(lds[0][1], kmajor, rb);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        const int cur = kt & 1;
+        if (kt + 1 < nk) {
+            ra = muon_fetch(h.a, h.lda, kmajor, avec, m0, M, (kt + 1) * kMuonBK, K);
+            if (!diag) rb = muon_fetch(h.a, h.lda, kmajor, avec, n0, M, (kt + 1) * kMuonBK, K);
+        }
+#pragma unroll
+        for (int kk = 0; kk < kMuonBK; kk += 16) {
+            const u32x4 fa = *reinterpret_cast<const u32x4 *>(&lds[cur][0][wm * kMuonLd + frag + kk]);
+            const u32x4 fb =
+                *reinterpret_cast<const u32x4 *>(&lds[cur][second][wn * kMuonLd + frag + kk]);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa),
+                                                          __builtin_bit_cast(bf16x8, fb), acc, 0, 0, 0);
+        }
+        if (kt + 1 < nk) {
+            muon_stage(lds[cur ^ 1][0], kmajor, ra);
+            if (!diag) muon_stage(lds[cur ^ 1][1], kmajor, rb);
+        }
+        __syncthreads();
+    }
+
+    // The tile, narrowed, into LDS: the operand buffers are free behind the
+    // K walk's last barrier. Rows past M hold zeros that nothing stores, and
+    // what a diagonal tile holds above its diagonal is never read.
+    uint16_t *e = &lds[0][0][0];
+    const int lc = wn + (lane & 31), col = n0 + lc;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int lr = wm + 8 * (j / 4) + 4 * (lane >> 5) + (j % 4), row = m0 + lr;
+        float v = __fmul_rn(beta, acc[j]);
+        if (h.cin && row < M && col <= row) {
+            const float x = bf16_to_f32(h.cin[static_cast<size_t>(row) * h.ldcin + col]);
+            v             = __fadd_rn(__fmul_rn(alpha, x), v);
+        }
+        e[lr * kMuonLdC + lc] = f32_to_bf16(v);
+    }
+    __syncthreads();
+    // 512 chunks of 8 elements, two per lane: chunk q is row q / 8 of what is
+    // stored, columns 8 * (q % 8) .. + 7, so 8 lanes fill a row's 128 bytes.
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int q = threadIdx.x + u * kMuonBlock, r = q >> 3, c0 = 8 * (q & 7);
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (diag) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int c = c0 + i, hi = r > c ? r : c, lo = r > c ? c : r;
+                v[i / 2] |= static_cast<uint32_t>(e[hi * kMuonLdC + lo]) << (16 * (i & 1));
+            }
+            muon_st8(h.c, h.ldc, m0 + r, m0 + c0, M, cvec, v);
+        } else {
+            const uint32_t *w = reinterpret_cast<const uint32_t *>(e + r * kMuonLdC + c0);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = w[i];
+            muon_st8(h.c, h.ldc, m0 + r, n0 + c0, M, cvec, v);
+            u32x4 x = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                x[i / 2] |= static_cast<uint32_t>(e[(c0 + i) * kMuonLdC + r]) << (16 * (i & 1));
+            }
+            muon_st8(h.c, h.ldc, n0 + r, m0 + c0, M, cvec, x);
+        }
+    }
+}
+
 // ---- momentum on the shard -----------------------------------------------------
 //   g = np > 0 ? sum / np : sum ;  m = (mu*m) + g ;  d = nesterov ? g + (mu*m) : m
 struct MuonMomSeg {
@@ -296,6 +454,7 @@ using namespace kf;
 constexpr UpdateFail fail_mom{"kf_muon_momentum_batch"};
 constexpr UpdateFail fail_scale{"kf_muon_scale_batch"};
 constexpr UpdateFail fail_gemm{"kf_muon_gemm_grouped"};
+constexpr UpdateFail fail_syrk{"kf_muon_syrk_grouped"};
 constexpr UpdateFail fail_apply{"kf_muon_apply_batch"};
 
 bool off(const void *p, uintptr_t align) { return (reinterpret_cast<uintptr_t>(p) % align) != 0; }
@@ -452,6 +611,59 @@ int kf_muon_gemm_grouped(const kf_muon_gemm *problems, int count, KungFu_Datatyp
         [&](unsigned gx, unsigned gy, const MuonGemmArgs &a) {
             muon_gemm_kernel<<<dim3(gx, gy), kMuonBlock, 0, s>>>(a, alpha, beta);
             return launch_status(fail_gemm);
+        });
+}
+
+int kf_muon_syrk_grouped(const kf_muon_gemm *problems, int count, KungFu_Datatype dt, float alpha,
+                         float beta, void *stream)
+{
+    if (count < 0) return fail_syrk(KF_ERR_ARG, "KF_ERR_ARG", "count < 0");
+    if (count == 0) return KF_OK;
+    if (dt != KungFu_BFLOAT16) return fail_syrk(KF_ERR_DTYPE, "KF_ERR_DTYPE", "bf16 matrices only");
+    if (!problems) return fail_syrk(KF_ERR_ARG, "KF_ERR_ARG", "null table");
+    std::vector<size_t> tiles(count);
+    for (int i = 0; i < count; ++i) {
+        const kf_muon_gemm &q = problems[i];
+        if (q.m < 1 || q.k < 1) {
+            return fail_syrk(KF_ERR_ARG, "KF_ERR_ARG", "a zero or negative dimension");
+        }
+        if (q.k > INT_MAX - kMuonBK) {
+            return fail_syrk(KF_ERR_ARG, "KF_ERR_ARG", "k above INT_MAX - 32");
+        }
+        if (q.n != q.m || q.b) {
+            return fail_syrk(KF_ERR_ARG, "KF_ERR_ARG",
+                             "a symmetric product has n == m and no b (both operands are a)");
+        }
+        if (!q.a || !q.c) return fail_syrk(KF_ERR_ARG, "KF_ERR_ARG", "null matrix");
+        if (off(q.a, 2) || off(q.c, 2) || off(q.cin, 2)) {
+            return fail_syrk(KF_ERR_ARG, "KF_ERR_ARG", "misaligned pointer");
+        }
+        if (q.trans_a < 0 || q.trans_a > 1) {
+            return fail_syrk(KF_ERR_ARG, "KF_ERR_ARG", "trans_a is 0 or 1");
+        }
+        if (q.lda < (q.trans_a ? q.m : q.k) || q.ldc < q.m || (q.cin && q.ldcin < q.m)) {
+            return fail_syrk(KF_ERR_ARG, "KF_ERR_ARG", "a leading dimension smaller than the row");
+        }
+        const size_t tm = static_cast<size_t>((q.m + kMuonTile - 1) / kMuonTile);
+        tiles[i]        = tm * (tm + 1) / 2;  // the lower triangle of the tile grid
+        if (tiles[i] > 0x400000u) {
+            return fail_syrk(KF_ERR_ARG, "KF_ERR_ARG", "more than 2^22 tiles in one problem");
+        }
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return plan_update_batch<MuonGemmArgs>(
+        tiles.data(), count, 1, 1,
+        [&](MuonGemmSeg &g, int i) {
+            const kf_muon_gemm &q = problems[i];
+            const int avec = !off(q.a, 16) && q.lda % 8 == 0, cvec = !off(q.c, 16) && q.ldc % 8 == 0;
+            g = MuonGemmSeg{static_cast<const uint16_t *>(q.a), nullptr,
+                            static_cast<const uint16_t *>(q.cin), static_cast<uint16_t *>(q.c),
+                            q.m, q.m, q.k, q.lda, 0, q.cin ? q.ldcin : 0, q.ldc,
+                            (q.trans_a ? 1 : 0) | (avec ? 4 : 0) | (cvec ? 16 : 0)};
+        },
+        [&](unsigned gx, unsigned gy, const MuonGemmArgs &a) {
+            muon_syrk_kernel<<<dim3(gx, gy), kMuonBlock, 0, s>>>(a, alpha, beta);
+            return launch_status(fail_syrk);
         });
 }
 

@@ -761,6 +761,48 @@ def muon_gemm_grouped_(problems, alpha=1.0, beta=1.0, stream=None):
     return [p[2] for p in problems]
 
 
+def _muon_syrk_table(name, problems):
+    """_muon_table for the symmetric product's problems (a, c[, cin[,
+    trans_a]]): checked as the general product of op(a) and op(a).T, then b
+    is NULL and n is m."""
+    general = []
+    for prob in problems:
+        a, c, cin, ta = (tuple(prob) + (None, False))[:4]
+        general.append((a, a, c, cin, ta, not ta))
+    tab, keep = _muon_table(name, general)
+    for q in tab:
+        q.b, q.ldb, q.trans_b = None, 0, 0
+    return tab, keep
+
+
+def _muon_syrk(tab, count, alpha, beta, stream):
+    rc = _lib.load().kf_muon_syrk_grouped(tab, count, int(DataType.BF16), float(alpha), float(beta),
+                                          stream)
+    _lib.check(rc, "kf_muon_syrk_grouped", source="")
+
+
+def muon_syrk_grouped_(problems, alpha=1.0, beta=1.0, stream=None):
+    """c = alpha * cin + beta * op(a) @ op(a).T for every problem, in one launch
+    per 32 problems of the symmetric MFMA kernel (kf_muon_syrk_grouped): only
+    the lower triangle of c's 64 x 64 tiles is computed, with
+    muon_gemm_grouped_'s bits, and mirrored, so c equals c.T bit for bit. A
+    problem is (a, c[, cin[, trans_a]]); op(a) is a.T where the flag is set;
+    c and cin are m x m, and cin is read at row >= col only; any m, k >= 1;
+    rows may be strided. c must not overlap a (cin may be c). Returns the cs."""
+    problems = list(problems)
+    if not problems:
+        return []
+    tab, keep = _muon_syrk_table("muon_syrk_grouped_", problems)
+    _muon_syrk(tab, len(problems), alpha, beta, _stream(stream, problems[0][1].device))
+    return [p[1] for p in problems]
+
+
+def _muon_symmetric(name, symmetric):
+    if not isinstance(symmetric, bool):
+        raise ValueError("%s: symmetric must be a bool, not %r" % (name, symmetric))
+    return symmetric
+
+
 class MuonPlan:
     """Newton-Schulz over a fixed list of tensors: dirs[t] is a flat bf16
     device tensor of rows * cols elements (a tensor's view in a direction
@@ -774,9 +816,15 @@ class MuonPlan:
     run(steps) -> the orthogonalised tensors, as rows x cols views of the
     workspace that the next run overwrites: 2 launches for the norms, the
     scale, and per step 3 grouped GEMM launches per 32 tensors (X X^T; b A + c
-    A A; a X + B X; for rows > cols X^T X and a X + X B)."""
+    A A; a X + B X; for rows > cols X^T X and a X + X B).
 
-    def __init__(self, dirs, shapes):
+    symmetric=True runs the first two products, whose results are symmetric,
+    on the symmetric kernel (muon_syrk_grouped_: the lower triangle of tiles,
+    mirrored) and the third on the general one as before; same workspace,
+    same launch count."""
+
+    def __init__(self, dirs, shapes, symmetric=False):
+        self.symmetric = _muon_symmetric("MuonPlan", symmetric)
         dirs, shapes = list(dirs), [tuple(int(x) for x in s) for s in shapes]
         if not dirs or len(dirs) != len(shapes):
             raise ValueError("MuonPlan: at least one tensor, and a (rows, cols) for each")
@@ -791,6 +839,7 @@ class MuonPlan:
         self.norms = SegNorm(dirs)
         self.sq = torch.zeros(len(dirs) + 1, dtype=torch.float64, device=self.device)
         off, self.x, gram, quint, xmul = 0, ([], []), ([], []), [], ([], [])
+        sgram, squint = ([], []), []
 
         def take(n):
             nonlocal off
@@ -802,13 +851,20 @@ class MuonPlan:
             x = [take(r * c).view(r, c) for _ in range(2)]
             a, b = (take(s * s).view(s, s) for _ in range(2))
             quint.append((a, a, b, a))
+            squint.append((a, b, a))
             for p in range(2):
                 self.x[p].append(x[p])
                 # rows > cols: the short side's Gram matrix, with no transposed copy
                 gram[p].append((x[p], x[p], a, None, tall, not tall))
+                sgram[p].append((x[p], a, None, tall))
                 xmul[p].append((x[p], b, x[1 - p], x[p]) if tall else (b, x[p], x[1 - p], x[p]))
-        self._tables = [[_muon_table("MuonPlan", t) for t in (gram[p], quint, xmul[p])]
-                        for p in range(2)]
+        if symmetric:
+            self._tables = [[_muon_syrk_table("MuonPlan", sgram[p]),
+                             _muon_syrk_table("MuonPlan", squint),
+                             _muon_table("MuonPlan", xmul[p])] for p in range(2)]
+        else:
+            self._tables = [[_muon_table("MuonPlan", t) for t in (gram[p], quint, xmul[p])]
+                            for p in range(2)]
 
     def run(self, steps=5, stream=None):
         if isinstance(steps, bool) or not isinstance(steps, int) or not 1 <= steps <= 16:
@@ -817,26 +873,29 @@ class MuonPlan:
         self.norms.run("sq", out=self.sq, stream=stream)
         muon_scale_batch_(self.dirs, [x.view(-1) for x in self.x[0]], self.sq, stream=stream)
         s = _stream(stream, self.device)
+        first = _muon_syrk if self.symmetric else _muon_gemm
         for i in range(steps):
             gram, quint, xmul = self._tables[i & 1]
-            _muon_gemm(gram[0], n, 0.0, 1.0, s)
-            _muon_gemm(quint[0], n, b, c, s)
+            first(gram[0], n, 0.0, 1.0, s)
+            first(quint[0], n, b, c, s)
             _muon_gemm(xmul[0], n, a, 1.0, s)
         return self.x[steps & 1]
 
 
-def muon_newton_schulz_(tensors2d, steps=5, stream=None):
+def muon_newton_schulz_(tensors2d, steps=5, stream=None, symmetric=False):
     """Every tensor (bf16, contiguous, viewed as shape[0] x the rest) replaced
     by its Newton-Schulz orthogonalisation, `steps` iterations of the quintic
     on t / (|t|_F + 1e-7): the whole chain of a MuonPlan made for this call.
-    An optimizer keeps its plan instead (MuonPlan)."""
+    An optimizer keeps its plan instead (MuonPlan). symmetric: MuonPlan's."""
+    _muon_symmetric("muon_newton_schulz_", symmetric)
     ts = list(tensors2d)
     if not ts:
         return ts
     for t in ts:
         if t.dim() < 2 or not t.is_contiguous():
             raise ValueError("muon_newton_schulz_: contiguous tensors of 2 or more dimensions")
-    plan = MuonPlan([t.view(-1) for t in ts], [(t.shape[0], t.numel() // t.shape[0]) for t in ts])
+    plan = MuonPlan([t.view(-1) for t in ts], [(t.shape[0], t.numel() // t.shape[0]) for t in ts],
+                    symmetric)
     for t, x in zip(ts, plan.run(steps, stream)):
         t.view(x.shape).copy_(x)
     return ts

@@ -1782,6 +1782,7 @@ class _ShardedMuon(_ShardedSGD):
     _kf_dtypes = ("float32",)
     _kf_dtype_words = "f32"
     _kf_ns_steps = 5
+    _kf_symmetric = False
 
     def _kf_new_group(self):
         return {"moms": None, "first": True, "db": None, "plan": None, "at": None, "scale": None}
@@ -1805,7 +1806,7 @@ class _ShardedMuon(_ShardedSGD):
             shapes.append((rows, cols))
             G["at"].append(v)
             G["scale"].append(max(1.0, rows / cols) ** 0.5)
-        G["plan"] = ops.MuonPlan(dirs, shapes) if dirs else None
+        G["plan"] = ops.MuonPlan(dirs, shapes, self._kf_symmetric) if dirs else None
 
     def step(self, closure=None):
         from . import ops
@@ -1842,7 +1843,7 @@ class _ShardedMuon(_ShardedSGD):
 
 
 def ShardedMuonOptimizer(optimizer, named_parameters=None, exchange=None, bucket_bytes=32 << 20,
-                         ns_steps=5):
+                         ns_steps=5, symmetric=False):
     """Muon (Jordan et al. 2024: momentum, then an update orthogonalised by a
     quintic Newton-Schulz iteration) on the sharded step.
     Every step is
@@ -1861,7 +1862,9 @@ def ShardedMuonOptimizer(optimizer, named_parameters=None, exchange=None, bucket
     Newton-Schulz work (bf16 products on the matrix units, one grouped launch
     per product for all tensors of a bucket group: ops.MuonPlan) is therefore
     REPLICATED on every rank; partitioning it needs a second exchange and is
-    not offered.
+    not offered. symmetric=True runs X X^T and b A + c A A, whose results are
+    symmetric, on the symmetric-product kernel (ops.muon_syrk_grouped_: only
+    the lower triangle of tiles is computed, then mirrored); off by default.
 
     `optimizer` must be a torch.optim.SGD (TypeError otherwise), which lends
     lr, momentum, nesterov and weight_decay (decoupled here), read at every
@@ -1889,6 +1892,8 @@ def ShardedMuonOptimizer(optimizer, named_parameters=None, exchange=None, bucket
                 raise ValueError("%s: %s=True is not supported" % (name, option))
     if isinstance(ns_steps, bool) or not isinstance(ns_steps, int) or not 1 <= ns_steps <= 16:
         raise ValueError("%s: ns_steps must be an int in [1, 16], not %r" % (name, ns_steps))
+    if not isinstance(symmetric, bool):
+        raise ValueError("%s: symmetric must be a bool, not %r" % (name, symmetric))
     opt = _wrap(optimizer, _ShardedMuon)
     opt._kf_setup(named_parameters, exchange, bucket_bytes)
     for p in opt._kf_params:
@@ -1903,7 +1908,7 @@ def ShardedMuonOptimizer(optimizer, named_parameters=None, exchange=None, bucket
             if not hasattr(ex, method):
                 raise ValueError("%s needs an exchange with %s() (collective.Exchange or "
                                  "exchange.NativeExchange)" % (name, method))
-    opt._kf_ns_steps = ns_steps
+    opt._kf_ns_steps, opt._kf_symmetric = ns_steps, symmetric
     return opt
 
 

@@ -111,6 +111,6 @@ def ShardedLionOptimizer(optimizer, named_parameters, **kwargs):
 
 def ShardedMuonOptimizer(optimizer, named_parameters, **kwargs):
     """kungfu_amd.optimizers.ShardedMuonOptimizer with `named_parameters`
-    positional. Keywords pass through: `exchange`, `bucket_bytes` and
-    `ns_steps`."""
+    positional. Keywords pass through: `exchange`, `bucket_bytes`,
+    `ns_steps` and `symmetric`."""
     return _opt.ShardedMuonOptimizer(optimizer, named_parameters=named_parameters, **kwargs)

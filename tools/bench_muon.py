@@ -1,6 +1,8 @@
 """Time Muon's Newton-Schulz chain (ops.MuonPlan: the grouped MFMA GEMM) beside
-the same chain written with torch.matmul in bf16, and the whole world-1 step
-of ShardedMuonOptimizer beside ShardedSGDOptimizer's.
+the same chain written with torch.matmul in bf16 and beside the plan with
+symmetric=True (the symmetric-product kernel for X X^T and b A + c A A), and
+the whole world-1 step of ShardedMuonOptimizer, general and symmetric, beside
+ShardedSGDOptimizer's.
 
   python tools/bench_muon.py [--window 0.5] [--repeats 5] [--only CASE]
                              [--out profiles/muon/bench.jsonl]
@@ -8,7 +10,7 @@ of ShardedMuonOptimizer beside ShardedSGDOptimizer's.
 Every figure is the median of `repeats` windows (the smallest and the largest
 are recorded beside it); a window is as many runs as fill `window` seconds,
 sized from a first short window, between HIP events, after 3 warm-up runs,
-four buffer sets used in turn. The two sides of a case alternate window by
+four buffer sets used in turn. The sides of a case alternate window by
 window. One JSON line per case. Needs a GPU."""
 import argparse
 import json
@@ -101,15 +103,20 @@ def timed(sides, window, repeats):
 
 def chain_case(name, shapes, window, repeats, steps=5):
     sets = [[torch.randn(s, device="cuda").to(torch.bfloat16) for s in shapes] for _ in range(4)]
-    plans = [ops.MuonPlan([t.view(-1) for t in ts], [(t.shape[0], t.numel() // t.shape[0]) for t in ts])
-             for ts in sets]
-    ours, theirs = timed([[lambda p=p: p.run(steps) for p in plans],
-                          [lambda ts=ts: torch_chain(ts, steps) for ts in sets]], window, repeats)
+    plans, sym = ([ops.MuonPlan([t.view(-1) for t in ts],
+                                [(t.shape[0], t.numel() // t.shape[0]) for t in ts], symmetric)
+                   for ts in sets] for symmetric in (False, True))
+    ours, theirs, syrk = timed([[lambda p=p: p.run(steps) for p in plans],
+                                [lambda ts=ts: torch_chain(ts, steps) for ts in sets],
+                                [lambda p=p: p.run(steps) for p in sym]], window, repeats)
+    same = all(torch.equal(x, y) for x, y in zip(plans[0].run(steps), sym[0].run(steps)))
     worst = max(float((x.float() - y.float()).abs().max())
                 for x, y in zip(plans[0].run(steps), torch_chain(sets[0], steps)))
     f = flops(shapes, steps)
     return {"case": name, "tensors": len(shapes), "steps": steps, "grouped": ours,
             "torch_matmul": theirs, "torch_over_grouped": theirs["ms"] / ours["ms"],
+            "symmetric": syrk, "symmetric_over_grouped": syrk["ms"] / ours["ms"],
+            "symmetric_same_bytes": same,
             "grouped_tflops": f / ours["ms"] / 1e9, "torch_tflops": f / theirs["ms"] / 1e9,
             "max_abs_difference": worst}
 
@@ -119,17 +126,18 @@ def step_case(window, repeats):
     from kungfu_amd.exchange import NativeExchange
     from kungfu_amd.optimizers import ShardedMuonOptimizer, ShardedSGDOptimizer
     opts, keep = [], []
-    for make in (ShardedMuonOptimizer, ShardedSGDOptimizer):
+    for make in (ShardedMuonOptimizer, ShardedSGDOptimizer,
+                 lambda o, **kw: ShardedMuonOptimizer(o, symmetric=True, **kw)):
         ps = [torch.nn.Parameter(torch.randn(s, device="cuda") * 0.05) for s in resnet50_convs()]
         ex = NativeExchange()
         opts.append(make(torch.optim.SGD(ps, lr=0.02, momentum=0.95, nesterov=True), exchange=ex))
         for p in ps:
             p.grad = torch.randn_like(p)
         keep.append((ps, ex))
-    muon, sgd = timed([[o.step] for o in opts], window, repeats)
+    muon, sgd, sym = timed([[o.step] for o in opts], window, repeats)
     for _, ex in keep:
         ex.close()
-    return {"case": "step_world1_resnet50_convs", "muon": muon, "sgd": sgd}
+    return {"case": "step_world1_resnet50_convs", "muon": muon, "sgd": sgd, "muon_symmetric": sym}
 
 
 def main():
