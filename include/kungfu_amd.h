@@ -881,6 +881,64 @@ int kf_sign1_pack_ef_batch(const void *const *grads, void *const *residuals, voi
 int kf_sign1_fold_batch(const void *const *packed, void *const *out_shards, const size_t *q, int nb,
                         int world, KungFu_Datatype dt, int np, void *stream);
 
+/* ---- Top-k gradient wire ----------------------------------------------------
+ *
+ * What phase 1 of a sharded step carries under kf_exchange_reduce_shards_
+ * topk_batch (kungfu_amd/csrc/kf_topk.hip; tests/topk_ref.py
+ * restates it in numpy): of every block of 64 consecutive elements of a piece
+ * the k elements of largest magnitude, k in {1, 2, 4, 8}, each as its f32
+ * value and a byte that says where in the block it stood, and an f32 residual
+ * per element that keeps what was not sent for later steps (Deep Gradient
+ * Compression, sparsified SGD with memory): 5 k / 64 bytes per element, 0.078,
+ * 0.156, 0.3125 and 0.625. The selection is per block, so a piece has a fixed
+ * size and the result is deterministic. The residual is part of the format.
+ *
+ * Pack, per block; g is the gradient widened to f32 (exactly), r the residual:
+ *   s      = g + r                one f32 add
+ *   key[i] = bits(s[i]) & 0x7fffffff, compared as an unsigned integer: NaN and
+ *            inf order above every finite value, +0 and -0 are equal
+ *   k rounds; each takes the element not yet taken with the largest key, among
+ *            equal keys the one with the smallest index in the block. A block
+ *            with fewer than k non-zero elements still sends k entries.
+ *   r'[i]  = +0.0 where element i was taken; +0.0 where it was not taken and
+ *            s[i] is not finite (it is dropped for good: the block's sent NaN
+ *            or inf already marks the step); s[i], bits unchanged, otherwise
+ * Fold, for a shard of q elements and the `world` pieces received for it:
+ *   acc = +0.0 everywhere; for the ranks in order and every entry of a piece
+ *   acc[64 * block + (index & 63)] += value in f32; then / np (np > 0) and one
+ *   RNE narrowing, as kf_mx8_fold_batch's. A well-formed piece names every
+ *   index at most once per block; the mask keeps a malformed index inside its
+ *   block, and of two entries of one (rank, block) with the same index one
+ *   may be lost.
+ *
+ * The packed form of one bucket of `count` elements over `world` ranks is
+ * `world` pieces, piece j what rank j receives: q = count / world elements as
+ * (q / 64) * k f32 values, block after block, in selection order within a
+ * block (the value is s itself, bits unchanged); then (q / 64) * k index bytes
+ * (0..63) in the same order; then zero bytes up to the next multiple of 16.
+ * Pieces lie kf_topk_piece_bytes(q, k) = ceil(5 * k * (q / 64) / 16) * 16
+ * apart (0 for a k that is not 1, 2, 4 or 8). The count % world tail is not
+ * packed, and its residuals are neither read nor written.
+ *
+ * kf_topk_pack_ef_batch: grads[b] (dt: f32, bf16 or f16; only read) and
+ * residuals[b] (counts[b] f32 values, read and written) -> packed[b], world *
+ * kf_topk_piece_bytes(counts[b] / world, k) bytes. kf_topk_fold_batch:
+ * packed[b], the world pieces received for this rank's shard of q[b] elements
+ * -> out_shards[b] in dt. A bucket with q == 0 is not looked at. Checks, in
+ * kf_sign1_pack_ef_batch's order with k behind the world, before any HIP call:
+ * nb < 0; (nb == 0: KF_OK;) a null table; dt (KF_ERR_DTYPE); world outside
+ * [1, KF_MAX_INPUTS]; k not 1, 2, 4 or 8; np < 0 (fold); then per non-empty
+ * bucket a null pointer, q % 64 != 0, a pointer off a 16-byte boundary; then
+ * (pack) a null residual table, a null residual, a residual off a 16-byte
+ * boundary. All KF_ERR_ARG but the dtype's, each with its kf_last_error()
+ * text. */
+size_t kf_topk_piece_bytes(size_t q, int k);
+int kf_topk_pack_ef_batch(const void *const *grads, void *const *residuals, void *const *packed,
+                          const size_t *counts, int nb, int world, KungFu_Datatype dt, int k,
+                          void *stream);
+int kf_topk_fold_batch(const void *const *packed, void *const *out_shards, const size_t *q, int nb,
+                       int world, KungFu_Datatype dt, int np, int k, void *stream);
+
 /* ---- Lion: a sign update, dense or over a 2-bit wire ------------------------
  *
  * Lion (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms") on
@@ -1655,6 +1713,14 @@ int kf_exchange_reduce_shards_mx8_sr_batch(kf_exchange_t *ex, void *const *grads
 int kf_exchange_reduce_shards_sign1_batch(kf_exchange_t *ex, void *const *grads,
                                           void *const *residuals, const size_t *counts, int nb,
                                           KungFu_Datatype dt, int *np, void *stream);
+/* The same over the top-k gradient wire (above) with k entries per block of
+ * 64: kf_topk_pack_ef_batch, the all-to-all of kf_topk_piece_bytes(q, k) bytes
+ * per rank and bucket, kf_topk_fold_batch with / world fused; the same body
+ * again. k must be 1, 2, 4 or 8 (KF_ERR_ARG, checked first) and q a multiple
+ * of 64. *np = 0. */
+int kf_exchange_reduce_shards_topk_batch(kf_exchange_t *ex, void *const *grads,
+                                         void *const *residuals, const size_t *counts, int nb,
+                                         KungFu_Datatype dt, int k, int *np, void *stream);
 /* recv[r * n + k] = rank r's send[k], k < n: the transport's byte all_gather
  * of n doubles per rank (device pointers; send may be recv + rank * n). World
  * 1 on the built-in transport is a copy. */

@@ -172,6 +172,10 @@ EXPORTED = (
     "kf_sign1_pack_ef_batch",
     "kf_sign1_fold_batch",
     "kf_exchange_reduce_shards_sign1_batch",
+    "kf_topk_piece_bytes",
+    "kf_topk_pack_ef_batch",
+    "kf_topk_fold_batch",
+    "kf_exchange_reduce_shards_topk_batch",
     "kf_muon_tile",
     "kf_muon_momentum_batch",
     "kf_muon_scale_batch",
@@ -770,6 +774,16 @@ def load():
                         lib.kf_exchange_reduce_shards_mx8_ef_batch)):
         getattr(lib, name).argtypes = like.argtypes
         getattr(lib, name).restype = like.restype
+    # the top-k wire's take an int k besides: before the stream, or before np (the exchange's)
+    lib.kf_topk_piece_bytes.argtypes = [c_size_t, c_int]
+    lib.kf_topk_piece_bytes.restype = c_size_t
+    for name, like, at in (("kf_topk_pack_ef_batch", lib.kf_mx8_pack_ef_batch, -1),
+                           ("kf_topk_fold_batch", lib.kf_mx8_fold_batch, -1),
+                           ("kf_exchange_reduce_shards_topk_batch",
+                            lib.kf_exchange_reduce_shards_mx8_ef_batch, -2)):
+        types = list(like.argtypes)
+        getattr(lib, name).argtypes = types[:at] + [c_int] + types[at:]
+        getattr(lib, name).restype = c_int
     lib.kf_lion_sign_bytes.argtypes = [c_size_t]
     lib.kf_lion_sign_bytes.restype = c_size_t
     lib.kf_lion_update_batch.argtypes = [P(c_void_p), P(c_void_p), P(c_void_p), P(c_size_t),

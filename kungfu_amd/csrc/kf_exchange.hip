@@ -865,15 +865,17 @@ static Reduced reduce_to_shards(kf_exchange &x, const void *const *sends, void *
 // transport call is skipped.
 // `pack` is the entry that fills the pieces: kf_mx8_pack_batch, its
 // error-feedback or stochastic-rounding variant, or
-// kf_sign1_pack_ef_batch; the piece size, the fold and the shard lengths'
-// block go with it and are the MXFP8 wire's unless set.
+// kf_sign1_pack_ef_batch or kf_topk_pack_ef_batch; the piece size, the fold
+// and the shard lengths' block go with it and are the MXFP8 wire's unless set
+// (callables, so that the top-k wire's carry its k).
 struct WirePack {
     const char *name;
     std::function<int(void *const *packed, hipStream_t s)> run;
-    size_t (*piece_bytes)(size_t q) = kf_mx8_piece_bytes;
-    const char *fold_name           = "kf_mx8_fold_batch";
-    int (*fold)(const void *const *packed, void *const *shards, const size_t *q, int nb, int world,
-                KungFu_Datatype dt, int np, void *stream) = kf_mx8_fold_batch;
+    std::function<size_t(size_t q)> piece_bytes = kf_mx8_piece_bytes;
+    const char *fold_name                       = "kf_mx8_fold_batch";
+    std::function<int(const void *const *packed, void *const *shards, const size_t *q, int nb,
+                      int world, KungFu_Datatype dt, int np, void *stream)>
+        fold          = kf_mx8_fold_batch;
     unsigned block    = 32;
     const char *phase = "phase-1 collective (MXFP8 wire)";
 };
@@ -2020,6 +2022,28 @@ int kf_exchange_reduce_shards_sign1_batch(kf_exchange_t *ex, void *const *grads,
          },
          kf_sign1_piece_bytes, "kf_sign1_fold_batch", kf_sign1_fold_batch, 64,
          "phase-1 collective (1-bit wire)"});
+}
+
+int kf_exchange_reduce_shards_topk_batch(kf_exchange_t *ex, void *const *grads,
+                                         void *const *residuals, const size_t *counts, int nb,
+                                         KungFu_Datatype dt, int k, int *np, void *stream)
+{
+    if (k != 1 && k != 2 && k != 4 && k != 8) {
+        return fail(KF_ERR_ARG, "kf_exchange_reduce_shards_topk_batch: k must be 1, 2, 4 or 8");
+    }
+    return exchange_reduce_wire(
+        "kf_exchange_reduce_shards_topk_batch", ex, grads, residuals, true, counts, nb, dt, np,
+        stream,
+        {"kf_topk_pack_ef_batch",
+         [&](void *const *packed, hipStream_t s) {
+             return kf_topk_pack_ef_batch(grads, residuals, packed, counts, nb, ex->world, dt, k, s);
+         },
+         [k](size_t q) { return kf_topk_piece_bytes(q, k); }, "kf_topk_fold_batch",
+         [k](const void *const *packed, void *const *shards, const size_t *q, int n, int world,
+             KungFu_Datatype t, int div, void *s) {
+             return kf_topk_fold_batch(packed, shards, q, n, world, t, div, k, s);
+         },
+         64, "phase-1 collective (top-k wire)"});
 }
 
 int kf_exchange_adam_gated_batch(kf_exchange_t *ex, void *const *params, void *const *grads,

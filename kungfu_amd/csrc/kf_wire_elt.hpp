@@ -1,7 +1,7 @@
 // kf_wire_elt.hpp — what the gradient wires' kernels share (kf_mx8.hip,
-// kf_sign1.hip): the pack's load of a lane's 8 elements, and the fold's
-// epilogue over a lane's 16 f32 accumulators (/np, one narrowing, 16-byte
-// stores). The formats and their cross-lane steps are each file's own.
+// kf_sign1.hip, kf_topk.hip): the pack's load of a lane's 8 elements, and the
+// fold's epilogue over a lane's 16 or 4 f32 accumulators (/np, one narrowing,
+// 16-byte stores). The formats and their cross-lane steps are each file's own.
 #pragma once
 #include "kf_sgd_elt.hpp"
 
@@ -68,6 +68,31 @@ __device__ __forceinline__ void wire_store16(void *out, size_t u, float (&acc)[1
             }
             st_u4<0>(out, 2 * u + w, raw);
         }
+    }
+}
+
+// The same epilogue over a lane's 4 sums (kf_topk.hip's read-out): unit u is
+// 4 elements, stored as 16 bytes (f32) or 8 (bf16, f16).
+typedef unsigned int wire_u32x2 __attribute__((ext_vector_type(2)));
+template <typename T, int DIV>
+__device__ __forceinline__ void wire_store4(void *out, size_t u, float (&acc)[4], const Div &d)
+{
+    if constexpr (DIV != 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = SgdElt<float>::div<DIV == 1>(acc[i], d);
+    }
+    if constexpr (std::is_same<T, float>::value) {
+        st_u4<0>(out, u,
+                 u32x4{__float_as_uint(acc[0]), __float_as_uint(acc[1]), __float_as_uint(acc[2]),
+                       __float_as_uint(acc[3])});
+    } else {
+        wire_u32x2 raw;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            raw[i] = static_cast<unsigned>(wire_narrow<T>(acc[2 * i])) |
+                     (static_cast<unsigned>(wire_narrow<T>(acc[2 * i + 1])) << 16);
+        }
+        reinterpret_cast<wire_u32x2 *>(out)[u] = raw;
     }
 }
 

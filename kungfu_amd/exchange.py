@@ -32,7 +32,8 @@ from .base import OP, OP_NAMES
 from .ops import kungfu_dtype
 
 ALGOS = {"auto": 0, "rs": 1, "a2a": 2, "rs_avg": 3}
-GRAD_WIRES = (None, "mx8", "sign1")  # NativeExchange.set_grad_wire
+GRAD_WIRES = (None, "mx8", "sign1", "topk")  # NativeExchange.set_grad_wire
+TOPK_K = (1, 2, 4, 8)                # set_grad_wire("topk", k=...): entries per block of 64
 # kf_exchange_phase_times' order: phase 1 (reduce-scatter, or all-to-all for
 # the rank-order fold), phase 2 (/np epilogue or the fold), phase 3
 # (all-gather), the SMA blend
@@ -136,7 +137,7 @@ class NativeExchange:
         self.groups = int(groups)
         return self
 
-    def set_grad_wire(self, wire, *, error_feedback=False, rounding="nearest", seed=0):
+    def set_grad_wire(self, wire, *, error_feedback=False, rounding="nearest", seed=0, k=4):
         """What phase 1 of the sharded steps carries: None (the default), the
         gradient buckets in their own dtype, or "mx8", block-scaled MXFP8 (one
         E4M3 code per element and one E8M0 scale byte per 32: 1.03125 bytes per
@@ -184,9 +185,25 @@ class NativeExchange:
         gated step has still consumed its gradient; there is no per-step host
         state, so a captured graph replays it. Without error_feedback=True,
         or with rounding="stochastic", the wire is refused: a sign wire
-        without memory does not converge."""
+        without memory does not converge.
+
+        "topk" (with error_feedback=True, part of the format as well;
+        DESIGN.md §29): of every block of 64 elements the `k` (1, 2, 4 or 8;
+        4 by default) largest magnitudes of g + r as f32 values with a byte
+        for their place: 5 k / 64 bytes per element, 0.078 at k = 1 and 0.3125
+        at k = 4. reduce_shards_ is kf_exchange_reduce_shards_topk_batch;
+        shard lengths must be multiples of 64. What is sent is sent exactly;
+        everything else stays in the f32 residual until it is among its
+        block's k largest, and a value that is not finite and not sent is
+        dropped. What is said above of the residual holds here too. `k` is
+        this wire's alone: with another wire it must be left at its default.
+        Without error_feedback=True, or with rounding="stochastic", the wire
+        is refused."""
         if wire not in GRAD_WIRES:
-            raise ValueError("grad_wire must be None, 'mx8' or 'sign1' (got %r)" % (wire,))
+            raise ValueError("grad_wire must be None, 'mx8', 'sign1' or 'topk' (got %r)" % (wire,))
+        if isinstance(k, bool) or k not in TOPK_K or (wire != "topk" and k != 4):
+            raise ValueError("grad_wire k must be 1, 2, 4 or 8, and is the 'topk' wire's alone "
+                             "(got k=%r with wire %r)" % (k, wire))
         if rounding not in ("nearest", "stochastic"):
             raise ValueError("grad_wire rounding must be 'nearest' or 'stochastic' (got %r)"
                              % (rounding,))
@@ -195,14 +212,14 @@ class NativeExchange:
             raise ValueError("grad_wire: error_feedback and rounding need a wire")
         if error_feedback and stochastic:
             raise ValueError("grad_wire: error_feedback or stochastic rounding, not both")
-        if wire == "sign1" and not error_feedback:
-            raise ValueError("grad_wire 'sign1' needs error_feedback=True and rounding='nearest': "
-                             "the residual is part of the format")
+        if wire in ("sign1", "topk") and not error_feedback:
+            raise ValueError("grad_wire %r needs error_feedback=True and rounding='nearest': "
+                             "the residual is part of the format" % (wire,))
         if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
             raise ValueError("grad_wire seed must be an int in [0, 2**64), not %r" % (seed,))
         self._wire = wire
         self._wire_mode = "ef" if error_feedback else "sr" if stochastic else None
-        self._wire_seed, self._wire_step = seed, 0
+        self._wire_seed, self._wire_step, self._wire_k = seed, 0, int(k)
         return self
 
     def grad_residuals(self):
@@ -581,7 +598,8 @@ class NativeExchange:
         the fold or under rs_avg, 1 at world 1 on the built-in transport.
         Under set_grad_wire("mx8"): kf_exchange_reduce_shards_mx8_batch (or its
         _ef / _sr variant, as set_grad_wire's options say), and 0; under
-        "sign1": kf_exchange_reduce_shards_sign1_batch, and 0."""
+        "sign1": kf_exchange_reduce_shards_sign1_batch, and 0; under "topk":
+        kf_exchange_reduce_shards_topk_batch with set_grad_wire's k, and 0."""
         grads = list(grad_buckets)
         if grads:
             self._check(grads)
@@ -593,10 +611,11 @@ class NativeExchange:
             tail = (_arr(ctypes.c_size_t, [g.numel() for g in grads]), len(grads), dt)
             end = (ctypes.byref(np_), torch.cuda.current_stream(self.device).cuda_stream)
             mode = getattr(self, "_wire_mode", None)
-            if mode == "ef":  # "sign1" has no other mode
+            if mode == "ef":  # "sign1" and "topk" have no other mode
                 res = _lib.ptr_array([r.data_ptr() for r in self._grad_residuals(grads)])
-                name = "kf_exchange_reduce_shards_%s_batch" % {"mx8": "mx8_ef", "sign1": "sign1"}[wire]
-                rc = getattr(self.lib, name)(*tabs, res, *tail, *end)
+                name = "kf_exchange_reduce_shards_%s_batch" % {"mx8": "mx8_ef"}.get(wire, wire)
+                own = (self._wire_k,) if wire == "topk" else ()
+                rc = getattr(self.lib, name)(*tabs, res, *tail, *own, *end)
             elif mode == "sr":
                 name = "kf_exchange_reduce_shards_mx8_sr_batch"
                 rc = self.lib.kf_exchange_reduce_shards_mx8_sr_batch(

@@ -1075,9 +1075,9 @@ def _mx8_pack_variant(name, grads, world, packed, stream, call, piece_bytes=mx8_
     return packed
 
 
-def _wire_pack_ef(name, piece_bytes, grads, residuals, world, packed, stream):
+def _wire_pack_ef(name, piece_bytes, grads, residuals, world, packed, stream, extra=()):
     """An error-feedback pack (kf_<name>): the residuals' checks, then
-    _mx8_pack_variant's."""
+    _mx8_pack_variant's. `extra`: the entry's own arguments before the stream."""
     grads, residuals = list(grads), list(residuals)
     if len(residuals) != len(grads) or any(
             r.dtype != torch.float32 or r.numel() != g.numel() or not r.is_contiguous()
@@ -1088,12 +1088,14 @@ def _wire_pack_ef(name, piece_bytes, grads, residuals, world, packed, stream):
     entry = "kf_" + name.rstrip("_")
     return _mx8_pack_variant(
         name, grads, world, packed, stream,
-        lambda lib, g, p, cnt, nb, dt, s: getattr(lib, entry)(g, res, p, cnt, nb, int(world), dt, s),
+        lambda lib, g, p, cnt, nb, dt, s: getattr(lib, entry)(g, res, p, cnt, nb, int(world), dt,
+                                                              *extra, s),
         piece_bytes)
 
 
-def _wire_fold(name, piece_bytes, packed, out_shards, world, np_, stream):
-    """A wire's fold (kf_<name>): one shard per packed tensor of world pieces."""
+def _wire_fold(name, piece_bytes, packed, out_shards, world, np_, stream, extra=()):
+    """A wire's fold (kf_<name>): one shard per packed tensor of world pieces.
+    `extra`: the entry's own arguments before the stream."""
     packed, outs, world = list(packed), list(out_shards), int(world)
     if len(packed) != len(outs):
         raise ValueError("%s: one shard per packed tensor" % name)
@@ -1108,7 +1110,7 @@ def _wire_fold(name, piece_bytes, packed, out_shards, world, np_, stream):
     entry = "kf_" + name.rstrip("_")
     rc = getattr(_lib.load(), entry)(_lib.ptr_array([p.data_ptr() for p in packed]),
                                      _lib.ptr_array([o.data_ptr() for o in outs]), q, len(outs),
-                                     world, int(kungfu_dtype(outs[0])), int(np_),
+                                     world, int(kungfu_dtype(outs[0])), int(np_), *extra,
                                      _stream(stream, outs[0].device))
     _lib.check(rc, entry, source="")
     return outs
@@ -1173,6 +1175,49 @@ def sign1_fold_batch_(packed, out_shards, world, np_=0, stream=None):
     uint8, world * sign1_piece_bytes(q) bytes for a shard of q elements (a
     multiple of 64)."""
     return _wire_fold("sign1_fold_batch_", sign1_piece_bytes, packed, out_shards, world, np_, stream)
+
+
+# -- the top-k gradient wire (include/kungfu_amd.h, DESIGN.md §29) -------------
+
+TOPK_BLOCK = 64                  # elements per selection
+TOPK_K = (1, 2, 4, 8)            # entries sent per block
+
+
+def _topk_k(name, k):
+    if isinstance(k, bool) or k not in TOPK_K:
+        raise ValueError("%s: k must be 1, 2, 4 or 8 (got %r)" % (name, k))
+    return int(k)
+
+
+def topk_piece_bytes(q, k):
+    """The bytes of one packed piece of q elements (kf_topk_piece_bytes):
+    q // 64 * k f32 values, as many index bytes, rounded up to 16."""
+    return int(_lib.load().kf_topk_piece_bytes(int(q), _topk_k("topk_piece_bytes", k)))
+
+
+def topk_pack_ef_batch_(grads, residuals, world, k, packed=None, stream=None):
+    """Every flat f32, bf16 or f16 bucket of `grads` as `world` packed top-k
+    pieces (kf_topk_pack_ef_batch), all buckets in one launch: per block of 64
+    elements the k (1, 2, 4 or 8) largest magnitudes of s = g + r, bits
+    unchanged, and their places in the block, largest first and the smaller
+    index first among equals; residuals[b] (f32, grads[b]'s length) is left as
+    +0.0 where an element was sent or is not finite and s elsewhere. packed[b]
+    is a uint8 tensor of world * topk_piece_bytes(numel // world, k) bytes, new
+    unless given. numel // world must be a multiple of 64; the numel % world
+    tail is not packed and its residuals are not touched. grads are only read."""
+    k = _topk_k("topk_pack_ef_batch_", k)
+    return _wire_pack_ef("topk_pack_ef_batch_", lambda q: topk_piece_bytes(q, k), grads, residuals,
+                         world, packed, stream, (k,))
+
+
+def topk_fold_batch_(packed, out_shards, world, k, np_=0, stream=None):
+    """out_shards[b] = (the entries of the `world` pieces of packed[b], added
+    in f32 in rank order where their indices say, zeros elsewhere) / np_
+    (np_ > 0), narrowed once (kf_topk_fold_batch): packed[b] is uint8, world *
+    topk_piece_bytes(q, k) bytes for a shard of q elements (a multiple of 64)."""
+    k = _topk_k("topk_fold_batch_", k)
+    return _wire_fold("topk_fold_batch_", lambda q: topk_piece_bytes(q, k), packed, out_shards,
+                      world, np_, stream, (k,))
 
 
 # -- LAMB (include/kungfu_amd.h "LAMB", DESIGN.md §17) -------------------------
